@@ -367,6 +367,10 @@ def main():
     ap.add_argument("--batch", default="", help="also measure B concurrent sequences over the paged KV cache, e.g. 2,4 "
                     "(SURVEY 8(f)#1; reported under \"concurrent\", the headline value stays batch 1)")
     ap.add_argument("--tune", default="", help="debug: kernel-variant knobs key=val[,key=val] (vh_tune)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what they handed their caller — every generated id and the full-vocabulary "
+                         "scores of the last step — as DIR/<name>.npy (float64 / float32); the inputs are seeded, so two builds "
+                         "compare output for output")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -543,6 +547,10 @@ def main():
         dt = float(tt.item())
     toks = eng.generated()
     assert len(toks) == 1 + Wm + K
+    dump = None
+    if args.dump_outputs:                              # before generate() below reuses the engine; gather_vocab is collective
+        dump = {"generated_ids": np.asarray(toks, np.float64),
+                "last_step_logits": eng.gather_vocab(eng.logits).cpu().numpy().astype(np.float32)}
 
     ms_step = dt * 1e3 / K
     tok_s = K / dt
@@ -698,6 +706,11 @@ def main():
                 out["cpu_baseline"] = cpu_baseline(VitaConfig(), ctx=int(S), request=req)
             except Exception as e:  # never lose the GPU line to a host-side problem
                 out["cpu_baseline"] = {"value": None, "error": str(e)[:200]}
+        if dump:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, arr in dump.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), arr)
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": {name: list(arr.shape) for name, arr in dump.items()}}
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

@@ -318,32 +318,17 @@ def test_ops_refuse_cpu_tensors():
 
 
 def test_audio_side_files_match_reference_loaders(tmp_path):
-    """train.yaml + global_cmvn (JSON and Kaldi text) parsed as the reference's whale/cmvn.py does."""
-    import json
+    """train.yaml + global_cmvn (JSON and Kaldi text) parsed as the reference's whale/cmvn.py does (its results on the same
+    files: tests/golden/reference_pins.npz, oracle/make_golden_pins.py)."""
     import numpy as np
+    from oracle import make_golden_pins as mp
     from vita_amd.audio_config import load_cmvn, read_audio_encoder_dir
-    rng = np.random.default_rng(4)
-    n, d = 12345.0, 80
-    s1 = rng.standard_normal(d) * 40 * n
-    s2 = (rng.random(d) * 30 + (s1 / n) ** 2) * n
-    pj, pk = tmp_path / "cmvn.json", tmp_path / "global_cmvn"
-    pj.write_text(json.dumps({"mean_stat": s1.tolist(), "var_stat": s2.tolist(), "frame_num": n}))
-    pk.write_text("[\n " + " ".join(repr(float(x)) for x in s1) + f" {n!r}\n " + " ".join(repr(float(x)) for x in s2) + " 0 ]\n")
-    mean = s1 / n
-    istd = 1.0 / np.sqrt(np.maximum(s2 / n - mean * mean, 1e-20))
-    for path, is_json in ((pj, True), (pk, False)):
-        m, i = load_cmvn(str(path), is_json)
+    g = np.load(os.path.join(GOLD, "reference_pins.npz"))
+    files, mean, istd = mp.cmvn_files(str(tmp_path))
+    for kind, (path, is_json) in files.items():
+        m, i = load_cmvn(path, is_json)
         np.testing.assert_allclose(m, mean, rtol=1e-6); np.testing.assert_allclose(i, istd, rtol=1e-6)
-    if os.path.isdir("/root/reference/vita"):
-        from oracle import ref_harness as rh
-        rh.install()
-        import logging, sys, math  # noqa: F401  (the reference's kaldi loader uses names it never imports)
-        from vita.model.multimodal_encoder.whale import cmvn as rc
-        rc.logging, rc.sys = logging, sys
-        for path, is_json in ((pj, True), (pk, False)):
-            rm, ri = rc.load_cmvn(str(path), is_json)
-            m, i = load_cmvn(str(path), is_json)
-            np.testing.assert_allclose(m, rm, rtol=1e-6); np.testing.assert_allclose(i, ri, rtol=1e-6)
+        np.testing.assert_allclose(m, g[f"cmvn_{kind}_mean"], rtol=1e-6); np.testing.assert_allclose(i, g[f"cmvn_{kind}_istd"], rtol=1e-6)
     (tmp_path / "train.yaml").write_text(
         "input_dim: 80\nis_json_cmvn: false\ndataset_conf:\n  resample_conf: {resample_rate: 16000}\n"
         "  fbank_conf: {num_mel_bins: 80, frame_length: 25, frame_shift: 10, dither: 1.0}\n"
@@ -353,32 +338,25 @@ def test_audio_side_files_match_reference_loaders(tmp_path):
     np.testing.assert_allclose(side["mean"], mean, rtol=1e-6)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/vita"), reason="reference tree only exists in the build container")
 def test_video_front_end_matches_reference_function(tmp_path):
-    """The reference's OWN `_get_rawvideo_dec` (video_audio_demo.py:30-118), imported from its demo script with
-    compat/ serving `vita.*` and `decord`, against vita_amd.host.video on the same synthetic frame container."""
-    import importlib.util
+    """The reference's OWN `_get_rawvideo_dec` (video_audio_demo.py:30-118, run with compat/ serving `vita.*` and `decord`
+    and this processor; its outputs: tests/golden/reference_pins.npz, oracle/make_golden_pins.py) against vita_amd.host.video
+    on the same synthetic frame containers."""
     import sys
     import numpy as np
     import torch
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, os.path.join(root, "compat"))
+    from oracle import make_golden_pins as mp
+    sys.path.insert(0, os.path.join(ROOT, "compat"))
     mine = lambda k: k in ("vita", "decord") or k.startswith(("vita.", "decord."))   # may be oracle/ref_harness stubs
     saved = {k: sys.modules.pop(k) for k in list(sys.modules) if mine(k)}
     try:
-        spec = importlib.util.spec_from_file_location("ref_video_audio_demo", "/root/reference/video_audio_demo.py")
-        ref = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(ref)                      # module level only defines functions + imports
         from decord import VideoReader, cpu
         from vita_amd.host.image_processing import make_image_processor
         from vita_amd.host.video import get_rawvideo, sample_positions
-        rng = np.random.default_rng(0)
-        proc = make_image_processor(56)
-        for T, fps, kw in ((70, 5.0, {}), (9, 3.0, {}), (400, 10.0, {}), (120, 4.0, {"s": 3, "e": 11})):
-            path = str(tmp_path / f"v{T}.npz")
-            np.savez(path, frames=rng.integers(0, 255, size=(T, 40, 60, 3), dtype=np.uint8), fps=fps)
-            want, n_want = ref._get_rawvideo_dec(path, proc, max_frames=16, min_frames=4, video_framerate=1,
-                                                 image_aspect_ratio="pad", **kw)
+        g = np.load(os.path.join(GOLD, "reference_pins.npz"))
+        proc = make_image_processor(mp.VIDEO_PROC_SIZE)
+        for i, (path, kw) in enumerate(mp.video_cases(str(tmp_path))):
+            want, n_want = torch.from_numpy(g[f"video_{i}"]), int(g[f"video_n_{i}"])
             got, n_got = get_rawvideo(VideoReader(path, ctx=cpu(0)), proc, **kw)
             assert n_got == n_want and 4 <= n_got <= 16
             assert torch.equal(got, want)

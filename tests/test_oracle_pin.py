@@ -1,7 +1,8 @@
 """CPU: pins the numpy oracle (oracle/) — (1) against the golden vectors produced by the
 REFERENCE'S OWN modules in the build container (tests/golden/tiny_e2e.npz, oracle/make_golden.py),
 (2) live against the installed HF Mixtral (the third-party code carrying the backbone arithmetic),
-(3) live against the reference modules when /root/reference is present."""
+(3) against the reference modules' outputs on further seeded inputs (tests/golden/reference_pins.npz,
+oracle/make_golden_pins.py)."""
 import os
 
 import numpy as np
@@ -74,41 +75,32 @@ def test_mixtral_live_vs_installed_hf():
     assert_close("oracle vs installed HF", lg, lg_hf, atol=5e-6)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/vita"), reason="reference tree only exists in the build container")
 def test_live_vs_reference_modules():
-    import torch
-    from oracle import ref_harness as rh
+    """InternViT tower and Whale encoder + adapter on inputs other than tiny_e2e's, against what the reference's modules
+    computed on them (oracle/make_golden_pins.py)."""
+    from oracle import make_golden_pins as mp
+    g = np.load(os.path.join(GOLD, "reference_pins.npz"))
     cfg = VitaConfig.tiny()
-    sd = synth_state_dict(cfg, seed=11)
-    rng = np.random.default_rng(12)
-    pix = rng.standard_normal((1, 3, 56, 56)).astype(np.float32)
-    feats = (rng.standard_normal((77, 80)) * 2 + 10).astype(np.float32)
-    with torch.no_grad():
-        ref_v = rh.build_internvit(cfg, sd)(torch.from_numpy(pix)).numpy()
-        ref_a = rh.build_whale(cfg, sd)(torch.from_numpy(feats)[None], torch.tensor([77]))["inputs_embeds"][0].numpy()
-    assert_close("live vit", oe.internvit_tower(sd, cfg.vision, pix), ref_v, atol=5e-6)
-    assert_close("live whale", oe.whale_encoder(sd, cfg.audio, feats)[0], ref_a, atol=5e-6)
+    sd = synth_state_dict(cfg, seed=mp.LIVE_SEEDS[0])
+    pix, feats = mp.live_inputs()
+    assert_close("live vit", oe.internvit_tower(sd, cfg.vision, pix), g["live_vit"], atol=5e-6)
+    assert_close("live whale", oe.whale_encoder(sd, cfg.audio, feats)[0], g["live_whale"], atol=5e-6)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/vita"), reason="reference tree only exists in the build container")
 def test_live_whale_padded_batch_vs_reference():
     """two clips of different lengths in ONE reference forward (pad mask in attention, zeroing before the adapter,
-    adpter mask) against the oracle run per clip with `length`."""
-    import torch
-    from oracle import ref_harness as rh
+    adpter mask; recorded by oracle/make_golden_pins.py) against the oracle run per clip with `length`."""
+    from oracle import make_golden_pins as mp
+    g = np.load(os.path.join(GOLD, "reference_pins.npz"))
     cfg = VitaConfig.tiny()
-    sd = synth_state_dict(cfg, seed=13)
-    rng = np.random.default_rng(14)
-    T, lens = 140, [140, 97]
-    feats = (rng.standard_normal((2, T, 80)) * 3 + 12).astype(np.float32)
-    with torch.no_grad():
-        ref = rh.build_whale(cfg, sd)(torch.from_numpy(feats), torch.tensor(lens))
+    sd = synth_state_dict(cfg, seed=mp.PAD_SEEDS[0])
+    feats = mp.pad_inputs()
     for b in range(2):
-        z, mask = oe.whale_encoder(sd, cfg.audio, feats[b], length=lens[b])
-        rmask = ref["attention_mask"][b].numpy().astype(bool)
+        z, mask = oe.whale_encoder(sd, cfg.audio, feats[b], length=mp.PAD_LENS[b])
+        rmask = g["pad_mask"][b]
         assert mask.tolist() == rmask.tolist()
         # rows the reference marks valid must agree; padded rows are whatever the adapter makes of zeros in both
-        assert_close(f"padded whale clip {b}", z[rmask], ref["inputs_embeds"][b].numpy()[rmask], atol=5e-6)
+        assert_close(f"padded whale clip {b}", z[rmask], g["pad_embeds"][b][rmask], atol=5e-6)
 
 
 def test_torch_encoder_baseline_matches_the_checker():
