@@ -255,3 +255,13 @@ def test_alternative_paths(dev, knob, value):
         _run(dev, cfg, S=200, n_new=8, seed=9)
     finally:
         _lib.tune(knob, default)
+
+
+def test_attention_rows_wider_than_moe_rows(dev):
+    """nq * head_dim (32 x 128 = 4096) wider than the MoE's 2 x intermediate (2048): the prefill's bf16 plane buffers carry both the
+    attention output rows (O projection input) and the expert h rows, and must be sized for the wider of the two (they were sized for
+    the MoE alone: the attention planes ran over into the residual rows; every hidden state wrong by O(1))."""
+    cfg = VitaConfig.tiny()
+    cfg.text = TextConfig(hidden_size=1024, num_hidden_layers=2, num_attention_heads=32, num_key_value_heads=8,
+                          intermediate_size=1024, num_local_experts=8, vocab_size=2000)
+    _run(dev, cfg, S=70, n_new=4, seed=2)

@@ -702,3 +702,196 @@ def test_lmhead_argmax_vs_oracle(dev, V, H):
     _, tok2 = ops.lmhead_argmax(_dev(w2[3].astype(np.float32) * 50, dev), _dev(np.ones(H, np.float32), dev), 1e-5, _dev(w2, dev, torch.bfloat16))
     lg2 = (om.rmsnorm((w2[3].astype(np.float32) * 50)[None], np.ones(H, np.float32), 1e-5) @ w2.T)[0]
     assert int(tok2.item()) == int(np.argmax(lg2)) and int(tok2.item()) in (3, int(np.argmax(lg2)))
+
+
+# ---- past 4096 tokens: the range a 16-frame video prompt reaches (tokenizer_model_max_length = 4600) ----------------------
+# vh_attn_decode merges its 64-key splits in rounds of 64 lanes (a second round from pos 4096 on), and a paged sequence past 4096
+# tokens has more than 64 pages.  The references take the ENGINE's RoPE rows (vita_amd/engine.py rope_tables): the oracle's table
+# computes inv_freq in another order and differs from it by one fp32 ulp of the angle (up to 4.9e-4 on cos / sin past 4096), so a
+# bit-exact target does not exist and the kernels, not the table definitions, are what these tests are about.
+LONG_CTX = 73 * 64          # 4672 rows: 73 splits / pages, room for the model's 4600-token limit plus decode steps
+
+
+def _rope64(x, c, s):
+    """rotate-half RoPE of x [..., 128] in fp64 with one position's engine row c, s [64] (modeling_mixtral.py:203-241)."""
+    x = np.asarray(x, np.float64)
+    a, b = x[..., :64], x[..., 64:]
+    c, s = np.asarray(c, np.float64), np.asarray(s, np.float64)
+    return np.concatenate([a * c - b * s, b * c + a * s], -1)
+
+
+def _unrope64(y, c, s):
+    """inverse of _rope64: the pre-RoPE row whose rotation is y."""
+    y = np.asarray(y, np.float64)
+    a, b = y[..., :64], y[..., 64:]
+    return np.concatenate([a * c + b * s, b * c - a * s], -1)
+
+
+def _to_pages(logical, perm):
+    """[nkv, n_pages * 64, d] in sequence order -> the physical pool with logical page p stored in page perm[p] (perm None: as is)."""
+    if perm is None:
+        return logical.copy()
+    phys = np.empty_like(logical)
+    for p, q in enumerate(perm):
+        phys[:, q * 64:(q + 1) * 64] = logical[:, p * 64:(p + 1) * 64]
+    return phys
+
+
+def _from_pages(phys, perm):
+    if perm is None:
+        return phys
+    return np.concatenate([phys[:, q * 64:(q + 1) * 64] for q in perm], 1)
+
+
+def _steer(q_roped, target):
+    """key row k [128] with q_g . k == target exactly (fp64) for every query head g of a KV group (least-norm solution)."""
+    Q = np.asarray(q_roped, np.float64)
+    return Q.T @ np.linalg.solve(Q @ Q.T, np.full(Q.shape[0], float(target)))
+
+
+@pytest.mark.parametrize("paged", [False, True], ids=["contiguous", "paged"])
+@pytest.mark.parametrize("nq,nkv", [(32, 8), (8, 2)])
+@pytest.mark.parametrize("pos,pattern", [(63, "random"), (64, "random"), (127, "random"), (4095, "random"), (4096, "random"),
+                                         (4097, "random"), (4600, "random"), (4671, "random"), (4600, "late-max-20"),
+                                         (4600, "late-max-100"), (4600, "late-splits-underflow")])
+def test_attn_decode_long_context(dev, nq, nkv, pos, pattern, paged):
+    """vh_attn_decode (the k_dec_attn launches; the one-launch block and the batched kernel share dec_attn_finish) across the
+    64-split boundary of its merge — nsplit = ceil((pos + 1) / 64) > 64 from pos 4096 on takes a second round of 64 lanes for the
+    split statistics and partials — and across 73 pages, contiguous or through a fixed random permutation of the pages (`table`).
+    Cache rows are random (no prefill needed); checked against fp64: the output, the appended RoPE'd K row and the appended V row.
+    Score patterns that pin the merge (pos 4600: 72 splits, 8 in the second lane round):
+      late-max-20   one key of split 70 scores 25 against |s| < ~4 elsewhere: the global max lives only in the second round;
+      late-max-100  the same key 100 above the rest: a merge whose running max M skipped the second round would weight that split
+                    by exp(> 88) = inf (at a gap of 20 such a merge is still exact up to rounding: only overflow shows it);
+      late-splits-underflow  the max sits in split 0 (+60), every key of splits >= 65 (the appended one included) scores -60:
+                    their merge weights exp(-120) are exactly 0 and must drop out without a NaN."""
+    from vita_amd import ops
+    from vita_amd.engine import rope_tables
+    rng = np.random.default_rng(pos * 7 + nq + (1 if paged else 0) + 1000 * len(pattern))
+    d, G = 128, nq // nkv
+    cos, sin = rope_tables(LONG_CTX, d, 1e6)
+    c, s = cos[pos].astype(np.float64), sin[pos].astype(np.float64)
+    scale = d ** -0.5
+    qkv = rng.standard_normal((nq + 2 * nkv) * d, dtype=np.float32)
+    std = 1.0 if pattern == "random" else 0.1
+    kl = (rng.standard_normal((nkv, LONG_CTX, d), dtype=np.float32) * std).astype(np.float32)
+    vl = rng.standard_normal((nkv, LONG_CTX, d), dtype=np.float32)
+    qr = _rope64(qkv[:nq * d].reshape(nq, d), c, s)
+    if pattern != "random":
+        hi_key, hi, lo = {"late-max-20": (70 * 64 + 9, 25.0, None), "late-max-100": (70 * 64 + 9, 100.0, None),
+                          "late-splits-underflow": (5, 60.0, -60.0)}[pattern]
+        for h in range(nkv):
+            Qg = qr[h * G:(h + 1) * G]
+            kl[h, hi_key] = _steer(Qg, hi / scale).astype(np.float32)
+            if lo is not None:
+                kl[h, 65 * 64:pos] = (_steer(Qg, lo / scale)[None, :] + 0.1 * rng.standard_normal((pos - 65 * 64, d))).astype(np.float32)
+                kn = _unrope64(_steer(Qg, lo / scale), c, s)          # the appended key lies in split 71 as well
+                qkv[(nq + h) * d:(nq + h + 1) * d] = kn.astype(np.float32)
+    perm = rng.permutation(LONG_CTX // 64) if paged else None
+    table = _dev(perm, dev, torch.int32) if paged else None
+    kc, vc = _dev(_to_pages(kl, perm), dev), _dev(_to_pages(vl, perm), dev)
+    out = ops.attn_decode(_dev(qkv, dev), kc, vc, pos, _dev(cos, dev), _dev(sin, dev), nq, nkv, scale, table=table)
+    k_new = _rope64(qkv[nq * d:(nq + nkv) * d].reshape(nkv, d), c, s)
+    v_new = qkv[(nq + nkv) * d:].reshape(nkv, d)
+    K = kl[:, :pos + 1].astype(np.float64)
+    V = vl[:, :pos + 1].astype(np.float64)
+    K[:, pos], V[:, pos] = k_new, v_new
+    ref = np.empty(nq * d)
+    for hq in range(nq):
+        sc = K[hq // G] @ qr[hq] * scale
+        if pattern == "late-splits-underflow":
+            assert sc.max() - sc[65 * 64:].max() > 110          # the late splits' weights are exactly 0 in fp32
+        elif pattern != "random":
+            assert np.argmax(sc) == hi_key and sc[hi_key] - np.delete(sc, hi_key).max() > 19
+        p = np.exp(sc - sc.max())
+        ref[hq * d:(hq + 1) * d] = (p / p.sum()) @ V[hq // G]
+    kb, vb = _from_pages(to_np(kc), perm), _from_pages(to_np(vc), perm)
+    assert_close(f"appended K row at {pos}", kb[:, pos], k_new, atol=5e-5)
+    assert_close(f"appended V row at {pos}", vb[:, pos], v_new, atol=0)
+    assert_close(f"attn_decode pos={pos} {pattern}", to_np(out), ref, atol=5e-5)
+
+
+@pytest.mark.parametrize("nq,nkv", [(32, 8), (8, 2)])
+def test_rope_kv_append_paged_across_page_64(dev, nq, nkv):
+    """vh_rope_kv_append through a page table: 12 rows at positions 4090 ... 4101 cross the page boundary at 4096 (logical page 64,
+    the 65th) and land in two physical pages of a fixed random permutation of 73; q, and the K / V rows read back through the table,
+    against fp64 RoPE with the engine's rows.  Every other row of the pool must be left as it was."""
+    from vita_amd import ops
+    from vita_amd.engine import rope_tables
+    rng = np.random.default_rng(4090 + nq)
+    d, pos0, n = 128, 4090, 12
+    cos, sin = rope_tables(LONG_CTX, d, 1e6)
+    qkv = rng.standard_normal((n, (nq + 2 * nkv) * d), dtype=np.float32)
+    perm = rng.permutation(LONG_CTX // 64)
+    k0 = rng.standard_normal((nkv, LONG_CTX, d), dtype=np.float32)
+    v0 = rng.standard_normal((nkv, LONG_CTX, d), dtype=np.float32)
+    kc, vc = _dev(k0, dev), _dev(v0, dev)
+    q = ops.rope_kv_append(_dev(qkv, dev), kc, vc, _dev(cos, dev), _dev(sin, dev), pos0, nq, nkv, table=_dev(perm, dev, torch.int32))
+    c, s = cos[pos0:pos0 + n, None, :], sin[pos0:pos0 + n, None, :]
+    qr = _rope64(qkv[:, :nq * d].reshape(n, nq, d), c, s).reshape(n, nq * d)
+    kr = _rope64(qkv[:, nq * d:(nq + nkv) * d].reshape(n, nkv, d), c, s).transpose(1, 0, 2)
+    vr = qkv[:, (nq + nkv) * d:].reshape(n, nkv, d).transpose(1, 0, 2)
+    kg, vg = to_np(kc), to_np(vc)
+    kb, vb = _from_pages(kg, perm), _from_pages(vg, perm)
+    assert_close("roped q", to_np(q), qr, atol=5e-5)
+    assert_close("k rows through the table", kb[:, pos0:pos0 + n], kr, atol=5e-5)
+    assert_close("v rows through the table", vb[:, pos0:pos0 + n], vr, atol=0)
+    rows = np.ones(LONG_CTX, bool)
+    rows[[perm[p // 64] * 64 + p % 64 for p in range(pos0, pos0 + n)]] = False
+    assert np.array_equal(kg[:, rows], k0[:, rows]) and np.array_equal(vg[:, rows], v0[:, rows]), "rows outside [4090, 4102) changed"
+
+
+_FA_LONG = {}
+
+
+def _fa_long_inputs(S):
+    """q [S, 32 * 128] and K / V [8, LONG_CTX, 128] (NaN past the context) for S = Sq = Sk, generated once per S."""
+    if S not in _FA_LONG:
+        _FA_LONG.clear()
+        rng = np.random.default_rng(S)
+        q = rng.standard_normal((S, 32 * 128), dtype=np.float32)
+        kc = rng.standard_normal((8, LONG_CTX, 128), dtype=np.float32)
+        vc = rng.standard_normal((8, LONG_CTX, 128), dtype=np.float32)
+        kc[:, S:] = np.nan
+        vc[:, S:] = np.nan
+        rows = {0, 15, 16, 31, 32, 63, 64, 4063, 4064, 4095, 4096, 4097}          # tile / half-tile edges, both sides of 4096
+        rows |= set(range((S - 1) // 64 * 64, S))                          # the last 64-key tile: every 16- and 32-row tail
+        rows |= set(rng.choice(S, 64, replace=False).tolist())
+        _FA_LONG[S] = (q, kc, vc, np.array(sorted(r for r in rows if r < S)))
+    return _FA_LONG[S]
+
+
+@pytest.mark.parametrize("S", [4097, 4600])
+@pytest.mark.parametrize("rows,xcd", [(16, 1), (32, 1), (32, 0)], ids=["rows16", "rows32", "rows32-plain-grid"])
+def test_attention_flash_form_long_prompt(dev, S, rows, xcd):
+    """k_attn_fa at the model's prompt limit: Sq = Sk = 4097 (one row past 4096: a lone row in the last 16 / 32-row block) and 4600
+    (72 key tiles, the last one 56 keys), causal, 32 : 8 heads, d = 128, K / V in cache layout with NaN rows past the context; the
+    16-row form, the 32-row form on the XCD-aware block order and on the plain grid.  fp64 reference on a fixed sample of query rows:
+    the tile and half-tile edges, both sides of 4064 and 4096, the whole last 64 rows (every tail), 64 random rows.
+    ops.attention passes no K / V tile images (kv_img), so the image-tile forms k_attn_fa<1, true, *> are covered by the engine-level
+    prefill of tests/test_long_context_gpu.py, not here."""
+    from vita_amd import _lib, ops
+    nq, nkv, d = 32, 8, 128
+    q, kc, vc, sample = _fa_long_inputs(S)
+    out = torch.full((S, nq * d), float("nan"), dtype=torch.float32, device=dev)
+    _lib.tune("attn_fa", 2)
+    _lib.tune("attn_rows", rows)
+    _lib.tune("attn_xcd", xcd)
+    try:
+        ops.attention(_dev(q, dev), _dev(kc, dev), _dev(vc, dev), out, B=1, Hq=nq, Hkv=nkv, Sq=S, Sk=S, d=d, ldq=nq * d, hsq=d, ldk=d,
+                      hsk=LONG_CTX * d, ldv=d, hsv=LONG_CTX * d, ldo=nq * d, scale=d ** -0.5, causal=True, q_off=0, klen=S)
+    finally:
+        _lib.tune("attn_fa", 1)
+        _lib.tune("attn_rows", 0)
+        _lib.tune("attn_xcd", 1)
+    got = to_np(out)
+    assert np.isfinite(got).all(), "NaN / inf in the output (a row past the context reached a product, or a row was not written)"
+    G, scale = nq // nkv, d ** -0.5
+    ref = np.empty((sample.size, nq * d))
+    K, V = kc[:, :S].astype(np.float64), vc[:, :S].astype(np.float64)
+    vis = np.arange(S)[None, :] <= sample[:, None]
+    for hq in range(nq):
+        sc = np.where(vis, (q[sample, hq * d:(hq + 1) * d].astype(np.float64) @ K[hq // G].T) * scale, -np.inf)
+        p = np.exp(sc - sc.max(-1, keepdims=True))
+        ref[:, hq * d:(hq + 1) * d] = (p / p.sum(-1, keepdims=True)) @ V[hq // G]
+    assert_close(f"flash form S={S} rows={rows} xcd={xcd} ({sample.size} sampled rows)", got[sample], ref, atol=ATTN_X3_ATOL)

@@ -396,7 +396,10 @@ struct vh_mixtral {
         const size_t Sm = (size_t)c.max_prefill;
         // ---- prefill scratch first: fixed offsets for a given (max_prefill, geometry) --------------------------------
         pxn_hi = cv.take<uint16_t>(Sm * H); pxn_lo = cv.take<uint16_t>(Sm * H);
-        ph_hi = cv.take<uint16_t>(2 * Sm * I); ph_lo = cv.take<uint16_t>(2 * Sm * I);
+        // ph planes: the MoE's h rows (2 S x I) and, before them in each layer, the attention output rows (S x nq hd) that feed the
+        // O projection — whichever is wider (nq hd > 2 I at small intermediate widths)
+        const size_t ph_cols = 2 * (size_t)I > (size_t)nq * hd ? 2 * (size_t)I : (size_t)nq * hd;
+        ph_hi = cv.take<uint16_t>(Sm * ph_cols); ph_lo = cv.take<uint16_t>(Sm * ph_cols);
         px = cv.take<float>(Sm * H); pxn = cv.take<float>(Sm * H);
         pqkv = cv.take<float>(Sm * nqkv);
         pq = cv.take<float>(Sm * nq * hd); pattn = cv.take<float>(Sm * nq * hd);
