@@ -1,0 +1,70 @@
+"""Coverage witness of the prefill MoE GEMM case list (tests/moe_gemm_cases.py) — no GPU.  The specialised kernel's tile schedule
+(vh_gemm_ps_inl.h: for_each_tile, PS_SCHED 1) is restated in Python for a 256-CU part; these tests assert that the cases
+tests/test_moe_gemm_gpu.py runs on that kernel reach every schedule path named below, for gate|up and for down.  If the schedule or
+the case list changes and a path is no longer reached, this fails and says which."""
+import pytest
+
+from tests import moe_gemm_cases as mc
+
+
+def _reached(sched_of):
+    rts, halves, r0, nosplit_tail, empty_second = set(), set(), [], [], []
+    for name, case in mc.CASES.items():      # every case runs on the specialised kernel: ps_cfg 2 forced, and auto where avg > 64
+        s = sched_of(case.rows)
+        rts |= {t.rt for t in s.tiles}
+        halves |= {t.half for t in s.tiles if t.half >= 0}
+        if s.R == 0:
+            r0.append(name)
+        if s.r > 0 and not s.split_tail:
+            nosplit_tail.append(name)
+        if s.empty_halves:
+            empty_second.append(name)
+    return rts, halves, r0, nosplit_tail, empty_second
+
+
+@pytest.mark.parametrize("proj", ["gateup", "down"])
+def test_case_list_reaches_every_schedule_path(proj):
+    sched_of = mc.gateup_schedule if proj == "gateup" else mc.down_schedule      # down: ksplit = -4, the engine's
+    rts, halves, r0, nosplit_tail, empty_second = _reached(sched_of)
+    assert rts == set(range(1, mc.RTMAX + 1)), f"{proj}: row-tile counts never run: {sorted(set(range(1, 13)) - rts)}"
+    assert halves == {0, 1}, f"{proj}: M-split tail halves reached: {sorted(halves)}"
+    assert r0, f"{proj}: no case has fewer tiles than blocks (R = 0)"
+    assert nosplit_tail, f"{proj}: no case has a partial last round that is not M-split"
+    assert empty_second, f"{proj}: no case has an M-split tail whose second half is empty"
+
+
+def test_named_edges_are_where_the_cases_say():
+    """the edges the case descriptions promise, pinned so that a schedule change shows up by name."""
+    gu = {n: mc.gateup_schedule(c.rows) for n, c in mc.CASES.items()}
+    assert (gu["uniform"].T, gu["uniform"].R, gu["uniform"].r, gu["uniform"].split_tail) == (896, 3, 128, True)
+    assert {t.rt for t in gu["uniform"].tiles if t.half >= 0} == {5, 4}
+    assert max(t.mi for t in gu["skew"].tiles if t.e in (0, 1)) == 23                   # 24 m-tiles on each hot expert
+    assert (gu["one_row"].T, gu["one_row"].R, gu["one_row"].split_tail, gu["one_row"].empty_halves) == (112, 0, True, 112)
+    assert (gu["two_rows"].T, gu["two_rows"].R, gu["two_rows"].split_tail) == (224, 0, False)
+    bnd = {(t.e, t.mi): t.rt for t in gu["boundary"].tiles if t.half < 0}
+    assert [bnd[(6, 0)], bnd[(6, 1)]] == [7, 6] and [bnd[(7, m)] for m in range(3)] == [9, 9, 7]
+    for tp_i in mc.TP_WIDTHS:                                                             # NT = 14 at TP = 8
+        assert mc.gateup_schedule(mc.CASES["uniform"].rows, N=tp_i).T == 8 * tp_i // 128
+
+
+@pytest.mark.parametrize("name", list(mc.CASES))
+@pytest.mark.parametrize("proj,ksplit", [("gateup", 1), ("down", -4), ("down", 1), ("down", 2), ("down", 3)])
+def test_restated_schedule_is_a_partition(name, proj, ksplit):
+    """sanity of the restatement itself: every (row, n-tile, K slice) of the problem is in exactly one tile."""
+    rows = mc.CASES[name].rows
+    s = mc.gateup_schedule(rows) if proj == "gateup" else mc.down_schedule(rows, ksplit=ksplit)
+    NT = mc.I // 128 if proj == "gateup" else mc.H // 256
+    seen = {}
+    for t in s.tiles:
+        assert t.m_end - t.m_begin <= 16 * t.rt and 1 <= t.rt <= mc.RTMAX
+        key = (t.nt, t.ks)
+        seen.setdefault(key, []).append((t.m_begin, t.m_end))
+    M = sum(rows)
+    assert len(seen) == NT * s.KS
+    for key, spans in seen.items():
+        spans.sort()
+        pos = 0
+        for b, e in spans:
+            assert b == pos, f"{key}: gap or overlap at row {pos}"
+            pos = e
+        assert pos == M

@@ -318,9 +318,10 @@ def split_planes_into(x, buf):
 
 def gemm_ps(a_hi, a_lo, w, *, w_up=None, bias=None, act=None, scale=None, resid=None, out=None, out_split=False,
             a_rowidx=None, m=None, c_rowidx=None, group_off=None, ngroups=0, w_group_stride=0, wide=False, ksplit=1,
-            nslab_out=None):
+            nslab_out=None, out_planes=None):
     """Weight-streaming GEMM on pre-split activations (vh_gemm_ps).  Returns fp32 out, or (hi, lo) planes when
-    out_split=True.  ksplit > 1: `out` must be [ksplit, rows, N] (partial sums per K range; the caller adds them)."""
+    out_split=True (out_planes: write them into these two bf16 [rows, N] views of equal row stride instead of new tensors).
+    ksplit > 1: `out` must be [ksplit, rows, N] (partial sums per K range; the caller adds them)."""
     _dev(a_hi, a_lo, w)
     _bf16(a_hi, "a_hi"); _bf16(a_lo, "a_lo"); _bf16(w, "w")
     g = _lib.GemmPsArgs()
@@ -334,9 +335,19 @@ def gemm_ps(a_hi, a_lo, w, *, w_up=None, bias=None, act=None, scale=None, resid=
     M = int(m if m is not None else (a_rowidx.shape[0] if a_rowidx is not None else a_hi.shape[0]))
     planes = None
     if out_split:
-        planes = (torch.empty((M, N), dtype=torch.bfloat16, device=w.device),
-                  torch.empty((M, N), dtype=torch.bfloat16, device=w.device))
-        g.C_hi, g.C_lo, g.ldc_split = planes[0].data_ptr(), planes[1].data_ptr(), N
+        if out_planes is not None:
+            planes = tuple(out_planes)
+            _dev(*planes)
+            for t in planes:
+                _bf16(_c(t, "out_planes"), "out_planes")
+                if t.ndim != 2 or t.shape[0] < M or t.shape[1] != N:
+                    raise ValueError(f"out_planes must be [>= {M}, {N}] bf16 views, got {tuple(t.shape)}")
+            if planes[0].stride(0) != planes[1].stride(0):
+                raise ValueError("out_planes: hi and lo need the same row stride")
+        else:
+            planes = (torch.empty((M, N), dtype=torch.bfloat16, device=w.device),
+                      torch.empty((M, N), dtype=torch.bfloat16, device=w.device))
+        g.C_hi, g.C_lo, g.ldc_split = planes[0].data_ptr(), planes[1].data_ptr(), int(planes[0].stride(0))
     else:
         if out is None:
             out = torch.empty((M, N), dtype=torch.float32, device=w.device)
