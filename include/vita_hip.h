@@ -351,6 +351,35 @@ int vh_attn_decode(const float* qkv, float* kcache, float* vcache, int pos, cons
 int vh_lmhead_argmax(const float* x, const float* delta, const float* norm_w, float eps, const uint16_t* W, int V, int H,
                      float* logits, int* token_out, float* blk_val, int* blk_idx, int nblk, void* stream);
 
+/* ---- seeded sampling (replaces HF GenerationMixin sampling with its TemperatureLogitsWarper, TopKLogitsWarper and
+ * TopPLogitsWarper — transformers generation/utils.py _sample, generation/logits_process.py — and vLLM's Sampler behind
+ * SamplingParams(temperature, top_k, top_p, seed), web_demo/web_ability_demo.py:351) --------------------------------------
+ * Per request: z = (double)logit / temperature; top-k keeps z >= the k-th largest z (ties kept); top-p, on the softmax of the
+ * top-k-kept set, keeps a value iff the mass strictly above it is < top_p (the maximum always, ties together; masses in double);
+ * the token is the argmax over kept i of z_i + G_i (lowest index on ties), G_i = -log(-log(u)), u = ((x >> 11) + 0.5) 2^-53,
+ * x = word i & 3 of Philox4x64-10 under key (seed, 0) at counter (i >> 2, draw, 0, 0).  draw = draw0 + the token's index in the
+ * request's output (the prefill's token is index 0), counted on the device.  Sampled candidates cross blocks and ranks as exact
+ * keys of their double scores, so given the logits a token is a function of the request alone (not of the grid, the vocab
+ * shards, the batch-mates or the lookahead window).
+ * NaN logits rank as -inf; when nothing finite is kept the id is 0.  temperature = 0 (or a null vh_sampling) is greedy: the
+ * greedy kernels and launches unchanged.  temperature must be finite and >= 0, top_k >= 0 (0 = off), 0 < top_p <= 1 (1 = off).
+ * Under a vocab-sharded LM head (vocab_n > 0) only temperature-only sampling is accepted (VH_E_ARG otherwise); an unsharded head
+ * under tensor parallelism holds the same logits on every rank, so every rank draws the same token. */
+typedef struct {
+    float temperature;
+    int top_k;
+    float top_p;
+    uint64_t seed;
+    int64_t draw0;
+} vh_sampling;
+/* single-sequence engine (vh_mixtral_prefill / decode); vh_mixtral_reset restores greedy */
+int vh_mixtral_set_sampling(vh_mixtral_t* m, const vh_sampling* s /* host, nullable */);
+/* one sequence of the paged engine; seq_alloc, seq_free and vh_mixtral_reset restore greedy */
+int vh_mixtral_seq_set_sampling(vh_mixtral_t* m, int seq, const vh_sampling* s /* host, nullable */);
+/* per-operator entry: tokens_out[r] = the draw of row r = logits + r * ld (ld = 0: the same row for every draw) at draw index
+ *   draw0 + r, by the engine's device code.  logits fp32, V entries per row; tokens_out int[rows].                             */
+int vh_sample_rows(const float* logits, long ld, int rows, int V, const vh_sampling* s /* host */, int* tokens_out, void* stream);
+
 /* Live HIP-event timing of the dominant kernel of a phase, on the stream the engine launches it on: stride > 0 samples the
  * DECODE gate|up expert GEMV of every stride-th layer, stride < 0 the PREFILL gate|up grouped GEMM of every |stride|-th layer
  * (0 = off), up to max_samples launches; read returns summed ms and sample count and clears the samples. */

@@ -85,6 +85,16 @@ class VitEmbedArgs(C.Structure):
     ]
 
 
+class Sampling(C.Structure):
+    """vh_sampling: seeded temperature / top-k / top-p sampling of one request (temperature 0 = greedy)."""
+    _fields_ = [("temperature", c_float), ("top_k", c_int), ("top_p", c_float), ("seed", C.c_uint64), ("draw0", C.c_int64)]
+
+
+def sampling(temperature=0.0, top_k=0, top_p=1.0, seed=0, draw0=0):
+    """-> Sampling; seed is taken modulo 2^64 (numpy.random.Philox keys an int the same way)."""
+    return Sampling(float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw0))
+
+
 class MixtralCfg(C.Structure):
     _fields_ = [
         ("hidden", c_int), ("n_layers", c_int), ("n_q_heads", c_int), ("n_kv_heads", c_int),
@@ -173,6 +183,9 @@ SIGNATURES = {
     "vh_mixtral_seq_tokens": (c_void_p, [c_void_p, c_int]),
     "vh_mixtral_seq_counters": (c_void_p, [c_void_p, c_int]),
     "vh_mixtral_seq_table": (c_int, [c_void_p, c_int, C.POINTER(c_int), c_int]),
+    "vh_mixtral_set_sampling": (c_int, [c_void_p, C.POINTER(Sampling)]),
+    "vh_mixtral_seq_set_sampling": (c_int, [c_void_p, c_int, C.POINTER(Sampling)]),
+    "vh_sample_rows": (c_int, [c_void_p, c_long, c_int, c_int, C.POINTER(Sampling), c_void_p, c_void_p]),
     "vh_mixtral_profile": (c_int, [c_void_p, c_int, c_int]),
     "vh_mixtral_profile_read": (c_int, [c_void_p, C.POINTER(C.c_double), C.POINTER(c_int)]),
 }

@@ -3,6 +3,7 @@
 // enqueues a whole forward (HF MixtralModel.forward + GenerationMixin greedy loop, as driven
 // by vita/model/language_model/vita_mixtral.py:101-215 and video_audio_demo.py:257-270).
 #include <dlfcn.h>
+#include <cmath>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -322,6 +323,7 @@ struct vh_mixtral {
     struct Seq {
         bool live = false;
         int host_pos = 0, poisoned = 0, npages = 0;
+        VhSampleParams samp{};         // vh_mixtral_seq_set_sampling (T = 0: greedy)
         std::vector<int> pages;        // host mirror of the device table (sized once: uploads read from it)
     };
     std::vector<Seq> seqs;
@@ -335,17 +337,19 @@ struct vh_mixtral {
     int *l_attn_cnt[VH_BMAX] = {}, *l_route[VH_BMAX] = {}, *l_blk_idx[VH_BMAX] = {};
     const int* table = nullptr;        // device page table of the bound sequence; null = contiguous rows (default state)
     int bound = -1;
-    struct { float *xa, *xb, *da, *dm; int *counters, *out_tokens; int host_pos, poisoned; } dflt{};
+    struct { float *xa, *xb, *da, *dm; int *counters, *out_tokens; int host_pos, poisoned; VhSampleParams samp; } dflt{};
+    VhSampleParams samp{};             // sampling of the bound sequence / of the single-sequence engine (T = 0: greedy)
+    float* samp_rows = nullptr;        // [VH_BMAX][V] logits rows of the batched head for sequences with a top-k / top-p filter
     int n_pages() const { return c.max_ctx / 64; }
     int live_seqs() const { int n = 0; for (const Seq& q : seqs) n += q.live; return n; }
     void bind(int s) {
-        dflt = {xa, xb, delta_attn, delta_moe, counters, out_tokens, host_pos, poisoned};
+        dflt = {xa, xb, delta_attn, delta_moe, counters, out_tokens, host_pos, poisoned, samp};
         float* x = seq_x + (size_t)s * 4 * H;
         xa = x; xb = x + H; delta_attn = x + 2 * H; delta_moe = x + 3 * H;
         counters = seq_counters + 4 * s;
         out_tokens = seq_tokens + (size_t)s * (c.max_new > 0 ? c.max_new : 1);
         table = seq_table + (size_t)s * max_splits;
-        host_pos = seqs[s].host_pos; poisoned = seqs[s].poisoned;
+        host_pos = seqs[s].host_pos; poisoned = seqs[s].poisoned; samp = seqs[s].samp;
         bound = s;
     }
     void unbind() {
@@ -353,7 +357,7 @@ struct vh_mixtral {
         q.host_pos = host_pos; q.poisoned = poisoned;
         xa = dflt.xa; xb = dflt.xb; delta_attn = dflt.da; delta_moe = dflt.dm;
         counters = dflt.counters; out_tokens = dflt.out_tokens;
-        host_pos = dflt.host_pos; poisoned = dflt.poisoned;
+        host_pos = dflt.host_pos; poisoned = dflt.poisoned; samp = dflt.samp;
         table = nullptr; bound = -1;
     }
     // pages covering positions [0, n_tokens) of sequence s; new table entries are uploaded on st.  -1: pool exhausted.
@@ -371,7 +375,7 @@ struct vh_mixtral {
     void release(int s) {
         Seq& q = seqs[s];
         for (int j = q.npages - 1; j >= 0; --j) free_pages.push_back(q.pages[j]);
-        q.npages = 0; q.live = false; q.host_pos = 0; q.poisoned = 0;
+        q.npages = 0; q.live = false; q.host_pos = 0; q.poisoned = 0; q.samp = VhSampleParams{};
     }
     void init_seqs() {
         seqs.assign(c.max_seqs > 0 ? c.max_seqs : 0, Seq{});
@@ -420,9 +424,9 @@ struct vh_mixtral {
         attn_out = cv.take<float>((size_t)nq * hd);
         attn_cnt = cv.take<int>(nkv);  // arrival tickets; zero at creation, reset by each last arriver
         hbuf = cv.take<float>((size_t)2 * I);
-        blk_val = cv.take<float>(lm_grid);
+        blk_val = cv.take<float>(3 * (size_t)lm_grid);   // greedy: one value per block; sampled: 3-float keys (vh_sample.h vhs_key3)
         blk_idx = cv.take<int>(lm_grid);
-        cand = cv.take<float>(2 * (c.tp_world > 0 ? c.tp_world : 1));
+        cand = cv.take<float>(4 * (c.tp_world > 0 ? c.tp_world : 1));
         route = cv.take<int>(4);
         counters = cv.take<int>(4);  // {pos, n_generated, attn_done (monotonic), device error flag}
         g_qkv = cv.take<unsigned long long>(nqkv);
@@ -449,10 +453,11 @@ struct vh_mixtral {
                 l_attn_cnt[b] = cv.take<int>(nkv);
                 l_hbuf[b] = cv.take<float>((size_t)2 * I);
                 l_route[b] = cv.take<int>(4);
-                l_blk_val[b] = cv.take<float>(lm_grid);
+                l_blk_val[b] = cv.take<float>(3 * (size_t)lm_grid);
                 l_blk_idx[b] = cv.take<int>(lm_grid);
-                l_cand[b] = cv.take<float>(2 * (c.tp_world > 0 ? c.tp_world : 1));
+                l_cand[b] = cv.take<float>(4 * (c.tp_world > 0 ? c.tp_world : 1));
             }
+            samp_rows = cv.take<float>((size_t)VH_BMAX * V);
         }
         kcache = cv.take<float>((size_t)c.n_layers * nkv * c.max_ctx * hd);
         vcache = cv.take<float>((size_t)c.n_layers * nkv * c.max_ctx * hd);
@@ -657,9 +662,53 @@ int vh_mixtral_reset(vh_mixtral_t* m, void* stream) {
     if (hipMemsetAsync(m->counters, 0, 4 * sizeof(int), S(stream)) != hipSuccess)
         return fail(VH_E_HIP, "reset memset failed");
     m->host_pos = 0; m->poisoned = 0;
+    m->samp = VhSampleParams{};                  // greedy again (released sequences too)
     for (int s = 0; s < (int)m->seqs.size(); ++s)
         if (m->seqs[s].live) m->release(s);      // the pool is one: a reset returns every page
     return VH_OK;
+}
+
+// a top-k / top-p filter is in force (the temperature-only draw folds into the LM head's per-block argmax)
+static bool sampling_filters(const VhSampleParams& p, int V) { return p.T > 0.0 && ((p.top_k > 0 && p.top_k < V) || p.top_p < 1.0); }
+// vh_sampling -> kernel parameters (T = 0 or null: greedy)
+static int sampling_params(const vh_sampling* s, VhSampleParams* out, const char* what) {
+    *out = VhSampleParams{};
+    if (!s) return VH_OK;
+    if (!std::isfinite(s->temperature) || s->temperature < 0.f) return fail(VH_E_ARG, "%s: temperature must be finite and >= 0 (got %g)", what, (double)s->temperature);
+    if (s->top_k < 0) return fail(VH_E_ARG, "%s: top_k must be >= 0 (got %d)", what, s->top_k);
+    if (!(s->top_p > 0.f && s->top_p <= 1.f)) return fail(VH_E_ARG, "%s: top_p must be in (0, 1] (got %g)", what, (double)s->top_p);
+    if (s->temperature == 0.f) return VH_OK;
+    out->T = s->temperature; out->top_p = s->top_p; out->top_k = s->top_k;
+    out->seed = s->seed; out->draw0 = s->draw0;
+    return VH_OK;
+}
+static int engine_sampling(const vh_mixtral* m, const vh_sampling* s, VhSampleParams* out, const char* what) {
+    const int rc = sampling_params(s, out, what);
+    if (rc != VH_OK) return rc;
+    // a vocab-sharded head sees its slice only: the temperature-only draw travels through the candidate exchange, a filter cannot
+    if (m->c.vocab_n > 0 && m->c.vocab_n < m->V && sampling_filters(*out, m->V))
+        return fail(VH_E_ARG, "%s: top-k / top-p need an unsharded LM head (vocab_n = %d of %d)", what, m->c.vocab_n, m->V);
+    if (m->c.vocab_n > 0 && m->c.tp_world > 64 && out->T > 0.0)
+        return fail(VH_E_ARG, "%s: sampling under a vocab-sharded head takes at most 64 ranks (tp_world %d)", what, m->c.tp_world);
+    return VH_OK;
+}
+
+int vh_mixtral_set_sampling(vh_mixtral_t* m, const vh_sampling* s) {
+    if (!m) return fail(VH_E_ARG, "null engine");
+    VhSampleParams p;
+    const int rc = engine_sampling(m, s, &p, "vh_mixtral_set_sampling");
+    if (rc != VH_OK) return rc;
+    m->samp = p;
+    return VH_OK;
+}
+
+int vh_sample_rows(const float* logits, long ld, int rows, int V, const vh_sampling* s, int* tokens_out, void* stream) {
+    if (!logits || !tokens_out) return fail(VH_E_ARG, "vh_sample_rows: null pointer");
+    if (rows < 1 || V < 1 || ld < 0) return fail(VH_E_SHAPE, "vh_sample_rows: rows %d, V %d, ld %ld", rows, V, ld);
+    VhSampleParams p;
+    const int rc = sampling_params(s, &p, "vh_sample_rows");
+    if (rc != VH_OK) return rc;
+    return check_launch("vh_sample_rows", vhk_sample_rows(S(stream), logits, ld, rows, V, p, tokens_out));
 }
 
 // a launcher returns non-zero when it REJECTS its arguments before launching (VH_E_SHAPE); a launch the runtime
@@ -1050,18 +1099,26 @@ int vh_mixtral_prefill(vh_mixtral_t* m, const float* embeds, int Sn, int pos0, f
 static int head_and_select(vh_mixtral* m, hipStream_t st, const float* x_in, const float* delta, int mode, int set_pos,
                            const VhXchg* cx) {
     const bool sharded = m->c.vocab_n > 0 && (m->c.tp_world > 1 || (m->comm && vh_comm_is_loopback(m->comm)));
+    const bool filt = sampling_filters(m->samp, m->V);   // top-k / top-p: greedy head, then the filter kernel on the kept row
+    const int keyed = m->samp.T > 0.0 ? 1 : 0;           // sampled candidates travel as exact keys of their double scores
     VH_TRY(vhk_dec_lmhead(st, x_in, delta, m->final_norm, m->c.rms_eps, m->lm_head, m->Vn, m->H, m->logits, m->blk_val,
-                          m->blk_idx, m->lm_grid, m->counters + 1, m->hist_rows(), m->v0, m->V, cx), "lm_head");
+                          m->blk_idx, m->lm_grid, m->counters + 1, m->hist_rows(), m->v0, m->V, cx, filt ? nullptr : &m->samp), "lm_head");
     int nblk = m->lm_grid;
-    if (sharded) {
+    if (filt) {
+        VhDecSampleJob j{};
+        j.n = 1; j.V = m->V; j.hist_rows = m->hist_rows();
+        j.logits[0] = m->logits; j.ngen[0] = m->counters + 1; j.blk_val[0] = m->blk_val; j.blk_idx[0] = m->blk_idx; j.sample[0] = m->samp;
+        VH_TRY(vhk_dec_sample(st, j), "sample");
+        nblk = 1;
+    } else if (sharded) {
         const int cw = m->cand_world();
-        VH_TRY(vhk_dec_cand(st, m->blk_val, m->blk_idx, m->lm_grid, m->cand, m->c.tp_rank, cw), "candidates");
-        if (m->allreduce(m->cand, 2L * cw, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
-        VH_TRY(vhk_dec_cand_unpack(st, m->cand, cw, m->blk_val, m->blk_idx), "candidates");
+        VH_TRY(vhk_dec_cand(st, m->blk_val, m->blk_idx, m->lm_grid, m->cand, m->c.tp_rank, cw, keyed), "candidates");
+        if (m->allreduce(m->cand, (keyed ? 4L : 2L) * cw, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
+        VH_TRY(vhk_dec_cand_unpack(st, m->cand, cw, m->blk_val, m->blk_idx, keyed), "candidates");
         nblk = cw;
     }
     VH_TRY(vhk_dec_select(st, m->blk_val, m->blk_idx, nblk, m->embed, m->H, m->V, m->xa, m->counters, m->counters + 1,
-                          m->out_tokens, m->c.max_new, mode, set_pos), "select");
+                          m->out_tokens, m->c.max_new, mode, set_pos, keyed), "select");
     return VH_OK;
 }
 
@@ -1186,7 +1243,7 @@ static int seq_ok(vh_mixtral* m, int s, const char* what) {
 int vh_mixtral_seq_alloc(vh_mixtral_t* m) {
     if (!m) return fail(VH_E_ARG, "null engine");
     for (int s = 0; s < (int)m->seqs.size(); ++s)
-        if (!m->seqs[s].live) { m->seqs[s].live = true; return s; }
+        if (!m->seqs[s].live) { m->seqs[s].live = true; m->seqs[s].samp = VhSampleParams{}; return s; }
     return fail(VH_E_FULL, "vh_mixtral_seq_alloc: all %d sequence slots are in use", (int)m->seqs.size());
 }
 
@@ -1194,6 +1251,16 @@ int vh_mixtral_seq_free(vh_mixtral_t* m, int s) {
     const int rc = seq_ok(m, s, "vh_mixtral_seq_free");
     if (rc != VH_OK) return rc;
     m->release(s);
+    return VH_OK;
+}
+
+int vh_mixtral_seq_set_sampling(vh_mixtral_t* m, int s, const vh_sampling* smp) {
+    const int rc0 = seq_ok(m, s, "vh_mixtral_seq_set_sampling");
+    if (rc0 != VH_OK) return rc0;
+    VhSampleParams p;
+    const int rc = engine_sampling(m, smp, &p, "vh_mixtral_seq_set_sampling");
+    if (rc != VH_OK) return rc;
+    m->seqs[s].samp = p;
     return VH_OK;
 }
 
@@ -1337,28 +1404,43 @@ static int decode_iteration(vh_mixtral* m, hipStream_t st, const int* ids, int n
         const int gn = n - g0 < VH_BMAX ? n - g0 : VH_BMAX;
         VhDecBatchVec hv{};
         VhDecBatchHead hdp{};
+        VhDecSampleJob sj{};
+        bool filt[VH_BMAX] = {};
         hv.n = gn;
+        sj.V = m->V; sj.hist_rows = 1;
         for (int b = 0; b < gn; ++b) {
+            const VhSampleParams& sp = m->seqs[ids[g0 + b]].samp;
             hv.x_in[b] = xa[g0 + b]; hv.delta[b] = dm[g0 + b];
             hdp.blk_val[b] = m->l_blk_val[b]; hdp.blk_idx[b] = m->l_blk_idx[b];
+            hdp.ngen[b] = cnt[g0 + b] + 1;
+            filt[b] = sampling_filters(sp, m->V);
+            if (!filt[b]) hdp.sample[b] = sp;
+            else {
+                hdp.logits[b] = m->samp_rows + (size_t)b * m->V;
+                const int j = sj.n++;
+                sj.logits[j] = gn >= 2 ? hdp.logits[b] : m->logits; sj.ngen[j] = cnt[g0 + b] + 1;
+                sj.blk_val[j] = m->l_blk_val[b]; sj.blk_idx[j] = m->l_blk_idx[b]; sj.sample[j] = sp;
+            }
         }
         if (gn >= 2) {   // one pass over the table for the group: 97 us (four activation rows, always) against n x 70
             VH_TRY(vhk_decb_lmhead(st, hv, m->final_norm, eps, m->lm_head, m->Vn, H, hdp, m->lm_grid, m->v0), "batched lm_head");
         } else {
             VH_TRY(vhk_dec_lmhead(st, xa[g0], dm[g0], m->final_norm, eps, m->lm_head, m->Vn, H, m->logits, m->l_blk_val[0],
-                                  m->l_blk_idx[0], m->lm_grid, cnt[g0] + 1, 1, m->v0, m->V), "lm_head");
+                                  m->l_blk_idx[0], m->lm_grid, cnt[g0] + 1, 1, m->v0, m->V, nullptr, &hdp.sample[0]), "lm_head");
         }
+        if (sj.n > 0) VH_TRY(vhk_dec_sample(st, sj), "sample");   // one workgroup per filtered sequence of the group
         for (int b = 0; b < gn; ++b) {
             const int sb = g0 + b;
-            int nblk = m->lm_grid;
-            if (sharded) {
-                VH_TRY(vhk_dec_cand(st, m->l_blk_val[b], m->l_blk_idx[b], m->lm_grid, m->l_cand[b], m->c.tp_rank, m->c.tp_world), "candidates");
-                if (m->allreduce(m->l_cand[b], 2L * m->c.tp_world, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
-                VH_TRY(vhk_dec_cand_unpack(st, m->l_cand[b], m->c.tp_world, m->l_blk_val[b], m->l_blk_idx[b]), "candidates");
+            int nblk = filt[b] ? 1 : m->lm_grid;
+            const int keyed = m->seqs[ids[sb]].samp.T > 0.0 ? 1 : 0;
+            if (sharded && !filt[b]) {
+                VH_TRY(vhk_dec_cand(st, m->l_blk_val[b], m->l_blk_idx[b], m->lm_grid, m->l_cand[b], m->c.tp_rank, m->c.tp_world, keyed), "candidates");
+                if (m->allreduce(m->l_cand[b], (keyed ? 4L : 2L) * m->c.tp_world, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
+                VH_TRY(vhk_dec_cand_unpack(st, m->l_cand[b], m->c.tp_world, m->l_blk_val[b], m->l_blk_idx[b], keyed), "candidates");
                 nblk = m->c.tp_world;
             }
             VH_TRY(vhk_dec_select(st, m->l_blk_val[b], m->l_blk_idx[b], nblk, m->embed, H, m->V, xa[sb], cnt[sb], cnt[sb] + 1,
-                                  m->seq_tokens + (size_t)ids[sb] * (m->c.max_new > 0 ? m->c.max_new : 1), m->c.max_new, 1, 0), "select");
+                                  m->seq_tokens + (size_t)ids[sb] * (m->c.max_new > 0 ? m->c.max_new : 1), m->c.max_new, 1, 0, keyed), "select");
         }
     }
     const hipError_t e = hipGetLastError();

@@ -36,6 +36,7 @@
 // MixtralExperts) as called from vita/model/language_model/vita_mixtral.py:158-173.
 #include "vh_common.h"
 #include "vh_kernels.h"
+#include "vh_sample.h"
 
 namespace {
 
@@ -794,17 +795,20 @@ __global__ __launch_bounds__(256) void k_dec_down(const float* __restrict__ hbuf
 // round trip they replace: profiles/EXPERIMENTS.md.)
 
 // ---- K_F: final RMSNorm + LM head GEMV + per-block argmax ---------------------------
+// SAMP: temperature-only sampling (vh_sample.h) — the per-block argmax compares z + G in double instead of the logit (the kept
+// logits stay raw); the draw index is sp.draw0 + n_generated.  The greedy instantiation is the kernel as it was.
 #define LM_R 8
-template <int NJ>
+template <int NJ, bool SAMP>
 __global__ __launch_bounds__(256) void k_dec_lmhead(const float* __restrict__ x_in, const float* __restrict__ delta,
                                                     const float* __restrict__ norm_w, float eps,
                                                     const uint16_t* __restrict__ W, int V, int K,
                                                     float* __restrict__ logits, float* __restrict__ blk_val,
                                                     int* __restrict__ blk_idx, const int* __restrict__ ngen_ptr,
-                                                    int hist_rows, int v0, int Vfull, const VhXchg cx) {
+                                                    int hist_rows, int v0, int Vfull, const VhXchg cx, const VhSampleParams sp) {
+    typedef typename std::conditional<SAMP, double, float>::type BT;
     __shared__ float red[4 * (LM_R + 1)];
     xchg_reduce(cx);
-    __shared__ float bv_s[LM_R];
+    __shared__ BT bv_s[LM_R];
     __shared__ int bi_s[LM_R];
     // logits history: row = index of the token this step produces (clamped), so the host can
     // read every step's scores after a multi-step launch (HF generate(output_scores=True)).
@@ -823,9 +827,10 @@ __global__ __launch_bounds__(256) void k_dec_lmhead(const float* __restrict__ x_
     float xr[NJ][8];
     const float ss = load_add_norm<NJ>(x_in, delta, norm_w, nullptr, K, xr, &cx);
     float inv = 0.f;
-    float best = -INFINITY;
+    BT best = -INFINITY;
     int besti = 0x7fffffff;
     bool first = true;
+    const unsigned long long draw = SAMP ? (unsigned long long)(sp.draw0 + *ngen_ptr) : 0ull;
     while (it < n_iter) {
         float acc[LM_R];
         gemv_fma<NJ, LM_R>(wa, xr, acc);
@@ -844,39 +849,47 @@ __global__ __launch_bounds__(256) void k_dec_lmhead(const float* __restrict__ x_
             for (int r = 0; r < LM_R; ++r) if (threadIdx.x == r) v = vals[r];
             v *= inv;
             logits[n0 + threadIdx.x] = v;
-            if (v > best) { best = v; besti = v0 + n0 + threadIdx.x; }  // ascending n: first max wins
+            if (SAMP) {
+                const double s = vhs_perturbed(v, v0 + n0 + threadIdx.x, sp, draw);
+                if (s > best) { best = s; besti = v0 + n0 + threadIdx.x; }
+            } else if (v > best) { best = v; besti = v0 + n0 + threadIdx.x; }  // ascending n: first max wins
         }
         it = nxt;
     }
     if (threadIdx.x < LM_R) { bv_s[threadIdx.x] = best; bi_s[threadIdx.x] = besti; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        float b = bv_s[0]; int bi = bi_s[0];
+        BT b = bv_s[0]; int bi = bi_s[0];
         for (int r = 1; r < LM_R; ++r)
             if (bv_s[r] > b || (bv_s[r] == b && bi_s[r] < bi)) { b = bv_s[r]; bi = bi_s[r]; }
-        blk_val[blockIdx.x] = b; blk_idx[blockIdx.x] = bi;
+        if (SAMP) vhs_key3(b, blk_val + blockIdx.x, gridDim.x);    // exact order across blocks and ranks: 3 x nblk floats
+        else blk_val[blockIdx.x] = b;
+        blk_idx[blockIdx.x] = bi;
     }
 }
 
 // ---- K_G: global argmax (lowest index on ties, as torch.argmax), bookkeeping, and the
 // next step's input embedding (vita_arch.py:155-175 decode early-exit + embed_tokens).
+// KEYED: sampled candidates, blk_val holds the 3-float keys of their double scores (vhs_key3, stride nblk)
+template <bool KEYED>
 __global__ __launch_bounds__(256) void k_dec_select(const float* __restrict__ blk_val, const int* __restrict__ blk_idx,
                                                     int nblk, const uint16_t* __restrict__ embed, int H, int vocab,
                                                     float* __restrict__ x_next, int* __restrict__ pos_ptr,
                                                     int* __restrict__ ngen_ptr, int* __restrict__ out_tokens,
                                                     int max_out, int mode, int set_pos) {
-    __shared__ float v_s[256];
+    typedef typename std::conditional<KEYED, double, float>::type VT;
+    __shared__ VT v_s[256];
     __shared__ int i_s[256];
-    float b = -INFINITY; int bi = 0x7fffffff;
+    VT b = -INFINITY; int bi = 0x7fffffff;
     for (int i = threadIdx.x; i < nblk; i += 256) {
-        const float v = blk_val[i]; const int ix = blk_idx[i];
+        const VT v = KEYED ? (VT)vhs_unkey3(blk_val + i, nblk) : (VT)blk_val[i]; const int ix = blk_idx[i];
         if (v > b || (v == b && ix < bi)) { b = v; bi = ix; }
     }
     v_s[threadIdx.x] = b; i_s[threadIdx.x] = bi;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
         if (threadIdx.x < s) {
-            const float v = v_s[threadIdx.x + s]; const int ix = i_s[threadIdx.x + s];
+            const VT v = v_s[threadIdx.x + s]; const int ix = i_s[threadIdx.x + s];
             if (v > v_s[threadIdx.x] || (v == v_s[threadIdx.x] && ix < i_s[threadIdx.x])) {
                 v_s[threadIdx.x] = v; i_s[threadIdx.x] = ix;
             }
@@ -929,35 +942,47 @@ __global__ __launch_bounds__(256) void k_dec_pick(const float* __restrict__ blk_
 // ---- vocab-sharded LM head: this rank's best (value, index) -> its slot of a zeroed [world][2] vector; the
 // all-reduce(sum) of that vector hands every rank every candidate (adding zeros is exact, indices < 2^24 are exact
 // in fp32), k_dec_select then takes the global argmax with the usual lowest-index tie rule on every rank alike.
+// KEYED (sampled candidates): keys in, and [world][4] = 3 key floats + index out
+template <bool KEYED>
 __global__ __launch_bounds__(256) void k_dec_cand(const float* __restrict__ blk_val, const int* __restrict__ blk_idx,
                                                   int nblk, float* __restrict__ cand, int rank, int world) {
-    __shared__ float v_s[256];
+    typedef typename std::conditional<KEYED, double, float>::type VT;
+    __shared__ VT v_s[256];
     __shared__ int i_s[256];
-    float b = -INFINITY; int bi = 0x7fffffff;
+    VT b = -INFINITY; int bi = 0x7fffffff;
     for (int i = threadIdx.x; i < nblk; i += 256) {
-        const float v = blk_val[i]; const int ix = blk_idx[i];
+        const VT v = KEYED ? (VT)vhs_unkey3(blk_val + i, nblk) : (VT)blk_val[i]; const int ix = blk_idx[i];
         if (v > b || (v == b && ix < bi)) { b = v; bi = ix; }
     }
     v_s[threadIdx.x] = b; i_s[threadIdx.x] = bi;
     __syncthreads();
     for (int s = 128; s > 0; s >>= 1) {
         if (threadIdx.x < s) {
-            const float v = v_s[threadIdx.x + s]; const int ix = i_s[threadIdx.x + s];
+            const VT v = v_s[threadIdx.x + s]; const int ix = i_s[threadIdx.x + s];
             if (v > v_s[threadIdx.x] || (v == v_s[threadIdx.x] && ix < i_s[threadIdx.x])) {
                 v_s[threadIdx.x] = v; i_s[threadIdx.x] = ix;
             }
         }
         __syncthreads();
     }
-    if ((int)threadIdx.x < 2 * world) {
+    if (KEYED) {
+        if ((int)threadIdx.x < 4 * world) cand[threadIdx.x] = 0.f;
+        __syncthreads();
+        if (threadIdx.x == 0) { vhs_key3((double)v_s[0], cand + 4 * rank, 1); cand[4 * rank + 3] = (float)i_s[0]; }
+    } else if ((int)threadIdx.x < 2 * world) {
         float o = 0.f;
         if ((int)threadIdx.x == 2 * rank) o = v_s[0];
         if ((int)threadIdx.x == 2 * rank + 1) o = (float)i_s[0];
         cand[threadIdx.x] = o;
     }
 }
-__global__ void k_dec_cand_unpack(const float* __restrict__ cand, int world, float* __restrict__ val, int* __restrict__ idx) {
-    if ((int)threadIdx.x < world) { val[threadIdx.x] = cand[2 * threadIdx.x]; idx[threadIdx.x] = (int)cand[2 * threadIdx.x + 1]; }
+__global__ void k_dec_cand_unpack(const float* __restrict__ cand, int world, float* __restrict__ val, int* __restrict__ idx, int keyed) {
+    const int r = threadIdx.x;
+    if (r >= world) return;
+    if (keyed) {      // keys at stride world (k_dec_select<true> with nblk = world)
+        val[r] = cand[4 * r]; val[world + r] = cand[4 * r + 1]; val[2 * world + r] = cand[4 * r + 2];
+        idx[r] = (int)cand[4 * r + 3];
+    } else { val[r] = cand[2 * r]; idx[r] = (int)cand[2 * r + 1]; }
 }
 
 
@@ -1022,15 +1047,17 @@ __global__ __launch_bounds__(256) void k_decb_attn(const VhDecBatchAttn bt, floa
                            bt.part_o[b], bt.part_ml[b], bt.cnt[b], bt.attn_out[b], nq, nkv, max_ctx, max_splits, scale, VhGranVec{}, VhGranVec{});
 }
 
-// final RMSNorm + LM head + per-block argmax for every sequence of the batch (the 424 MB table is read once)
-template <int NJ>
+// final RMSNorm + LM head + per-block argmax for every sequence of the batch (the 424 MB table is read once); SAMP: sequences with
+// hd.sample[b].T > 0 compare z + G (as k_dec_lmhead<SAMP>), the others their logits (in double: the same order and winner)
+template <int NJ, bool SAMP>
 __global__ __launch_bounds__(256) void k_decb_lmhead(const VhDecBatchVec bt, const float* __restrict__ norm_w, float eps,
                                                      const uint16_t* __restrict__ W, int V, int K, const VhDecBatchHead hd,
                                                      int v0) {
     constexpr int NV = VH_BMAX * (LM_R + 1);
     __shared__ float red[4 * NV];
     __shared__ float tot[NV];
-    __shared__ float bv_s[VH_BMAX][LM_R];
+    typedef typename std::conditional<SAMP, double, float>::type BT;
+    __shared__ BT bv_s[VH_BMAX][LM_R];
     __shared__ int bi_s[VH_BMAX][LM_R];
     const int n_iter = (V + LM_R - 1) / LM_R;
     auto rows_of = [&](int it, const uint16_t* (&rows)[LM_R]) {
@@ -1042,13 +1069,16 @@ __global__ __launch_bounds__(256) void k_decb_lmhead(const VhDecBatchVec bt, con
     const uint16_t* rows[LM_R];
     if (it < n_iter) { rows_of(it, rows); gemv_issue<NJ, LM_R>(rows, K, wa); }
     float xr[VH_BMAX][NJ][8];
-    float ss[VH_BMAX], inv[VH_BMAX], best[VH_BMAX];
+    float ss[VH_BMAX], inv[VH_BMAX];
+    BT best[VH_BMAX];
     int besti[VH_BMAX];
+    unsigned long long draw[VH_BMAX];
 #pragma unroll
     for (int b = 0; b < VH_BMAX; ++b) {
         const int bb = min(b, bt.n - 1);
         ss[b] = load_add_norm<NJ>(bt.x_in[bb], bt.delta[bb], norm_w, nullptr, K, xr[b]);
         inv[b] = 0.f; best[b] = -INFINITY; besti[b] = 0x7fffffff;
+        draw[b] = (SAMP && b < bt.n && hd.sample[b].T > 0.0) ? (unsigned long long)(hd.sample[b].draw0 + *hd.ngen[b]) : 0ull;
     }
     bool first = true;
     while (it < n_iter) {
@@ -1072,7 +1102,10 @@ __global__ __launch_bounds__(256) void k_decb_lmhead(const VhDecBatchVec bt, con
                 float v = tot[b * (LM_R + 1) + threadIdx.x];
                 v *= inv[b];
                 if (hd.logits[b]) hd.logits[b][v0 + n0 + threadIdx.x] = v;
-                if (v > best[b]) { best[b] = v; besti[b] = v0 + n0 + threadIdx.x; }
+                if (SAMP) {
+                    const double s = hd.sample[b].T > 0.0 ? vhs_perturbed(v, v0 + n0 + threadIdx.x, hd.sample[b], draw[b]) : (double)v;
+                    if (s > best[b]) { best[b] = s; besti[b] = v0 + n0 + threadIdx.x; }
+                } else if (v > best[b]) { best[b] = v; besti[b] = v0 + n0 + threadIdx.x; }
             }
         }
         first = false;
@@ -1084,11 +1117,34 @@ __global__ __launch_bounds__(256) void k_decb_lmhead(const VhDecBatchVec bt, con
     __syncthreads();
     if ((int)threadIdx.x < bt.n) {
         const int b = threadIdx.x;
-        float bv = bv_s[b][0]; int bi = bi_s[b][0];
+        BT bv = bv_s[b][0]; int bi = bi_s[b][0];
         for (int r = 1; r < LM_R; ++r)
             if (bv_s[b][r] > bv || (bv_s[b][r] == bv && bi_s[b][r] < bi)) { bv = bv_s[b][r]; bi = bi_s[b][r]; }
-        hd.blk_val[b][blockIdx.x] = bv; hd.blk_idx[b][blockIdx.x] = bi;
+        if (SAMP && hd.sample[b].T > 0.0) vhs_key3(bv, hd.blk_val[b] + blockIdx.x, gridDim.x);
+        else hd.blk_val[b][blockIdx.x] = bv;
+        hd.blk_idx[b][blockIdx.x] = bi;
     }
+}
+
+// ---- filtered draws (top-k / top-p) after the LM head: one workgroup per request row (vh_sample.h) ----------------------------
+#define SAMPLE_NT 1024
+__global__ __launch_bounds__(SAMPLE_NT) void k_dec_sample(const VhDecSampleJob job) {
+    __shared__ VhsShared<SAMPLE_NT / 64> sh;
+    const int b = blockIdx.x;
+    const int n = *job.ngen[b];
+    const float* row = job.logits[b] + (size_t)min(n, job.hist_rows - 1) * job.V;
+    double best; int bi;
+    vhs_row<SAMPLE_NT>(row, job.V, job.sample[b], (unsigned long long)(job.sample[b].draw0 + n), sh, best, bi);
+    if (threadIdx.x == 0) { vhs_key3(best, job.blk_val[b], 1); job.blk_idx[b][0] = bi; }
+}
+// per-operator entry vh_sample_rows: row r = logits + r * ld (ld = 0: one row for every draw), draw = draw0 + r
+template <int NT>
+__global__ __launch_bounds__(NT) void k_sample_rows(const float* __restrict__ logits, long ld, int V, const VhSampleParams sp,
+                                                    int* __restrict__ tokens) {
+    __shared__ VhsShared<NT / 64> sh;
+    double best; int bi;
+    vhs_row<NT>(logits + (size_t)blockIdx.x * ld, V, sp, (unsigned long long)(sp.draw0 + blockIdx.x), sh, best, bi);
+    if (threadIdx.x == 0) tokens[blockIdx.x] = (bi >= 0 && bi < V) ? bi : 0;
 }
 
 template <typename F>
@@ -1235,20 +1291,40 @@ int vhk_dec_down(hipStream_t st, const float* hbuf, const int* route, const uint
 
 int vhk_dec_lmhead(hipStream_t st, const float* x_in, const float* delta, const float* norm_w, float eps,
                    const uint16_t* W, int V, int K, float* logits, float* blk_val, int* blk_idx, int grid,
-                   const int* ngen_ptr, int hist_rows, int v0, int Vfull, const VhXchg* cx) {
+                   const int* ngen_ptr, int hist_rows, int v0, int Vfull, const VhXchg* cx, const VhSampleParams* sample) {
+    const bool samp = sample && sample->T > 0.0;
+    if (samp && !ngen_ptr) return -1;
+    const VhSampleParams sp = samp ? *sample : VhSampleParams{};
     return pick_nj(K, [&](auto nj) {
-        hipLaunchKernelGGL((k_dec_lmhead<decltype(nj)::value>), dim3(grid), dim3(256), 0, st, x_in, delta, norm_w, eps,
-                           W, V, K, logits, blk_val, blk_idx, ngen_ptr, hist_rows, v0, Vfull, xchg_or_none(cx));
+        if (samp)
+            hipLaunchKernelGGL((k_dec_lmhead<decltype(nj)::value, true>), dim3(grid), dim3(256), 0, st, x_in, delta, norm_w, eps,
+                               W, V, K, logits, blk_val, blk_idx, ngen_ptr, hist_rows, v0, Vfull, xchg_or_none(cx), sp);
+        else
+            hipLaunchKernelGGL((k_dec_lmhead<decltype(nj)::value, false>), dim3(grid), dim3(256), 0, st, x_in, delta, norm_w, eps,
+                               W, V, K, logits, blk_val, blk_idx, ngen_ptr, hist_rows, v0, Vfull, xchg_or_none(cx), sp);
         return 0;
     });
 }
-int vhk_dec_cand(hipStream_t st, const float* blk_val, const int* blk_idx, int nblk, float* cand, int rank, int world) {
-    if (world < 1 || world > 128) return -1;
-    hipLaunchKernelGGL(k_dec_cand, dim3(1), dim3(256), 0, st, blk_val, blk_idx, nblk, cand, rank, world);
+int vhk_dec_sample(hipStream_t st, const VhDecSampleJob& job) {
+    if (job.n < 1 || job.n > VH_BMAX || job.V < 1 || job.hist_rows < 1) return -1;
+    hipLaunchKernelGGL(k_dec_sample, dim3(job.n), dim3(SAMPLE_NT), 0, st, job);
     return 0;
 }
-int vhk_dec_cand_unpack(hipStream_t st, const float* cand, int world, float* val, int* idx) {
-    hipLaunchKernelGGL(k_dec_cand_unpack, dim3(1), dim3(128), 0, st, cand, world, val, idx);
+int vhk_sample_rows(hipStream_t st, const float* logits, long ld, int rows, int V, const VhSampleParams& sp, int* tokens_out) {
+    if (rows < 1 || V < 1 || ld < 0) return -1;
+    // small rows: 256 threads (more workgroups per CU for many-draw calls); released vocab: 1024
+    if (V <= 4096) hipLaunchKernelGGL(k_sample_rows<256>, dim3(rows), dim3(256), 0, st, logits, ld, V, sp, tokens_out);
+    else hipLaunchKernelGGL(k_sample_rows<SAMPLE_NT>, dim3(rows), dim3(SAMPLE_NT), 0, st, logits, ld, V, sp, tokens_out);
+    return 0;
+}
+int vhk_dec_cand(hipStream_t st, const float* blk_val, const int* blk_idx, int nblk, float* cand, int rank, int world, int keyed) {
+    if (world < 1 || world > (keyed ? 64 : 128)) return -1;
+    if (keyed) hipLaunchKernelGGL(k_dec_cand<true>, dim3(1), dim3(256), 0, st, blk_val, blk_idx, nblk, cand, rank, world);
+    else hipLaunchKernelGGL(k_dec_cand<false>, dim3(1), dim3(256), 0, st, blk_val, blk_idx, nblk, cand, rank, world);
+    return 0;
+}
+int vhk_dec_cand_unpack(hipStream_t st, const float* cand, int world, float* val, int* idx, int keyed) {
+    hipLaunchKernelGGL(k_dec_cand_unpack, dim3(1), dim3(128), 0, st, cand, world, val, idx, keyed);
     return 0;
 }
 
@@ -1259,9 +1335,12 @@ int vhk_dec_pick(hipStream_t st, const float* blk_val, const int* blk_idx, int n
 }
 
 int vhk_dec_select(hipStream_t st, const float* blk_val, const int* blk_idx, int nblk, const uint16_t* embed, int H,
-                   int vocab, float* x_next, int* pos_ptr, int* ngen_ptr, int* out_tokens, int max_out, int mode, int set_pos) {
-    hipLaunchKernelGGL(k_dec_select, dim3(1), dim3(256), 0, st, blk_val, blk_idx, nblk, embed, H, vocab, x_next, pos_ptr,
-                       ngen_ptr, out_tokens, max_out, mode, set_pos);
+                   int vocab, float* x_next, int* pos_ptr, int* ngen_ptr, int* out_tokens, int max_out, int mode, int set_pos,
+                   int keyed) {
+    if (keyed) hipLaunchKernelGGL(k_dec_select<true>, dim3(1), dim3(256), 0, st, blk_val, blk_idx, nblk, embed, H, vocab, x_next, pos_ptr,
+                                  ngen_ptr, out_tokens, max_out, mode, set_pos);
+    else hipLaunchKernelGGL(k_dec_select<false>, dim3(1), dim3(256), 0, st, blk_val, blk_idx, nblk, embed, H, vocab, x_next, pos_ptr,
+                            ngen_ptr, out_tokens, max_out, mode, set_pos);
     return 0;
 }
 
@@ -1297,7 +1376,10 @@ int vhk_decb_lmhead(hipStream_t st, const VhDecBatchVec& bt, const float* norm_w
     return pick_nj(K, [&](auto nj) {
         constexpr int NJ = decltype(nj)::value;
         if (NJ > 2) return -1;
-        hipLaunchKernelGGL((k_decb_lmhead<(NJ > 2 ? 2 : NJ)>), dim3(grid), dim3(256), 0, st, bt, norm_w, eps, W, V, K, hd, v0);
+        bool samp = false;
+        for (int b = 0; b < bt.n; ++b) samp = samp || hd.sample[b].T > 0.0;
+        if (samp) hipLaunchKernelGGL((k_decb_lmhead<(NJ > 2 ? 2 : NJ), true>), dim3(grid), dim3(256), 0, st, bt, norm_w, eps, W, V, K, hd, v0);
+        else hipLaunchKernelGGL((k_decb_lmhead<(NJ > 2 ? 2 : NJ), false>), dim3(grid), dim3(256), 0, st, bt, norm_w, eps, W, V, K, hd, v0);
         return 0;
     });
 }

@@ -135,7 +135,23 @@ struct VhDecBatchAttn {
     const float* qkv[VH_BMAX]; int pos[VH_BMAX]; const int* table[VH_BMAX];
     float* part_o[VH_BMAX]; float* part_ml[VH_BMAX]; int* cnt[VH_BMAX]; float* attn_out[VH_BMAX];
 };
-struct VhDecBatchHead { float* logits[VH_BMAX]; float* blk_val[VH_BMAX]; int* blk_idx[VH_BMAX]; };   // logits[b]: nullable full-vocab row
+// seeded sampling of one request (vh_sample.h; the vh_sampling of the C ABI in double): T = 0 greedy, top_k 0 / top_p >= 1 off;
+// the draw of a token is draw0 + its index in the request's output (counters[1] on the device)
+struct VhSampleParams { double T, top_p; int top_k, pad_; unsigned long long seed; long long draw0; };
+// logits[b]: nullable full-vocab row; sample[b]: T > 0 folds the Gumbel-max draw into the per-block argmax (the SAMP instantiation),
+// ngen[b] = the sequence's counters + 1
+struct VhDecBatchHead {
+    float* logits[VH_BMAX]; float* blk_val[VH_BMAX]; int* blk_idx[VH_BMAX];
+    VhSampleParams sample[VH_BMAX]; const int* ngen[VH_BMAX];
+};
+// filtered draws (top-k / top-p) after the LM head: block b reads row logits[b] + min(*ngen[b], hist_rows - 1) * V and leaves its
+// draw in blk_val[b][0] / blk_idx[b][0] (k_dec_select then runs with nblk = 1)
+struct VhDecSampleJob {
+    const float* logits[VH_BMAX]; const int* ngen[VH_BMAX]; float* blk_val[VH_BMAX]; int* blk_idx[VH_BMAX];
+    VhSampleParams sample[VH_BMAX]; int hist_rows, V, n;
+};
+int vhk_dec_sample(hipStream_t st, const VhDecSampleJob& job);
+int vhk_sample_rows(hipStream_t st, const float* logits, long ld, int rows, int V, const VhSampleParams& sp, int* tokens_out);
 int vhk_decb_gemv(hipStream_t st, const VhDecBatchVec& bt, const float* norm_w, float eps, const uint16_t* W, int N, int K, int norm);
 int vhk_decb_attn(hipStream_t st, const VhDecBatchAttn& bt, int n, float* kcache, float* vcache, const float* rope_cos,
                   const float* rope_sin, int nq, int nkv, int max_ctx, int max_splits, float scale);
@@ -148,12 +164,15 @@ int vhk_dec_down(hipStream_t st, const float* hbuf, const int* route, const uint
                  const VhXchg* px = nullptr);
 int vhk_dec_lmhead(hipStream_t st, const float* x_in, const float* delta, const float* norm_w, float eps,
                    const uint16_t* W, int V, int K, float* logits, float* blk_val, int* blk_idx, int grid,
-                   const int* ngen_ptr, int hist_rows, int v0, int Vfull, const VhXchg* cx = nullptr);
-int vhk_dec_cand(hipStream_t st, const float* blk_val, const int* blk_idx, int nblk, float* cand, int rank, int world);
-int vhk_dec_cand_unpack(hipStream_t st, const float* cand, int world, float* val, int* idx);
+                   const int* ngen_ptr, int hist_rows, int v0, int Vfull, const VhXchg* cx = nullptr,
+                   const VhSampleParams* sample = nullptr);   // sample: temperature-only draw (T > 0; ngen_ptr required)
+// keyed: sampled candidates (the 3-float keys of vh_sample.h vhs_key3 at stride nblk in blk_val; cand holds [world][4])
+int vhk_dec_cand(hipStream_t st, const float* blk_val, const int* blk_idx, int nblk, float* cand, int rank, int world, int keyed = 0);
+int vhk_dec_cand_unpack(hipStream_t st, const float* cand, int world, float* val, int* idx, int keyed = 0);
 int vhk_dec_pick(hipStream_t st, const float* blk_val, const int* blk_idx, int nblk, int vocab, int* token_out, float* value_out);
 int vhk_dec_select(hipStream_t st, const float* blk_val, const int* blk_idx, int nblk, const uint16_t* embed, int H,
-                   int vocab, float* x_next, int* pos_ptr, int* ngen_ptr, int* out_tokens, int max_out, int mode, int set_pos);
+                   int vocab, float* x_next, int* pos_ptr, int* ngen_ptr, int* out_tokens, int max_out, int mode, int set_pos,
+                   int keyed = 0);
 
 // ---- GEMM (vh_gemm.hip) -------------------------------------------------------------
 // C[orow(m), n] = epilogue( sum_k A[arow(m,k), k] * W[n, k] )

@@ -227,6 +227,17 @@ class MixtralEngine:
         base = self.workspace.data_ptr()
         return self.workspace[ptr - base: ptr - base + 4 * n].view(torch.int32)
 
+    def set_sampling(self, temperature=0.0, top_k=0, top_p=1.0, seed=0, draw0=0):
+        """seeded sampling of the following prefill / decode calls (vh_mixtral_set_sampling; temperature 0 = greedy).  The draw
+        of generated token i is draw0 + i (i counts from the prefill's token), so the ids are a function of the arguments."""
+        s = _lib.sampling(temperature, top_k, top_p, seed, draw0)
+        check(self.lib.vh_mixtral_set_sampling(self.h, C.byref(s)), "vh_mixtral_set_sampling")
+
+    def seq_set_sampling(self, s, temperature=0.0, top_k=0, top_p=1.0, seed=0, draw0=0):
+        """seeded sampling of sequence s (vh_mixtral_seq_set_sampling); seq_alloc / seq_free / reset restore greedy."""
+        p = _lib.sampling(temperature, top_k, top_p, seed, draw0)
+        check(self.lib.vh_mixtral_seq_set_sampling(self.h, int(s), C.byref(p)), "vh_mixtral_seq_set_sampling")
+
     def seq_alloc(self):
         """-> sequence slot id (raises VitaHipError, code VH_E_FULL, when every slot is taken)."""
         s = self.lib.vh_mixtral_seq_alloc(self.h)

@@ -238,9 +238,23 @@ class VITAMixtralForCausalLM(_HipModule):
     def generate(self, input_ids=None, images=None, audios=None, do_sample=False, temperature=None, top_p=None,
                  num_beams=1, output_scores=False, return_dict_in_generate=False, max_new_tokens=None,
                  use_cache=True, stopping_criteria=None, inputs_embeds=None, attention_mask=None,
-                 eos_token_id=None, streamer=None, **kwargs):
-        if do_sample or num_beams != 1:
-            raise NotImplementedError("vita_amd implements greedy decoding (do_sample=False, num_beams=1)")
+                 eos_token_id=None, streamer=None, top_k=None, seed=None, **kwargs):
+        """HF generate.  do_sample=True draws on the device (temperature -> top-k -> top-p, Gumbel-max over a Philox stream keyed
+        by `seed`; include/vita_hip.h vh_sampling) and needs seed=: the ids are a function of the request.  Unset parameters take
+        HF's defaults (temperature 1.0, top_k 50, top_p 1.0).  scores stay the raw logits."""
+        if num_beams != 1:
+            raise NotImplementedError("vita_amd implements num_beams=1 (greedy or seeded sampling)")
+        if do_sample and seed is None:
+            raise NotImplementedError("vita_amd samples only with a seed: pass seed= with do_sample=True (no hidden RNG state)")
+        if do_sample:
+            temperature = 1.0 if temperature is None else float(temperature)
+            top_k = 50 if top_k is None else int(top_k)
+            top_p = 1.0 if top_p is None else float(top_p)
+            if not temperature > 0:       # as HF's TemperatureLogitsWarper: sampling needs a strictly positive temperature
+                raise ValueError(f"do_sample=True needs temperature > 0 (got {temperature}); use do_sample=False for greedy")
+            if self.engine.vocab_sharded and (top_k > 0 or top_p < 1.0):
+                raise ValueError("top-k / top-p need an unsharded LM head (this model's head is vocab-sharded over the TP ranks); "
+                                 "pass top_k=0 and top_p=1.0 for temperature-only sampling (HF's default top_k is 50)")
         max_new = int(max_new_tokens or self.generation_config.max_new_tokens or 20)
         if max_new > self.max_new_tokens:
             raise ValueError(f"max_new_tokens={max_new} exceeds the engine capacity {self.max_new_tokens}")
@@ -256,6 +270,10 @@ class VITAMixtralForCausalLM(_HipModule):
             raise ValueError("prompt + max_new_tokens exceeds the KV-cache capacity")
         ev[1].record()
         eng = self.engine
+        if do_sample:
+            eng.set_sampling(temperature, top_k, top_p, int(seed))
+        else:
+            eng.set_sampling()
         eng.prefill(emb)
         prompt = input_ids if input_ids is not None else torch.zeros((1, 0), dtype=torch.long, device=self._device)
         prompt = prompt.to(self._device)

@@ -436,3 +436,23 @@ def lmhead_argmax(x, norm_w, eps, w, delta=None, nblk=1024):
     check(_lib.load().vh_lmhead_argmax(_p(x), _p(delta), _p(norm_w), float(eps), _p(w), V, H, _p(logits), _p(tok), _p(bv), _p(bi), nblk,
                                        _stream()), "vh_lmhead_argmax")
     return logits, tok
+
+
+def sample_rows(logits, rows=None, temperature=1.0, top_k=0, top_p=1.0, seed=0, draw0=0):
+    """Seeded draws (vh_sample_rows, the engine's device code): token r of `rows` is sampled from row r of logits fp32 [R, V]
+    at draw index draw0 + r; a 1-D logits row is broadcast to `rows` draws.  -> int32 [rows]."""
+    _dev(logits)
+    if logits.dtype != torch.float32:
+        raise TypeError("logits must be float32")
+    if logits.dim() == 1:
+        ld, V, n = 0, logits.shape[0], int(rows if rows is not None else 1)
+    else:
+        if logits.stride(1) != 1:
+            raise ValueError("logits rows must be contiguous")
+        ld, V, n = logits.stride(0), logits.shape[1], int(rows if rows is not None else logits.shape[0])
+        if n > logits.shape[0]:
+            raise ValueError("rows exceeds the logits rows")
+    tok = torch.empty(n, dtype=torch.int32, device=logits.device)
+    s = _lib.sampling(temperature, top_k, top_p, seed, draw0)
+    check(_lib.load().vh_sample_rows(_p(logits), ld, n, V, C.byref(s), _p(tok), _stream()), "vh_sample_rows")
+    return tok

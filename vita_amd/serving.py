@@ -14,7 +14,9 @@ input processor (web_demo/vllm_tools/vllm_file/mixtral.py:194-311) we tile each 
 dynamic_preprocess (+thumbnail), expand its placeholder to 256 tokens per tile and each audio placeholder to
 `((T-1)//2-1)//2 -> (.-1)//2+1` tokens.  Audio features arrive CMVN-normalised by WhaleFeatureExtractor (the
 vLLM audio tower has no global_cmvn: mixtral.py:1245-1247), so the encoder is run with `normalized=True`.
-temperature <= 0.01 is greedy (the demo's setting); other sampling is not implemented.
+Sampling: a request with SamplingParams(seed=...) and temperature > 0 is sampled on the device (temperature -> top_k -> top_p,
+Gumbel-max over a Philox stream keyed by the seed: include/vita_hip.h vh_sampling), so its ids are a function of the request;
+unseeded temperature <= 0.01 is greedy (the demo's setting) and unseeded sampling above it raises.
 
 Concurrent requests (the interactive demo's AsyncLLMEngine, web_interactive_demo.py:126,315-328,942-951): the engine's
 KV cache is a pool of 64-token pages addressed through per-sequence block tables (vh_mixtral_seq_* in
@@ -45,6 +47,22 @@ class SamplingParams:
     stop_token_ids: Optional[List[int]] = None
     top_p: float = 1.0
     top_k: int = -1
+    seed: Optional[int] = None
+
+
+def sampling_of(sp):
+    """the device sampling of a request (dict for MixtralEngine.set_sampling / seq_set_sampling), or None for greedy: seeded
+    requests with temperature > 0 sample; vLLM's top_k = -1 (off) is 0."""
+    if sp is None or sp.seed is None or not sp.temperature or sp.temperature <= 0:
+        return None
+    top_k = 0 if sp.top_k is None or int(sp.top_k) < 0 else int(sp.top_k)
+    return dict(temperature=float(sp.temperature), top_k=top_k, top_p=1.0 if sp.top_p is None else float(sp.top_p), seed=int(sp.seed))
+
+
+def sample_kwargs(sp):
+    """generate() keywords of a request"""
+    s = sampling_of(sp)
+    return dict(do_sample=False) if s is None else dict(do_sample=True, **s)
 
 
 @dataclass
@@ -175,8 +193,9 @@ class LLM:
         images = images if isinstance(images, list) else [images]
         audios = mm.get("audio", [])
         audios = audios if isinstance(audios, list) else [audios]
-        if sp.temperature is not None and sp.temperature > 0.011:
-            raise NotImplementedError("vita_amd serves greedy decoding (temperature <= 0.01, the reference demo's setting)")
+        if sampling_of(sp) is None and sp.temperature is not None and sp.temperature > 0.011:
+            raise NotImplementedError("vita_amd samples only with a seed: pass SamplingParams(seed=...) "
+                                      "(unseeded temperature <= 0.01 stays greedy, the reference demo's setting)")
         dev = self.model.device
         max_tokens = min(int(sp.max_tokens), int(self.model.max_new_tokens))   # the engine's output buffer is the hard cap
         sent, tiles = self._expand(ids, images, audios)
@@ -228,9 +247,9 @@ class LLM:
         enc.normalized_input = req["normalized"]
         try:
             out = self.model.generate(torch.tensor([sent], dtype=torch.long, device=dev), images=pix,
-                                      audios={"audios": feats.to(dev), "lengths": lens.to(dev)}, do_sample=False,
-                                      num_beams=1, return_dict_in_generate=True, max_new_tokens=max_tokens,
-                                      eos_token_id=list(req["eos"]), streamer=streamer)
+                                      audios={"audios": feats.to(dev), "lengths": lens.to(dev)}, num_beams=1,
+                                      return_dict_in_generate=True, max_new_tokens=max_tokens,
+                                      eos_token_id=list(req["eos"]), streamer=streamer, **sample_kwargs(sp))
         finally:
             enc.normalized_input = False
         gen = out.sequences[0, len(sent):].tolist()
@@ -322,13 +341,14 @@ class ContinuousBatcher:
         self.errors = {}                  # request id -> exception of a request that failed alone (event reason "error")
         self.stats = {"iterations": 0, "prefills": 0, "preemptions": 0, "decode_steps": 0, "failed": 0}
 
-    def add(self, request_id, embeds, max_tokens, eos=()):
+    def add(self, request_id, embeds, max_tokens, eos=(), sampling=None):
+        """sampling: None (greedy) or the keywords of MixtralEngine.seq_set_sampling without draw0 (see sampling_of)."""
         S = int(embeds.shape[0])
         if S + 2 > self.eng.max_ctx or S > self.eng.max_prefill:
             raise ValueError(f"prompt of {S} tokens exceeds the engine (max_prefill {self.eng.max_prefill}, pool "
                              f"{self.eng.max_ctx} tokens)")
         self.waiting.append(dict(id=request_id, emb=embeds, max_tokens=min(int(max_tokens), self.eng.max_new),
-                                 eos=set(eos), out=[], seq=None, base=0))
+                                 eos=set(eos), out=[], seq=None, base=0, sampling=sampling))
 
     def abort(self, request_id):
         for r in list(self.running):
@@ -380,6 +400,16 @@ class ContinuousBatcher:
             except Exception as e:
                 self._fail(r, e, events)
                 continue
+            if r["sampling"] is not None:
+                # draw index of the next token = tokens already generated (r["base"] after a recompute preemption): the
+                # continued ids are the ones an unpreempted run draws
+                try:
+                    self.eng.seq_set_sampling(r["seq"], draw0=r["base"], **r["sampling"])
+                except Exception as e:
+                    self.eng.seq_free(r["seq"])
+                    r["seq"] = None
+                    self._fail(r, e, events)
+                    continue
             try:
                 self._prefill(r)
             except Exception as e:
@@ -540,7 +570,7 @@ class AsyncLLMEngine:
                 try:
                     req = self.llm._prepare(inputs, sp)
                     emb = self.llm._embed(req)
-                    self.batcher.add(rid, emb, req["max_tokens"], req["eos"])
+                    self.batcher.add(rid, emb, req["max_tokens"], req["eos"], sampling=sampling_of(sp))
                     state[rid] = (req["ids"], sp, [])
                 except BaseException as e:          # surfaced to the caller's iterator
                     self._post(rid, e)
