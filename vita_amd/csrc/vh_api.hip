@@ -407,7 +407,7 @@ struct vh_mixtral {
         px = cv.take<float>(Sm * H); pxn = cv.take<float>(Sm * H);
         pqkv = cv.take<float>(Sm * nqkv);
         pq = cv.take<float>(Sm * nq * hd); pattn = cv.take<float>(Sm * nq * hd);
-        py = cv.take<float>(4 * 2 * Sm * H);   // py: up to 4 K-split slabs of the MoE down projection / 8 of the projections
+        py = cv.take<float>(4 * (size_t)down_slab(H));   // up to 4 K-split slabs of the MoE down projection / 8 of the projections
         ptmp = cv.take<float>(Sm * H);
         pwts = cv.take<float>(2 * Sm);
         pids = cv.take<int>(2 * Sm); pgoff = cv.take<int>(E + 1);
@@ -463,6 +463,12 @@ struct vh_mixtral {
         vcache = cv.take<float>((size_t)c.n_layers * nkv * c.max_ctx * hd);
         return al(cv.off, 256);
     }
+    // py layout: a K-split slab of a projection output (QKV, O) `ncols` wide holds max_prefill rows, one of the MoE down
+    // projection 2 max_prefill (a row per routed token slot); the overlapped tensor-parallel steps keep the slabs of column
+    // half h of the O / down projection from py_half(h) on (py_half(0) is py itself)
+    long proj_slab(long ncols) const { return (long)c.max_prefill * ncols; }
+    long down_slab(long ncols) const { return 2L * c.max_prefill * ncols; }
+    float* py_half(int h) const { return py + (size_t)h * 8 * c.max_prefill * (H / 2); }
     int hist_rows() const { return c.logit_rows > 1 ? c.logit_rows : 1; }
     int cand_world() const { return c.tp_world > 1 ? c.tp_world : 1; }   // slots of the vocab-sharded head's candidate vector (loop-back: this rank's only)
     void derive() {
@@ -725,13 +731,87 @@ static int head_and_select(vh_mixtral* m, hipStream_t st, const float* x_in, con
         if ((expr) != 0) return launch_failed(what);   \
     } while (0)
 
+}  // extern "C" (reduce_rows below is a template)
+
+// Row-parallel output under tensor parallelism (o_proj and the experts are RowParallel in the reference: vllm_file/mixtral.py:
+// 405-414, 470-476): px += all-reduce(this rank's partial rows).  produce(h, part, ncols) enqueues the partial rows of output
+// columns [h * ncols, (h + 1) * ncols) into part ([Sn][ncols]) on st.  overlap: two column halves, the all-reduce of half 0
+// (comm stream) runs under the producer of half 1, then one add of both; otherwise all columns in one pass.
+template <class Produce>
+static int reduce_rows(vh_mixtral* m, hipStream_t st, int Sn, bool overlap, Produce&& produce) {
+    const int H = m->H, H2 = H / 2;
+    int rc;
+    if (!overlap) {
+        if ((rc = produce(0, m->ptmp, H)) != VH_OK) return rc;
+        if (m->allreduce(m->ptmp, (long)Sn * H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
+        VH_TRY(vhk_add(st, m->px, m->ptmp, (long)Sn * H), "add");
+        return VH_OK;
+    }
+    for (int h = 0; h < 2; ++h) {
+        float* part = m->ptmp + (size_t)h * Sn * H2;
+        if ((rc = produce(h, part, H2)) != VH_OK) return rc;
+        (void)hipEventRecord(m->ev_c[h], st);
+        (void)hipStreamWaitEvent(m->cs, m->ev_c[h], 0);
+        if (m->allreduce(part, (long)Sn * H2, m->cs) != 0) return fail(VH_E_COMM, "all-reduce failed");
+        (void)hipEventRecord(m->ev_r[h], m->cs);
+    }
+    (void)hipStreamWaitEvent(st, m->ev_r[0], 0);
+    (void)hipStreamWaitEvent(st, m->ev_r[1], 0);
+    VH_TRY(vhk_add_halves(st, m->px, m->ptmp, m->ptmp + (size_t)Sn * H2, Sn, H), "add");
+    return VH_OK;
+}
+
+// Weight-streaming MoE over n token rows, from the bf16 hi/lo planes (pxn_hi / lo) and top-2 ids (pids) that vhk_rmsnorm_route
+// left: the rows are sorted by expert, gate|up runs one tall m-tile per expert (weights cross the fabric once) and emits the
+// planes of h (ph_hi / lo), the down projection is K-split into `nslab` partial slabs of py that the combine adds.
+struct MoeGemms {
+    VhGemmPsArgs gate_up, down;   // launched by the caller (down: all H columns)
+    int nslab;                    // slabs the combine adds (1 when the kernel picks the split ...
+    const int* nslab_dev;         // ... and reports it here; null otherwise)
+};
+static int moe_gemms(vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, int n, MoeGemms* p) {
+    const int H = m->H, I = m->I, E = m->E;
+    VH_TRY(vhk_moe_sort(st, m->pids, n, E, m->pgoff, m->pstok, m->psslot), "sort");
+    *p = MoeGemms{};
+    VhGemmPsArgs &g = p->gate_up, &d = p->down;
+    g.A_hi = m->pxn_hi; g.A_lo = m->pxn_lo; g.lda = H; g.a_rowidx = m->pstok;
+    g.W = w.w1; g.W_up = w.w3; g.ldw = H; g.w_group_stride = (long)I * H;
+    g.group_off = m->pgoff; g.ngroups = E;
+    g.C_hi = m->ph_hi; g.C_lo = m->ph_lo; g.ldc_split = I; g.M = 2 * n; g.N = I; g.K = H; g.ksplit = 1;
+    int ks = vh_tuning()->moe_ksplit;   // 1 .. 4 slabs, or -n: chosen by the kernel from the expert sizes (up to n)
+    if (ks == 0) ks = 1;
+    if (ks > 4) ks = 4;
+    if (ks < -4) ks = -4;
+    if (ks > (I >> 6)) ks = 1;
+    d.A_hi = m->ph_hi; d.A_lo = m->ph_lo; d.lda = I;
+    d.W = w.w2; d.ldw = I; d.w_group_stride = (long)H * I;
+    d.group_off = m->pgoff; d.ngroups = E;
+    d.C = m->py; d.ldc = H; d.c_rowidx = m->psslot; d.M = 2 * n; d.N = H; d.K = I;
+    d.ksplit = ks; d.c_split_stride = m->down_slab(H); d.nslab_out = m->pnslab;
+    p->nslab = ks < 0 ? 1 : ks;
+    p->nslab_dev = ks < 0 ? m->pnslab : nullptr;
+    return VH_OK;
+}
+// the down projection of output columns [h * ncols, (h + 1) * ncols) into the slabs from py_half(h), then their
+// routing-weighted sum into part ([n][ncols], zeroed first)
+static int moe_down(vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, const MoeGemms& p, int n, int h, int ncols,
+                    float* part) {
+    VhGemmPsArgs d = p.down;
+    d.W = w.w2 + (size_t)h * ncols * m->I; d.N = ncols; d.C = m->py_half(h); d.ldc = ncols; d.c_split_stride = m->down_slab(ncols);
+    VH_TRY(vhk_gemm_ps(st, d), "down gemm");
+    if (hipMemsetAsync(part, 0, (size_t)n * ncols * sizeof(float), st) != hipSuccess) return fail(VH_E_HIP, "memset failed");
+    VH_TRY(vhk_moe_combine(st, part, d.C, m->pwts, n, ncols, p.nslab, d.c_split_stride, p.nslab_dev), "combine");
+    return VH_OK;
+}
+
 static int prefill_impl(vh_mixtral* m, const float* embeds, int Sn, int pos0, float* logits_out, float* hidden_dbg,
                         hipStream_t st) {
     if (Sn < 1 || Sn > m->c.max_prefill) return fail(VH_E_SHAPE, "prefill length %d outside [1,%d]", Sn, m->c.max_prefill);
     if (pos0 < 0 || pos0 + Sn >= m->c.max_ctx) return fail(VH_E_SHAPE, "prefill exceeds KV capacity %d", m->c.max_ctx);
-    const int H = m->H, I = m->I, E = m->E, nq = m->nq, nkv = m->nkv, hd = m->hd;
+    const int H = m->H, nq = m->nq, nkv = m->nkv, hd = m->hd, KO = nq * hd;
     const bool tp = m->c.tp_world > 1 || vh_tuning()->force_allreduce;
     const float scale = 1.0f / sqrtf((float)hd);
+    int rc;
     if (hipMemcpyAsync(m->px, embeds, (size_t)Sn * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
         return fail(VH_E_HIP, "prefill: embed copy failed");
     if (hipMemsetAsync(m->counters + 1, 0, 3 * sizeof(int), st) != hipSuccess) return fail(VH_E_HIP, "memset failed");
@@ -740,8 +820,7 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, int Sn, int pos0, fl
         hipMemsetAsync(m->logits, 0, (size_t)m->hist_rows() * m->V * sizeof(float), st) != hipSuccess)
         return fail(VH_E_HIP, "memset failed");   // vocab-sharded head: a kept score row holds THIS rank's slice, zeros elsewhere
     // overlapped tensor-parallel prefill: needs a collective that takes a stream, and halves that stay 16-byte rows
-    const int H2 = H / 2;
-    const bool overlap = tp && vh_tuning()->tp_overlap != 0 && m->stream_capable() && (H2 % 4) == 0 && Sn >= 16;
+    const bool overlap = tp && vh_tuning()->tp_overlap != 0 && m->stream_capable() && ((H / 2) % 4) == 0 && Sn >= 16;
     if (overlap) {
         if (m->ensure_comm_stream() != 0) return fail(VH_E_HIP, "prefill: comm stream creation failed");
         // the comm stream starts behind everything already queued on the compute stream
@@ -750,10 +829,9 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, int Sn, int pos0, fl
     }
 
     // py holds 8 * max_prefill * H floats: K-split slabs of the projections (and of the MoE down projection later)
-    const long Sm = m->c.max_prefill;
     int qkv_slabs = (int)((8L * H) / m->nqkv);
     if (qkv_slabs > 4) qkv_slabs = 4;
-    const bool stream_attn = vh_tuning()->prefill_attn_gemm == 0 && qkv_slabs >= 1 && (H % 64) == 0 && ((nq * hd) % 64) == 0 &&
+    const bool stream_attn = vh_tuning()->prefill_attn_gemm == 0 && qkv_slabs >= 1 && (H % 64) == 0 && (KO % 64) == 0 &&
                              H <= 4096 && (m->nqkv % 4) == 0;
     // (r03) K-split slabs are summed by the norm kernel that consumes the rows (VhRowUpdate) on the single-rank path;
     // vh_tune("prefill_fuse_rows", 0) restores the separate slab-sum / combine launches
@@ -769,19 +847,18 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, int Sn, int pos0, fl
     bool combine_pending = false;
     int pend_nslab = 1;
     const int* pend_nslab_dev = nullptr;
-    const long pend_slab = (long)2 * m->c.max_prefill * H;
     for (int l = 0; l < m->c.n_layers; ++l) {
         const vh_mixtral_layer& w = m->L[l];
         float* kc = m->kcache + (size_t)l * nkv * m->c.max_ctx * hd;
         float* vc = m->vcache + (size_t)l * nkv * m->c.max_ctx * hd;
-        bool o_pending = false;
+        // ---- attention norm + QKV + RoPE
         if (stream_attn) {
             // weight-streaming projections (vh_gemm_ps.hip): the norm emits the bf16 hi/lo planes, the 35 row tiles of
             // S = 552 run as 3 m-tiles per 256 weight rows and the kernel picks a K split that fills the CUs
             // (72 QKV tiles x 3 slabs); the partial slabs are summed by the consumer (RoPE / KV write)
             // (r03) the previous layer's expert outputs are still K-split slabs in py: this norm applies the routing-weighted
             // sum to the residual rows first (VhRowUpdate), so no combine kernel runs between the layers
-            const VhRowUpdate cu{m->py, (long)H, pend_slab, pend_nslab_dev, pend_nslab, m->pwts};
+            const VhRowUpdate cu{m->py, (long)H, m->down_slab(H), pend_nslab_dev, pend_nslab, m->pwts};
             VH_TRY(vhk_rmsnorm_route(st, m->px, nullptr, m->pxn_hi, m->pxn_lo, w.attn_norm, Sn, H, m->c.rms_eps, nullptr, 0,
                                      nullptr, nullptr, combine_pending ? &cu : nullptr), "rmsnorm");
             if (combine_pending && hidden_dbg)
@@ -791,7 +868,7 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, int Sn, int pos0, fl
             VhGemmPsArgs g{};
             g.A_hi = m->pxn_hi; g.A_lo = m->pxn_lo; g.lda = H;
             g.W = w.wqkv; g.ldw = H; g.C = m->py; g.ldc = m->nqkv; g.M = Sn; g.N = m->nqkv; g.K = H;
-            g.ksplit = -qkv_slabs; g.c_split_stride = (long)Sm * m->nqkv; g.nslab_out = m->pnslab + 1;
+            g.ksplit = -qkv_slabs; g.c_split_stride = m->proj_slab(m->nqkv); g.nslab_out = m->pnslab + 1;
             VH_TRY(vhk_gemm_ps(st, g), "qkv gemm");
             if (use_img)   // one-shot prefill under the flash kernel: RoPE + cache write + the K / V tile images in one pass
                 VH_TRY(vhk_rope_kv_img(st, m->py, m->nqkv, m->pq, kc, vc, m->rope_cos, m->rope_sin, Sn, nq, nkv, m->c.max_ctx,
@@ -808,162 +885,83 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, int Sn, int pos0, fl
             VH_TRY(vhk_rope_kv(st, m->pqkv, m->nqkv, m->pq, kc, vc, m->rope_cos, m->rope_sin, Sn, pos0, nq, nkv,
                                m->c.max_ctx, m->table, nullptr, 0), "rope");
         }
-        {
-            VhAttnArgs a{};
-            a.Q = m->pq; a.ldq = (long)nq * hd; a.hsq = hd;
-            a.K = kc; a.ldk = hd; a.hsk = (long)m->c.max_ctx * hd;
-            a.V = vc; a.ldv = hd; a.hsv = (long)m->c.max_ctx * hd;
-            a.O = m->pattn; a.ldo = (long)nq * hd;
-            a.B = 1; a.Hq = nq; a.Hkv = nkv; a.Sq = Sn; a.Sk = pos0 + Sn; a.d = hd;
-            a.causal = 1; a.q_off = pos0; a.klen = pos0 + Sn; a.chunk = 0; a.left = -1; a.scale = scale;
-            a.ktable = m->table; a.kv_rows = m->c.max_ctx;
-            if (use_img) { a.kv_img = m->kv_img; a.img_tiles = m->img_tiles; }
-            if (attn_planes) { a.O = nullptr; a.O_hi = m->ph_hi; a.O_lo = m->ph_lo; a.ldo_split = (long)nq * hd; }
-            VH_TRY(vhk_attn(st, a), "attention");
-        }
+        // ---- attention
+        VhAttnArgs a{};
+        a.Q = m->pq; a.ldq = KO; a.hsq = hd;
+        a.K = kc; a.ldk = hd; a.hsk = (long)m->c.max_ctx * hd;
+        a.V = vc; a.ldv = hd; a.hsv = (long)m->c.max_ctx * hd;
+        a.O = m->pattn; a.ldo = KO;
+        a.B = 1; a.Hq = nq; a.Hkv = nkv; a.Sq = Sn; a.Sk = pos0 + Sn; a.d = hd;
+        a.causal = 1; a.q_off = pos0; a.klen = pos0 + Sn; a.chunk = 0; a.left = -1; a.scale = scale;
+        a.ktable = m->table; a.kv_rows = m->c.max_ctx;
+        if (use_img) { a.kv_img = m->kv_img; a.img_tiles = m->img_tiles; }
+        if (attn_planes) { a.O = nullptr; a.O_hi = m->ph_hi; a.O_lo = m->ph_lo; a.ldo_split = KO; }
+        VH_TRY(vhk_attn(st, a), "attention");
+        // ---- O projection
+        bool o_pending = false;
         if (stream_attn) {
-            // O projection on the streaming kernel: planes of the attention output (written by the attention kernel itself
-            // when it is the direct-operand one), K-split slabs, slab sum fused into the FFN norm (or feeding the all-reduce
-            // under tensor parallelism)
-            const int KO = nq * hd;
+            // on the streaming kernel: planes of the attention output (written by the attention kernel itself when it is the
+            // direct-operand one), K-split slabs, slab sum fused into the FFN norm (or feeding the all-reduce under tensor
+            // parallelism)
             if (!attn_planes) VH_TRY(vhk_split_planes(st, m->pattn, KO, m->ph_hi, m->ph_lo, KO, Sn, KO), "split planes");
             VhGemmPsArgs g{};
             g.A_hi = m->ph_hi; g.A_lo = m->ph_lo; g.lda = KO;
-            g.W = w.wo; g.ldw = KO; g.M = Sn; g.K = KO; g.ksplit = -8;
-            if (tp && overlap) {
-                // column halves: the all-reduce of half 0 (comm stream) runs under the GEMM of half 1 (SURVEY 8(e);
-                // o_proj is RowParallel in the reference: vllm_file/mixtral.py:470-476)
-                for (int h = 0; h < 2; ++h) {
-                    float* part = m->ptmp + (size_t)h * Sn * H2;
-                    float* yh = m->py + (size_t)h * 8 * Sm * H2;
-                    g.W = w.wo + (size_t)h * H2 * g.ldw; g.N = H2; g.C = yh; g.ldc = H2;
-                    g.c_split_stride = Sm * H2; g.nslab_out = m->pnslab + 2 + h;
-                    VH_TRY(vhk_gemm_ps(st, g), "o gemm");
-                    VH_TRY(vhk_sum_slabs(st, part, H2, yh, H2, Sn, H2, m->pnslab + 2 + h, 1, g.c_split_stride, 0), "slab sum");
-                    (void)hipEventRecord(m->ev_c[h], st);
-                    (void)hipStreamWaitEvent(m->cs, m->ev_c[h], 0);
-                    if (m->allreduce(part, (long)Sn * H2, m->cs) != 0) return fail(VH_E_COMM, "all-reduce failed");
-                    (void)hipEventRecord(m->ev_r[h], m->cs);
-                }
-                (void)hipStreamWaitEvent(st, m->ev_r[0], 0);
-                (void)hipStreamWaitEvent(st, m->ev_r[1], 0);
-                VH_TRY(vhk_add_halves(st, m->px, m->ptmp, m->ptmp + (size_t)Sn * H2, Sn, H), "add");
-            } else {
-                g.N = H; g.C = m->py; g.ldc = H; g.c_split_stride = Sm * H; g.nslab_out = m->pnslab + 2;
+            g.ldw = KO; g.M = Sn; g.K = KO; g.ksplit = -8;
+            // output columns [h * ncols, (h + 1) * ncols) as K-split slabs from py_half(h), then (part != null) their sum into part
+            auto o_slabs = [&](int h, float* part, int ncols) -> int {
+                g.W = w.wo + (size_t)h * ncols * KO; g.N = ncols; g.C = m->py_half(h); g.ldc = ncols;
+                g.c_split_stride = m->proj_slab(ncols); g.nslab_out = m->pnslab + 2 + h;
                 VH_TRY(vhk_gemm_ps(st, g), "o gemm");
-                if (tp) {
-                    VH_TRY(vhk_sum_slabs(st, m->ptmp, H, m->py, H, Sn, H, m->pnslab + 2, 1, g.c_split_stride, 0), "slab sum");
-                    if (m->allreduce(m->ptmp, (long)Sn * H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
-                    VH_TRY(vhk_add(st, m->px, m->ptmp, (long)Sn * H), "add");
-                } else if (fuse_rows) {
-                    o_pending = true;                   // summed into px by the FFN norm below
-                } else {
-                    VH_TRY(vhk_sum_slabs(st, m->px, H, m->py, H, Sn, H, m->pnslab + 2, 1, g.c_split_stride, 1), "slab sum");
-                }
-            }
-        } else
-        {
-            VhGemmArgs g{};
-            g.A = m->pattn; g.lda = (long)nq * hd; g.a_rows = Sn; g.nseg = 1; g.seglen = nq * hd;
-            g.W = w.wo; g.ldw = (long)nq * hd; g.M = Sn; g.N = H; g.K = nq * hd;
-            if (tp && overlap) {
-                // column halves: the all-reduce of half 0 (comm stream) runs under the GEMM of half 1 (SURVEY 8(e);
-                // o_proj is RowParallel in the reference: vllm_file/mixtral.py:470-476)
-                for (int h = 0; h < 2; ++h) {
-                    float* part = m->ptmp + (size_t)h * Sn * H2;
-                    g.W = w.wo + (size_t)h * H2 * g.ldw; g.N = H2; g.C = part; g.ldc = H2;
-                    VH_TRY(vhk_gemm(st, g), "o gemm");
-                    (void)hipEventRecord(m->ev_c[h], st);
-                    (void)hipStreamWaitEvent(m->cs, m->ev_c[h], 0);
-                    if (m->allreduce(part, (long)Sn * H2, m->cs) != 0) return fail(VH_E_COMM, "all-reduce failed");
-                    (void)hipEventRecord(m->ev_r[h], m->cs);
-                }
-                (void)hipStreamWaitEvent(st, m->ev_r[0], 0);
-                (void)hipStreamWaitEvent(st, m->ev_r[1], 0);
-                VH_TRY(vhk_add_halves(st, m->px, m->ptmp, m->ptmp + (size_t)Sn * H2, Sn, H), "add");
+                if (part) VH_TRY(vhk_sum_slabs(st, part, ncols, g.C, ncols, Sn, ncols, g.nslab_out, 1, g.c_split_stride, 0), "slab sum");
+                return VH_OK;
+            };
+            if (tp) {
+                if ((rc = reduce_rows(m, st, Sn, overlap, o_slabs)) != VH_OK) return rc;
             } else {
-                if (tp) { g.C = m->ptmp; g.ldc = H; }
-                else { g.C = m->px; g.ldc = H; g.resid = m->px; g.ldr = H; }
-                VH_TRY(vhk_gemm(st, g), "o gemm");
-                if (tp) {
-                    if (m->allreduce(m->ptmp, (long)Sn * H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
-                    VH_TRY(vhk_add(st, m->px, m->ptmp, (long)Sn * H), "add");
-                }
+                if ((rc = o_slabs(0, nullptr, H)) != VH_OK) return rc;
+                if (fuse_rows) o_pending = true;   // summed into px by the FFN norm below
+                else VH_TRY(vhk_sum_slabs(st, m->px, H, m->py, H, Sn, H, m->pnslab + 2, 1, m->proj_slab(H), 1), "slab sum");
             }
-        }
-        bool moe_done = false;
-        int nslab = 1;
-        const int* nslab_dev = nullptr;
-        const long slab = (long)2 * m->c.max_prefill * H;
-        {
-            // weight-streaming MoE: the norm kernel emits the bf16 hi/lo planes directly, one tall m-tile per
-            // expert (weights cross the fabric once), gate|up emits the planes of h, the down projection is
-            // K-split into `nslab` partial slabs that the combine kernel adds
-            const VhRowUpdate ou{m->py, (long)H, (long)Sm * H, m->pnslab + 2, 1, nullptr};     // the O projection's slabs
-            VH_TRY(vhk_rmsnorm_route(st, m->px, nullptr, m->pxn_hi, m->pxn_lo, w.ffn_norm, Sn, H, m->c.rms_eps, w.wrouter,
-                                     E, m->pids, m->pwts, o_pending ? &ou : nullptr), "rmsnorm + route");
-            VH_TRY(vhk_moe_sort(st, m->pids, Sn, E, m->pgoff, m->pstok, m->psslot), "sort");
-            VhGemmPsArgs g{};
-            g.A_hi = m->pxn_hi; g.A_lo = m->pxn_lo; g.lda = H; g.a_rowidx = m->pstok;
-            g.W = w.w1; g.W_up = w.w3; g.ldw = H; g.w_group_stride = (long)I * H;
-            g.group_off = m->pgoff; g.ngroups = E;
-            g.C_hi = m->ph_hi; g.C_lo = m->ph_lo; g.ldc_split = I; g.M = 2 * Sn; g.N = I; g.K = H; g.ksplit = 1;
-            const bool prof = m->prof_stride < 0 && (l % -m->prof_stride) == 0 && m->prof_used + 2 <= m->prof_ev.size();
-            if (prof) (void)hipEventRecord(m->prof_ev[m->prof_used], st);
-            VH_TRY(vhk_gemm_ps(st, g), "gate/up gemm");
-            if (prof) { (void)hipEventRecord(m->prof_ev[m->prof_used + 1], st); m->prof_used += 2; }
-            nslab = vh_tuning()->moe_ksplit;           // < 0: chosen by the kernel from the expert sizes (up to -n)
-            if (nslab == 0) nslab = 1;
-            if (nslab > 4) nslab = 4;
-            if (nslab < -4) nslab = -4;
-            if (nslab > (I >> 6)) nslab = 1;
-            nslab_dev = nslab < 0 ? m->pnslab : nullptr;
-            VhGemmPsArgs d{};
-            d.A_hi = m->ph_hi; d.A_lo = m->ph_lo; d.lda = I;
-            d.W = w.w2; d.ldw = I; d.w_group_stride = (long)H * I;
-            d.group_off = m->pgoff; d.ngroups = E;
-            d.C = m->py; d.ldc = H; d.c_rowidx = m->psslot; d.M = 2 * Sn; d.N = H; d.K = I;
-            d.ksplit = nslab; d.c_split_stride = slab; d.nslab_out = m->pnslab;
-            if (nslab < 0) nslab = 1;                   // (the reducer reads the device value)
-            if (tp && overlap) {
-                // "all-reduce over xGMI overlapped with the expert GEMMs" (FusedMoE reduce_results, vllm_file/
-                // mixtral.py:405-414): the down projection runs as two COLUMN halves (disjoint weight rows); half
-                // 0 is combined and all-reduced on the comm stream while half 1 streams its weights
-                const long hslab = (long)2 * m->c.max_prefill * H2;            // one K-split slab of a half
-                for (int h = 0; h < 2; ++h) {
-                    float* yh = m->py + (size_t)h * 4 * hslab;
-                    float* part = m->ptmp + (size_t)h * Sn * H2;
-                    d.W = w.w2 + (size_t)h * H2 * I; d.N = H2; d.C = yh; d.ldc = H2; d.c_split_stride = hslab;
-                    VH_TRY(vhk_gemm_ps(st, d), "down gemm");
-                    if (hipMemsetAsync(part, 0, (size_t)Sn * H2 * sizeof(float), st) != hipSuccess)
-                        return fail(VH_E_HIP, "memset failed");
-                    VH_TRY(vhk_moe_combine(st, part, yh, m->pwts, Sn, H2, nslab, hslab, nslab_dev), "combine");
-                    (void)hipEventRecord(m->ev_c[h], st);
-                    (void)hipStreamWaitEvent(m->cs, m->ev_c[h], 0);
-                    if (m->allreduce(part, (long)Sn * H2, m->cs) != 0) return fail(VH_E_COMM, "all-reduce failed");
-                    (void)hipEventRecord(m->ev_r[h], m->cs);
-                }
-                (void)hipStreamWaitEvent(st, m->ev_r[0], 0);
-                (void)hipStreamWaitEvent(st, m->ev_r[1], 0);
-                VH_TRY(vhk_add_halves(st, m->px, m->ptmp, m->ptmp + (size_t)Sn * H2, Sn, H), "add");
-                moe_done = true;
-            } else {
-                VH_TRY(vhk_gemm_ps(st, d), "down gemm");
-            }
-        }
-        if (moe_done) {
-        } else if (tp) {
-            if (hipMemsetAsync(m->ptmp, 0, (size_t)Sn * H * sizeof(float), st) != hipSuccess)
-                return fail(VH_E_HIP, "memset failed");
-            VH_TRY(vhk_moe_combine(st, m->ptmp, m->py, m->pwts, Sn, H, nslab, slab, nslab_dev), "combine");
-            if (m->allreduce(m->ptmp, (long)Sn * H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
-            VH_TRY(vhk_add(st, m->px, m->ptmp, (long)Sn * H), "add");
-        } else if (fuse_rows && l + 1 < m->c.n_layers) {
-            combine_pending = true;                     // applied by the next layer's attention norm
-            pend_nslab = nslab; pend_nslab_dev = nslab_dev;
         } else {
-            VH_TRY(vhk_moe_combine(st, m->px, m->py, m->pwts, Sn, H, nslab, slab, nslab_dev), "combine");
+            VhGemmArgs g{};
+            g.A = m->pattn; g.lda = KO; g.a_rows = Sn; g.nseg = 1; g.seglen = KO;
+            g.W = w.wo; g.ldw = KO; g.M = Sn; g.N = H; g.K = KO;
+            if (tp) {
+                rc = reduce_rows(m, st, Sn, overlap, [&](int h, float* part, int ncols) -> int {
+                    g.W = w.wo + (size_t)h * ncols * KO; g.N = ncols; g.C = part; g.ldc = ncols;
+                    VH_TRY(vhk_gemm(st, g), "o gemm");
+                    return VH_OK;
+                });
+                if (rc != VH_OK) return rc;
+            } else {
+                g.C = m->px; g.ldc = H; g.resid = m->px; g.ldr = H;
+                VH_TRY(vhk_gemm(st, g), "o gemm");
+            }
         }
+        // ---- experts
+        const VhRowUpdate ou{m->py, (long)H, m->proj_slab(H), m->pnslab + 2, 1, nullptr};     // the O projection's slabs
+        VH_TRY(vhk_rmsnorm_route(st, m->px, nullptr, m->pxn_hi, m->pxn_lo, w.ffn_norm, Sn, H, m->c.rms_eps, w.wrouter,
+                                 m->E, m->pids, m->pwts, o_pending ? &ou : nullptr), "rmsnorm + route");
+        MoeGemms moe;
+        if ((rc = moe_gemms(m, st, w, Sn, &moe)) != VH_OK) return rc;
+        const bool prof = m->prof_stride < 0 && (l % -m->prof_stride) == 0 && m->prof_used + 2 <= m->prof_ev.size();
+        if (prof) (void)hipEventRecord(m->prof_ev[m->prof_used], st);
+        VH_TRY(vhk_gemm_ps(st, moe.gate_up), "gate/up gemm");
+        if (prof) { (void)hipEventRecord(m->prof_ev[m->prof_used + 1], st); m->prof_used += 2; }
+        if (tp) {
+            rc = reduce_rows(m, st, Sn, overlap,
+                             [&](int h, float* part, int ncols) { return moe_down(m, st, w, moe, Sn, h, ncols, part); });
+            if (rc != VH_OK) return rc;
+        } else {
+            VH_TRY(vhk_gemm_ps(st, moe.down), "down gemm");
+            if (fuse_rows && l + 1 < m->c.n_layers) {
+                combine_pending = true;             // applied by the next layer's attention norm
+                pend_nslab = moe.nslab; pend_nslab_dev = moe.nslab_dev;
+            } else {
+                VH_TRY(vhk_moe_combine(st, m->px, m->py, m->pwts, Sn, H, moe.nslab, m->down_slab(H), moe.nslab_dev), "combine");
+            }
+        }
+        // ---- debug copies (a pending combine: the next layer's attention norm applies it, then copies this layer's rows)
         if (m->route_dbg)
             (void)hipMemcpyAsync(m->route_dbg + (size_t)l * 2 * Sn, m->pids, (size_t)2 * Sn * sizeof(int),
                            hipMemcpyDeviceToDevice, st);
@@ -973,10 +971,7 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, int Sn, int pos0, fl
     }
     // logits of the last position only (the reference computes all S rows and uses the last:
     // vita_mixtral.py:171-172 + HF greedy argmax(logits[:, -1]))
-    {
-        const int rc = head_and_select(m, st, m->px + (size_t)(Sn - 1) * H, nullptr, /*mode=*/0, /*set_pos=*/pos0 + Sn);
-        if (rc != VH_OK) return rc;
-    }
+    if ((rc = head_and_select(m, st, m->px + (size_t)(Sn - 1) * H, nullptr, /*mode=*/0, /*set_pos=*/pos0 + Sn)) != VH_OK) return rc;
     m->host_pos = pos0 + Sn;
     if (logits_out)
         (void)hipMemcpyAsync(logits_out, m->logits, (size_t)m->V * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -993,6 +988,8 @@ static int api_num_cus() {
     }
     return n;
 }
+
+extern "C" {
 
 int vh_encoder_layer(const vh_encoder_layer_args* a, void* stream) {
     if (!a || !a->x || !a->h_in || !a->qkv_w || !a->proj_w || !a->n2_w || !a->fc1_w || !a->fc2_w || !a->qkv || !a->attn ||
@@ -1093,6 +1090,15 @@ int vh_mixtral_prefill(vh_mixtral_t* m, const float* embeds, int Sn, int pos0, f
     return prefill_impl(m, embeds, Sn, pos0, logits_out, hidden_dbg, S(stream));
 }
 
+// Vocab-sharded head: this rank's best per-block candidate (value, index; a 4-float key when sampled) goes into its slot of
+// cand, the all-reduce fills the other world - 1 slots, and the world candidates replace the per-block ones for the select
+static int exchange_candidates(vh_mixtral* m, hipStream_t st, float* blk_val, int* blk_idx, float* cand, int world, int keyed) {
+    VH_TRY(vhk_dec_cand(st, blk_val, blk_idx, m->lm_grid, cand, m->c.tp_rank, world, keyed), "candidates");
+    if (m->allreduce(cand, (keyed ? 4L : 2L) * world, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
+    VH_TRY(vhk_dec_cand_unpack(st, cand, world, blk_val, blk_idx, keyed), "candidates");
+    return VH_OK;
+}
+
 // Final norm + LM head + greedy selection.  Vocab-sharded head: every rank scores its rows, the (max, index) candidates
 // travel through the all-reduce hook, every rank takes the same global argmax; when scores are kept (logit_rows > 1)
 // the full row is assembled by an all-reduce of the zero-filled slices.
@@ -1111,11 +1117,9 @@ static int head_and_select(vh_mixtral* m, hipStream_t st, const float* x_in, con
         VH_TRY(vhk_dec_sample(st, j), "sample");
         nblk = 1;
     } else if (sharded) {
-        const int cw = m->cand_world();
-        VH_TRY(vhk_dec_cand(st, m->blk_val, m->blk_idx, m->lm_grid, m->cand, m->c.tp_rank, cw, keyed), "candidates");
-        if (m->allreduce(m->cand, (keyed ? 4L : 2L) * cw, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
-        VH_TRY(vhk_dec_cand_unpack(st, m->cand, cw, m->blk_val, m->blk_idx, keyed), "candidates");
-        nblk = cw;
+        nblk = m->cand_world();
+        const int rc = exchange_candidates(m, st, m->blk_val, m->blk_idx, m->cand, nblk, keyed);
+        if (rc != VH_OK) return rc;
     }
     VH_TRY(vhk_dec_select(st, m->blk_val, m->blk_idx, nblk, m->embed, m->H, m->V, m->xa, m->counters, m->counters + 1,
                           m->out_tokens, m->c.max_new, mode, set_pos, keyed), "select");
@@ -1363,28 +1367,11 @@ static int decode_iteration(vh_mixtral* m, hipStream_t st, const int* ids, int n
             VH_TRY(vhk_gather_rows(st, m->seq_x, m->seq_batch, n, H, m->px), "gather");
             VH_TRY(vhk_rmsnorm_route(st, m->px, nullptr, m->pxn_hi, m->pxn_lo, w.ffn_norm, n, H, eps, w.wrouter, E, m->pids,
                                      m->pwts), "rmsnorm + route");
-            VH_TRY(vhk_moe_sort(st, m->pids, n, E, m->pgoff, m->pstok, m->psslot), "sort");
-            VhGemmPsArgs g{};
-            g.A_hi = m->pxn_hi; g.A_lo = m->pxn_lo; g.lda = H; g.a_rowidx = m->pstok;
-            g.W = w.w1; g.W_up = w.w3; g.ldw = H; g.w_group_stride = (long)I * H;
-            g.group_off = m->pgoff; g.ngroups = E;
-            g.C_hi = m->ph_hi; g.C_lo = m->ph_lo; g.ldc_split = I; g.M = 2 * n; g.N = I; g.K = H; g.ksplit = 1;
-            VH_TRY(vhk_gemm_ps(st, g), "gate/up gemm");
-            int nslab = vh_tuning()->moe_ksplit;
-            if (nslab == 0) nslab = 1;
-            if (nslab > 4) nslab = 4;
-            if (nslab < -4) nslab = -4;
-            if (nslab > (I >> 6)) nslab = 1;
-            const long slab = (long)2 * m->c.max_prefill * H;
-            VhGemmPsArgs d{};
-            d.A_hi = m->ph_hi; d.A_lo = m->ph_lo; d.lda = I;
-            d.W = w.w2; d.ldw = I; d.w_group_stride = (long)H * I;
-            d.group_off = m->pgoff; d.ngroups = E;
-            d.C = m->py; d.ldc = H; d.c_rowidx = m->psslot; d.M = 2 * n; d.N = H; d.K = I;
-            d.ksplit = nslab; d.c_split_stride = slab; d.nslab_out = m->pnslab;
-            VH_TRY(vhk_gemm_ps(st, d), "down gemm");
-            if (hipMemsetAsync(m->ptmp, 0, (size_t)n * H * sizeof(float), st) != hipSuccess) return fail(VH_E_HIP, "memset failed");
-            VH_TRY(vhk_moe_combine(st, m->ptmp, m->py, m->pwts, n, H, nslab < 0 ? 1 : nslab, slab, nslab < 0 ? m->pnslab : nullptr), "combine");
+            MoeGemms moe;
+            int rc = moe_gemms(m, st, w, n, &moe);
+            if (rc != VH_OK) return rc;
+            VH_TRY(vhk_gemm_ps(st, moe.gate_up), "gate/up gemm");
+            if ((rc = moe_down(m, st, w, moe, n, 0, H, m->ptmp)) != VH_OK) return rc;
             if (tp && m->allreduce(m->ptmp, (long)n * H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
         } else {
             for (int g0 = 0; g0 < n; g0 += VH_BMAX) {
@@ -1434,10 +1421,9 @@ static int decode_iteration(vh_mixtral* m, hipStream_t st, const int* ids, int n
             int nblk = filt[b] ? 1 : m->lm_grid;
             const int keyed = m->seqs[ids[sb]].samp.T > 0.0 ? 1 : 0;
             if (sharded && !filt[b]) {
-                VH_TRY(vhk_dec_cand(st, m->l_blk_val[b], m->l_blk_idx[b], m->lm_grid, m->l_cand[b], m->c.tp_rank, m->c.tp_world, keyed), "candidates");
-                if (m->allreduce(m->l_cand[b], (keyed ? 4L : 2L) * m->c.tp_world, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
-                VH_TRY(vhk_dec_cand_unpack(st, m->l_cand[b], m->c.tp_world, m->l_blk_val[b], m->l_blk_idx[b], keyed), "candidates");
                 nblk = m->c.tp_world;
+                const int rc = exchange_candidates(m, st, m->l_blk_val[b], m->l_blk_idx[b], m->l_cand[b], nblk, keyed);
+                if (rc != VH_OK) return rc;
             }
             VH_TRY(vhk_dec_select(st, m->l_blk_val[b], m->l_blk_idx[b], nblk, m->embed, H, m->V, xa[sb], cnt[sb], cnt[sb] + 1,
                                   m->seq_tokens + (size_t)ids[sb] * (m->c.max_new > 0 ? m->c.max_new : 1), m->c.max_new, 1, 0, keyed), "select");
