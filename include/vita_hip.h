@@ -97,6 +97,11 @@ typedef struct {
 } vh_gemm_ps_args;
 int vh_gemm_ps(const vh_gemm_ps_args* args, void* stream);
 int vh_split_planes(const float* x, long ldx, uint16_t* hi, uint16_t* lo, long ldo, int rows, int cols, void* stream);
+/* vh_gemm_ps on int8 weights: args->W / W_up must be null; W (and W_up: GLU) int8 with args->ldw /
+ * w_group_stride counted in int8 elements; column n of group e is scaled by s[e * s_group_stride + n] (s_up for the up half).
+ * Always the 12-wave specialised kernel. */
+int vh_gemm_ps_i8(const vh_gemm_ps_args* args, const int8_t* W, const float* s, const int8_t* W_up, const float* s_up,
+                  long s_group_stride, void* stream);
 
 /* vh_attention: softmax(scale * Q K^T [+ (Q+v) P^T]) V with causal / pad / chunk masks.
  * Replaces InternAttention._naive_attn (modeling_intern_vit.py:158-177), Whale
@@ -228,6 +233,25 @@ size_t vh_mixtral_workspace_bytes(const vh_mixtral_cfg* cfg);
 vh_mixtral_t* vh_mixtral_create(const vh_mixtral_cfg* cfg, const vh_mixtral_layer* layers, const uint16_t* embed,
                                 const float* final_norm, const uint16_t* lm_head, const float* rope_cos,
                                 const float* rope_sin, void* workspace, size_t workspace_bytes);
+/* int8 experts (vLLM's quantization="experts_int8", the reference's load_8bit): the expert weights of every layer
+ * as int8 with one fp32 scale per output row, s[r] = max_k |w[r,k]| / 127, q = clamp(rint(w / s), -127, 127) (vh_quant_rows_i8);
+ * the engine computes with w' = q s.  w2's scales are over the FULL row of `inter` columns even when a tensor-parallel rank
+ * stores only its column slice of q, so that every TP degree computes the same w'.  Activations stay fp32. */
+typedef struct {
+    const int8_t* w1; const float* s1;   /* [n_experts][inter][hidden] int8, [n_experts][inter] fp32 */
+    const int8_t* w3; const float* s3;   /* [n_experts][inter][hidden] int8, [n_experts][inter] fp32 */
+    const int8_t* w2; const float* s2;   /* [n_experts][hidden][inter] int8 (this rank's columns), [n_experts][hidden] fp32 */
+} vh_mixtral_experts_i8;
+/* vh_mixtral_create with int8 experts: `experts` is a host array of cfg->n_layers entries (copied); layers[l].w1 / w3 / w2 must
+ * be null.  NULL (vh_last_error says why; VH_E_ARG) for a null array, a non-null bf16 expert pointer or a null int8 weight or
+ * scale.  The workspace is vh_mixtral_workspace_bytes(cfg), as for the bf16 engine. */
+vh_mixtral_t* vh_mixtral_create_i8(const vh_mixtral_cfg* cfg, const vh_mixtral_layer* layers, const vh_mixtral_experts_i8* experts,
+                                   const uint16_t* embed, const float* final_norm, const uint16_t* lm_head, const float* rope_cos,
+                                   const float* rope_sin, void* workspace, size_t workspace_bytes);
+/* Per-row int8 quantisation (the formula above, IEEE divisions): w bf16 [rows][ld_src] -> s fp32 [rows] over all `cols`, and
+ * q int8 [rows][ld_dst] holding columns [col0, col0 + ncols) (a TP rank's slice of w2 with the full-row scale). */
+int vh_quant_rows_i8(const uint16_t* w, long rows, int cols, long ld_src, int col0, int ncols, int8_t* q, long ld_dst, float* s,
+                     void* stream);
 void vh_mixtral_destroy(vh_mixtral_t* m);
 
 /* Tensor-parallel all-reduce hook (sum, fp32, in place).  Either the built-in RCCL path or a
@@ -332,6 +356,10 @@ int vh_router_top2(const float* x, long ldx, const uint16_t* Wg, int E, int H, i
 int vh_moe_decode(const float* x, const float* delta, const float* norm_w, float eps, const uint16_t* Wg, const uint16_t* W1,
                   const uint16_t* W3, const uint16_t* W2, int E, int I, int H, float* x_out, float* y, int* route, float* hbuf,
                   void* stream);
+/* vh_moe_decode_i8: the same on int8 experts (vh_mixtral_experts_i8 layout; s1, s3 [E][I], s2 [E][H]); the router stays bf16. */
+int vh_moe_decode_i8(const float* x, const float* delta, const float* norm_w, float eps, const uint16_t* Wg, const int8_t* W1,
+                     const float* s1, const int8_t* W3, const float* s3, const int8_t* W2, const float* s2, int E, int I, int H,
+                     float* x_out, float* y, int* route, float* hbuf, void* stream);
 /* vh_rope_kv_append (K22): rotate-half RoPE on the q and k heads of S fused-QKV rows and append k, v to the cache at
  *   positions [pos0, pos0 + S) (HF apply_rotary_pos_emb + Cache.update; vLLM rotary_emb + KV write, mixtral.py:477-501).
  *   qkv fp32 [S][ldqkv] = q heads | k heads | v heads (head_dim 128); q_out fp32 [S][nq*128]; caches fp32

@@ -112,6 +112,10 @@ class MixtralLayer(C.Structure):
     ]
 
 
+class MixtralExpertsI8(C.Structure):
+    _fields_ = [("w1", c_void_p), ("s1", c_void_p), ("w3", c_void_p), ("s3", c_void_p), ("w2", c_void_p), ("s2", c_void_p)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(c_int, c_void_p, c_void_p, c_long, c_void_p)
 
 # every symbol include/vita_hip.h declares: (restype, argtypes)
@@ -122,6 +126,8 @@ SIGNATURES = {
     "vh_gemm": (c_int, [C.POINTER(GemmArgs), c_void_p]),
     "vh_gemm_ln": (c_int, [C.POINTER(GemmArgs), c_void_p, c_void_p, c_float, c_void_p, c_long, c_void_p]),
     "vh_gemm_ps": (c_int, [C.POINTER(GemmPsArgs), c_void_p]),
+    "vh_gemm_ps_i8": (c_int, [C.POINTER(GemmPsArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
+    "vh_quant_rows_i8": (c_int, [c_void_p, c_long, c_int, c_long, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p]),
     "vh_split_planes": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p]),
     "vh_attention": (c_int, [C.POINTER(AttnArgs), c_void_p]),
     "vh_encoder_layer": (c_int, [C.POINTER(EncoderLayerArgs), c_void_p]),
@@ -141,6 +147,8 @@ SIGNATURES = {
     "vh_router_top2": (c_int, [c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vh_moe_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vh_moe_decode_i8": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vh_rope_kv_append": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                   c_int, c_void_p, c_void_p]),
     "vh_attn_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p,
@@ -150,6 +158,8 @@ SIGNATURES = {
     "vh_mixtral_workspace_bytes": (c_size_t, [C.POINTER(MixtralCfg)]),
     "vh_mixtral_create": (c_void_p, [C.POINTER(MixtralCfg), C.POINTER(MixtralLayer), c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_void_p, c_size_t]),
+    "vh_mixtral_create_i8": (c_void_p, [C.POINTER(MixtralCfg), C.POINTER(MixtralLayer), C.POINTER(MixtralExpertsI8), c_void_p,
+                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "vh_mixtral_destroy": (None, [c_void_p]),
     "vh_mixtral_set_allreduce": (c_int, [c_void_p, ALLREDUCE_FN, c_void_p]),
     "vh_rccl_unique_id": (c_int, [c_void_p]),

@@ -176,8 +176,57 @@ def vocab_shard(vocab, rank, world):
     return lo, max(0, min(per, vocab - lo))
 
 
-def pack_mixtral(sd, cfg: VitaConfig, device, rank=0, world=1, shard_vocab=True):
-    """state dict (reference names) -> dict of device tensors in engine layout for this TP rank."""
+EXPERT_MODES = ("bf16", "int8")
+
+
+def quant_rows_i8(w, col0=0, ncols=None, q=None, s=None):
+    """Per-row int8 quantisation of a bf16 device matrix [rows, cols] on the device (vh_quant_rows_i8):
+    s[r] = max |w[r, :]| / 127 over ALL cols, q = clamp(rint(w / s), -127, 127) for the columns [col0, col0 + ncols).
+    q (int8 [rows, ncols]) and s (fp32 [rows]) may be given as views to fill."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    if w.dtype != torch.bfloat16 or w.ndim != 2 or w.stride(1) != 1:
+        raise ValueError("quant_rows_i8 wants a 2-D bfloat16 matrix contiguous along its last dimension")
+    rows, cols = w.shape
+    ncols = cols - col0 if ncols is None else ncols
+    if q is None:
+        q = torch.empty(rows, ncols, dtype=torch.int8, device=w.device)
+    if s is None:
+        s = torch.empty(rows, dtype=torch.float32, device=w.device)
+    if q.dtype != torch.int8 or tuple(q.shape) != (rows, ncols) or q.stride(1) != 1 or s.dtype != torch.float32 or not s.is_contiguous():
+        raise ValueError("quant_rows_i8: q must be int8 [rows, ncols] (last dimension contiguous), s fp32 [rows]")
+    _lib.check(_lib.load().vh_quant_rows_i8(C.c_void_p(w.data_ptr()), rows, cols, w.stride(0), int(col0), int(ncols),
+                                            C.c_void_p(q.data_ptr()), q.stride(0), C.c_void_p(s.data_ptr()),
+                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vh_quant_rows_i8")
+    return q, s
+
+
+def _experts_i8(E, I, H, device, fill_w13, fill_w2, ff):
+    """int8 experts of one layer, one expert at a time through a bf16 scratch (peak: the int8 model + one bf16 expert).
+    fill_w13(e, name, dst [I, H]) and fill_w2(e, dst [H, I_full]) write the bf16 values; w2's scales are over the full row."""
+    import torch
+    i8, f32, bf = torch.int8, torch.float32, torch.bfloat16
+    out = {"w1": torch.empty(E, I, H, dtype=i8, device=device), "s1": torch.empty(E, I, dtype=f32, device=device),
+           "w3": torch.empty(E, I, H, dtype=i8, device=device), "s3": torch.empty(E, I, dtype=f32, device=device),
+           "w2": torch.empty(E, H, I, dtype=i8, device=device), "s2": torch.empty(E, H, dtype=f32, device=device)}
+    for e in range(E):
+        for nm, sn in (("w1", "s1"), ("w3", "s3")):
+            w = fill_w13(e, nm)
+            quant_rows_i8(w, q=out[nm][e], s=out[sn][e])
+        w2 = fill_w2(e)
+        quant_rows_i8(w2, col0=ff.start, ncols=I, q=out["w2"][e], s=out["s2"][e])
+    return out
+
+
+def pack_mixtral(sd, cfg: VitaConfig, device, rank=0, world=1, shard_vocab=True, experts="bf16"):
+    """state dict (reference names) -> dict of device tensors in engine layout for this TP rank.
+    experts="int8": w1 / w3 / w2 become int8 with per-row fp32 scales s1 / s3 / s2, quantised on the device one
+    expert at a time; everything else is packed as for "bf16"."""
+    if experts not in EXPERT_MODES:
+        raise ValueError(f"experts must be one of {EXPERT_MODES}, got {experts!r}")
     import torch
     t = cfg.text
     qs, kvs, ff = tp_slices(t, rank, world)
@@ -186,7 +235,7 @@ def pack_mixtral(sd, cfg: VitaConfig, device, rank=0, world=1, shard_vocab=True)
     lo, n = vocab_shard(t.vocab_size, rank, world if shard_vocab else 1)
     out = {"embed": _t(g("model.embed_tokens.weight"), device, bf),
            "final_norm": _t(g("model.norm.weight"), device, f32),
-           "lm_head": _t(g("lm_head.weight")[lo:lo + n], device, bf), "layers": []}
+           "lm_head": _t(g("lm_head.weight")[lo:lo + n], device, bf), "layers": [], "experts": experts}
     if world > 1 and shard_vocab:
         out["vocab_lo"], out["vocab_n"] = lo, n
     for l in range(t.num_hidden_layers):
@@ -202,10 +251,17 @@ def pack_mixtral(sd, cfg: VitaConfig, device, rank=0, world=1, shard_vocab=True)
             "wo": _t(g(p + "self_attn.o_proj.weight")[:, qs], device, bf),
             "ffn_norm": _t(g(p + "post_attention_layernorm.weight"), device, f32),
             "wrouter": _t(g(p + "block_sparse_moe.gate.weight"), device, bf),
-            "w1": _t(stack([w[ff] for w in ex("w1")], 0), device, bf),
-            "w3": _t(stack([w[ff] for w in ex("w3")], 0), device, bf),
-            "w2": _t(stack([w[:, ff] for w in ex("w2")], 0), device, bf),
         }
+        if experts == "int8":
+            ew = lambda e, nm: g(p + f"block_sparse_moe.experts.{e}.{nm}.weight")
+            layer.update(_experts_i8(t.num_local_experts, ff.stop - ff.start, t.hidden_size, device,
+                                     lambda e, nm: _t(ew(e, nm)[ff], device, bf), lambda e: _t(ew(e, "w2"), device, bf), ff))
+        else:
+            layer.update({
+                "w1": _t(stack([w[ff] for w in ex("w1")], 0), device, bf),
+                "w3": _t(stack([w[ff] for w in ex("w3")], 0), device, bf),
+                "w2": _t(stack([w[:, ff] for w in ex("w2")], 0), device, bf),
+            })
         out["layers"].append(layer)
     return out
 
@@ -236,13 +292,17 @@ def hash_fill(dst, name, seed=0, ld_src=None, idx0=0):
     return dst
 
 
-def synth_mixtral_device(cfg: VitaConfig, device, seed=0, rank=0, world=1, shard_vocab=True):
+def synth_mixtral_device(cfg: VitaConfig, device, seed=0, rank=0, world=1, shard_vocab=True, experts="bf16"):
     """Random-init backbone generated directly on the GPU in packed layout (the full model is 93.7 GB bf16, too
     large to stage through host numpy).  SURVEY §8(d) init (sigma ~0.02, norms 1) from the counter-based generator
     vh_fill_hash_bf16, keyed by the REFERENCE'S parameter names: a tensor-parallel rank's shard holds exactly the
     values of its slice of the full tensor, and the CPU oracle regenerates any tensor on the host
-    (oracle/hashw.py) — the released geometry can be parity-checked without a checkpoint."""
+    (oracle/hashw.py) — the released geometry can be parity-checked without a checkpoint.
+    experts="int8": the experts are generated one at a time into a bf16 scratch and quantised (pack_mixtral); a w2 shard's
+    scratch holds the expert's full [H, I] so that its scales are over full rows."""
     import torch
+    if experts not in EXPERT_MODES:
+        raise ValueError(f"experts must be one of {EXPERT_MODES}, got {experts!r}")
     t = cfg.text
     qs, kvs, ff = tp_slices(t, rank, world)
     nq = (qs.stop - qs.start) // t.head_dim
@@ -254,7 +314,15 @@ def synth_mixtral_device(cfg: VitaConfig, device, seed=0, rank=0, world=1, shard
     new = lambda *shape: torch.empty(shape, device=device, dtype=bf)
     lo, nv = vocab_shard(t.vocab_size, rank, world if shard_vocab else 1)
     out = {"embed": hash_fill(new(t.vocab_size, H), "model.embed_tokens.weight", seed), "final_norm": ones(H),
-           "lm_head": hash_fill(new(nv, H), "lm_head.weight", seed, idx0=lo * H), "layers": []}
+           "lm_head": hash_fill(new(nv, H), "lm_head.weight", seed, idx0=lo * H), "layers": [], "experts": experts}
+    if experts == "int8":
+        s13, s2 = new(I, H), new(H, t.intermediate_size)      # one bf16 expert of scratch
+
+        def hashed_experts(prefix):
+            """the fill callables of _experts_i8 for the layer whose parameter names start with `prefix`"""
+            f13 = lambda e, nm: hash_fill(s13, prefix + f"block_sparse_moe.experts.{e}.{nm}.weight", seed, idx0=ff.start * H)
+            f2 = lambda e: hash_fill(s2, prefix + f"block_sparse_moe.experts.{e}.w2.weight", seed)
+            return f13, f2
     if world > 1 and shard_vocab:
         out["vocab_lo"], out["vocab_n"] = lo, nv
     for l in range(t.num_hidden_layers):
@@ -265,13 +333,17 @@ def synth_mixtral_device(cfg: VitaConfig, device, seed=0, rank=0, world=1, shard
         hash_fill(wqkv[(nq + nkv) * hd:], p + "self_attn.v_proj.weight", seed, idx0=kvs.start * H)
         wo = hash_fill(new(H, nq * hd), p + "self_attn.o_proj.weight", seed, ld_src=t.num_attention_heads * hd,
                        idx0=qs.start)
-        w1, w3, w2 = new(E, I, H), new(E, I, H), new(E, H, I)
-        for e in range(E):
-            q = p + f"block_sparse_moe.experts.{e}."
-            hash_fill(w1[e], q + "w1.weight", seed, idx0=ff.start * H)
-            hash_fill(w3[e], q + "w3.weight", seed, idx0=ff.start * H)
-            hash_fill(w2[e], q + "w2.weight", seed, ld_src=t.intermediate_size, idx0=ff.start)
+        if experts == "int8":
+            ex = _experts_i8(E, I, H, device, *hashed_experts(p), ff)
+        else:
+            w1, w3, w2 = new(E, I, H), new(E, I, H), new(E, H, I)
+            for e in range(E):
+                q = p + f"block_sparse_moe.experts.{e}."
+                hash_fill(w1[e], q + "w1.weight", seed, idx0=ff.start * H)
+                hash_fill(w3[e], q + "w3.weight", seed, idx0=ff.start * H)
+                hash_fill(w2[e], q + "w2.weight", seed, ld_src=t.intermediate_size, idx0=ff.start)
+            ex = {"w1": w1, "w3": w3, "w2": w2}
         out["layers"].append({
             "attn_norm": ones(H), "wqkv": wqkv, "wo": wo, "ffn_norm": ones(H),
-            "wrouter": hash_fill(new(E, H), p + "block_sparse_moe.gate.weight", seed), "w1": w1, "w3": w3, "w2": w2})
+            "wrouter": hash_fill(new(E, H), p + "block_sparse_moe.gate.weight", seed), **ex})
     return out

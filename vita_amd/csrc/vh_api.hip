@@ -105,6 +105,27 @@ int vh_gemm_ps(const vh_gemm_ps_args* a, void* stream) {
         return fail(VH_E_SHAPE, "vh_gemm_ps: activation plane above the 32-bit offset range");
     return check_launch("vh_gemm_ps", vhk_gemm_ps(S(stream), g));
 }
+int vh_gemm_ps_i8(const vh_gemm_ps_args* a, const int8_t* W, const float* s, const int8_t* W_up, const float* s_up,
+                  long s_group_stride, void* stream) {
+    if (!a || !a->A_hi || !a->A_lo || !W || !s || (W_up != nullptr) != (s_up != nullptr)) return fail(VH_E_ARG, "vh_gemm_ps_i8: null pointer");
+    if (a->W || a->W_up) return fail(VH_E_ARG, "vh_gemm_ps_i8: args->W / W_up must be null (the weights are the int8 arguments)");
+    VhGemmPsArgs g{};
+    g.A_hi = a->A_hi; g.A_lo = a->A_lo; g.lda = a->lda; g.a_rowidx = a->a_rowidx;
+    g.ldw = a->ldw; g.w_group_stride = a->w_group_stride;
+    g.group_off = a->group_off; g.ngroups = a->ngroups;
+    g.C = a->C; g.ldc = a->ldc; g.C_hi = a->C_hi; g.C_lo = a->C_lo; g.ldc_split = a->ldc_split;
+    g.c_rowidx = a->c_rowidx; g.bias = a->bias; g.scale = a->scale; g.resid = a->resid; g.ldr = a->ldr;
+    g.M = a->M; g.N = a->N; g.K = a->K; g.act = a->act;
+    g.ksplit = a->ksplit; g.c_split_stride = a->c_split_stride; g.nslab_out = a->nslab_out;
+    if ((size_t)a->lda * 2 * (size_t)(a->M > 0 ? a->M : 1) >= (1ull << 32))
+        return fail(VH_E_SHAPE, "vh_gemm_ps_i8: activation plane above the 32-bit offset range");
+    return check_launch("vh_gemm_ps_i8", vhk_gemm_ps_i8(S(stream), g, VhPsI8{W, W_up, s, s_up, s_group_stride}));
+}
+int vh_quant_rows_i8(const uint16_t* w, long rows, int cols, long ld_src, int col0, int ncols, int8_t* q, long ld_dst, float* s,
+                     void* stream) {
+    if (!w || !q || !s) return fail(VH_E_ARG, "vh_quant_rows_i8: null pointer");
+    return check_launch("vh_quant_rows_i8", vhk_quant_rows_i8(S(stream), w, rows, cols, ld_src, col0, ncols, q, ld_dst, s));
+}
 int vh_split_planes(const float* x, long ldx, uint16_t* hi, uint16_t* lo, long ldo, int rows, int cols, void* stream) {
     if (!x || !hi || !lo) return fail(VH_E_ARG, "vh_split_planes: null pointer");
     return check_launch("vh_split_planes", vhk_split_planes(S(stream), x, ldx, hi, lo, ldo, rows, cols));
@@ -210,6 +231,17 @@ int vh_moe_decode(const float* x, const float* delta, const float* norm_w, float
     if (rc != VH_OK) return rc;
     return check_launch("vh_moe_decode (down)", vhk_dec_down(S(stream), hbuf, route, W2, H, I, y));
 }
+int vh_moe_decode_i8(const float* x, const float* delta, const float* norm_w, float eps, const uint16_t* Wg, const int8_t* W1,
+                     const float* s1, const int8_t* W3, const float* s3, const int8_t* W2, const float* s2, int E, int I, int H,
+                     float* x_out, float* y, int* route, float* hbuf, void* stream) {
+    if (!x || !norm_w || !Wg || !W1 || !s1 || !W3 || !s3 || !W2 || !s2 || !y || !route || !hbuf)
+        return fail(VH_E_ARG, "vh_moe_decode_i8: null pointer");
+    if (H % 64 || I % 64 || H > 14336 || I > 14336) return fail(VH_E_SHAPE, "vh_moe_decode_i8: H, I must be multiples of 64 and <= 14336");
+    int rc = check_launch("vh_moe_decode_i8 (gate|up)", vhk_dec_gateup_i8(S(stream), x, delta, x_out, norm_w, eps, Wg, E, W1, s1, W3, s3,
+                                                                          I, H, route, hbuf, 0));
+    if (rc != VH_OK) return rc;
+    return check_launch("vh_moe_decode_i8 (down)", vhk_dec_down_i8(S(stream), hbuf, route, W2, s2, H, I, H, y));
+}
 
 int vh_rope_kv_append(const float* qkv, long ldqkv, float* q_out, float* kcache, float* vcache, const float* rope_cos,
                       const float* rope_sin, int Sn, int pos0, int nq, int nkv, int max_ctx, const int* table, void* stream) {
@@ -300,6 +332,7 @@ struct Carver {
 struct vh_mixtral {
     vh_mixtral_cfg c;
     std::vector<vh_mixtral_layer> L;
+    std::vector<vh_mixtral_experts_i8> Q;   // int8 experts (vh_mixtral_create_i8): one entry per layer; empty = bf16
     const uint16_t* embed; const float* final_norm; const uint16_t* lm_head;
     const float* rope_cos; const float* rope_sin;
     int nq, nkv, hd, H, I, E, V, nqkv, max_splits, lm_grid;
@@ -572,6 +605,31 @@ vh_mixtral_t* vh_mixtral_create(const vh_mixtral_cfg* cfg, const vh_mixtral_laye
     return m;
 }
 
+vh_mixtral_t* vh_mixtral_create_i8(const vh_mixtral_cfg* cfg, const vh_mixtral_layer* layers, const vh_mixtral_experts_i8* experts,
+                                   const uint16_t* embed, const float* final_norm, const uint16_t* lm_head, const float* rope_cos,
+                                   const float* rope_sin, void* workspace, size_t workspace_bytes) {
+    if (cfg_ok(cfg) != VH_OK) return nullptr;
+    if (!layers || !experts) {
+        fail(VH_E_ARG, "vh_mixtral_create_i8: null layers / experts");
+        return nullptr;
+    }
+    for (int l = 0; l < cfg->n_layers; ++l) {
+        const vh_mixtral_layer& w = layers[l];
+        const vh_mixtral_experts_i8& q = experts[l];
+        if (w.w1 || w.w3 || w.w2) {
+            fail(VH_E_ARG, "vh_mixtral_create_i8: layers[%d].w1 / w3 / w2 must be null (the experts are int8)", l);
+            return nullptr;
+        }
+        if (!q.w1 || !q.s1 || !q.w3 || !q.s3 || !q.w2 || !q.s2) {
+            fail(VH_E_ARG, "vh_mixtral_create_i8: null int8 weight or scale in experts[%d]", l);
+            return nullptr;
+        }
+    }
+    vh_mixtral_t* m = vh_mixtral_create(cfg, layers, embed, final_norm, lm_head, rope_cos, rope_sin, workspace, workspace_bytes);
+    if (m) m->Q.assign(experts, experts + cfg->n_layers);
+    return m;
+}
+
 void vh_mixtral_destroy(vh_mixtral_t* m) {
     if (!m) return;
     for (hipEvent_t e : m->prof_ev) (void)hipEventDestroy(e);
@@ -765,7 +823,8 @@ static int reduce_rows(vh_mixtral* m, hipStream_t st, int Sn, bool overlap, Prod
 // left: the rows are sorted by expert, gate|up runs one tall m-tile per expert (weights cross the fabric once) and emits the
 // planes of h (ph_hi / lo), the down projection is K-split into `nslab` partial slabs of py that the combine adds.
 struct MoeGemms {
-    VhGemmPsArgs gate_up, down;   // launched by the caller (down: all H columns)
+    VhGemmPsArgs gate_up, down;   // launched by the caller (down: all H columns) through moe_gate_up / moe_down
+    const vh_mixtral_experts_i8* q; // int8 experts of the layer (null: bf16): the same arguments with W / W_up null
     int nslab;                    // slabs the combine adds (1 when the kernel picks the split ...
     const int* nslab_dev;         // ... and reports it here; null otherwise)
 };
@@ -773,6 +832,7 @@ static int moe_gemms(vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, i
     const int H = m->H, I = m->I, E = m->E;
     VH_TRY(vhk_moe_sort(st, m->pids, n, E, m->pgoff, m->pstok, m->psslot), "sort");
     *p = MoeGemms{};
+    p->q = m->Q.empty() ? nullptr : &m->Q[&w - m->L.data()];
     VhGemmPsArgs &g = p->gate_up, &d = p->down;
     g.A_hi = m->pxn_hi; g.A_lo = m->pxn_lo; g.lda = H; g.a_rowidx = m->pstok;
     g.W = w.w1; g.W_up = w.w3; g.ldw = H; g.w_group_stride = (long)I * H;
@@ -792,13 +852,27 @@ static int moe_gemms(vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, i
     p->nslab_dev = ks < 0 ? m->pnslab : nullptr;
     return VH_OK;
 }
+// int8 experts: the specialised streaming GEMM with the int8 stagers (vhk_gemm_ps_i8), the same arguments with W / W_up null
+static int moe_gate_up(hipStream_t st, const MoeGemms& p) {
+    if (!p.q) return vhk_gemm_ps(st, p.gate_up);
+    VhGemmPsArgs g = p.gate_up;
+    g.W = nullptr; g.W_up = nullptr;
+    return vhk_gemm_ps_i8(st, g, VhPsI8{p.q->w1, p.q->w3, p.q->s1, p.q->s3, (long)g.N});
+}
+// down projection of output columns [c0, c0 + d.N) (d: p.down with N / C narrowed by the caller)
+static int moe_down_gemm(hipStream_t st, const MoeGemms& p, const VhGemmPsArgs& d, int c0, int H) {
+    if (!p.q) return vhk_gemm_ps(st, d);
+    VhGemmPsArgs a = d;
+    a.W = nullptr;
+    return vhk_gemm_ps_i8(st, a, VhPsI8{p.q->w2 + (size_t)c0 * a.ldw, nullptr, p.q->s2 + c0, nullptr, (long)H});
+}
 // the down projection of output columns [h * ncols, (h + 1) * ncols) into the slabs from py_half(h), then their
 // routing-weighted sum into part ([n][ncols], zeroed first)
 static int moe_down(vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, const MoeGemms& p, int n, int h, int ncols,
                     float* part) {
     VhGemmPsArgs d = p.down;
-    d.W = w.w2 + (size_t)h * ncols * m->I; d.N = ncols; d.C = m->py_half(h); d.ldc = ncols; d.c_split_stride = m->down_slab(ncols);
-    VH_TRY(vhk_gemm_ps(st, d), "down gemm");
+    d.W = w.w2 ? w.w2 + (size_t)h * ncols * m->I : nullptr; d.N = ncols; d.C = m->py_half(h); d.ldc = ncols; d.c_split_stride = m->down_slab(ncols);
+    VH_TRY(moe_down_gemm(st, p, d, h * ncols, m->H), "down gemm");
     if (hipMemsetAsync(part, 0, (size_t)n * ncols * sizeof(float), st) != hipSuccess) return fail(VH_E_HIP, "memset failed");
     VH_TRY(vhk_moe_combine(st, part, d.C, m->pwts, n, ncols, p.nslab, d.c_split_stride, p.nslab_dev), "combine");
     return VH_OK;
@@ -946,14 +1020,14 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, int Sn, int pos0, fl
         if ((rc = moe_gemms(m, st, w, Sn, &moe)) != VH_OK) return rc;
         const bool prof = m->prof_stride < 0 && (l % -m->prof_stride) == 0 && m->prof_used + 2 <= m->prof_ev.size();
         if (prof) (void)hipEventRecord(m->prof_ev[m->prof_used], st);
-        VH_TRY(vhk_gemm_ps(st, moe.gate_up), "gate/up gemm");
+        VH_TRY(moe_gate_up(st, moe), "gate/up gemm");
         if (prof) { (void)hipEventRecord(m->prof_ev[m->prof_used + 1], st); m->prof_used += 2; }
         if (tp) {
             rc = reduce_rows(m, st, Sn, overlap,
                              [&](int h, float* part, int ncols) { return moe_down(m, st, w, moe, Sn, h, ncols, part); });
             if (rc != VH_OK) return rc;
         } else {
-            VH_TRY(vhk_gemm_ps(st, moe.down), "down gemm");
+            VH_TRY(moe_down_gemm(st, moe, moe.down, 0, H), "down gemm");
             if (fuse_rows && l + 1 < m->c.n_layers) {
                 combine_pending = true;             // applied by the next layer's attention norm
                 pend_nslab = moe.nslab; pend_nslab_dev = moe.nslab_dev;
@@ -1165,10 +1239,11 @@ static int decode_one_step(vh_mixtral* m, hipStream_t st) {
     bool have_xm = false;
     for (int l = 0; l < m->c.n_layers; ++l) {
         const vh_mixtral_layer& w = m->L[l];
+        const vh_mixtral_experts_i8* q8 = m->Q.empty() ? nullptr : &m->Q[l];
         float* kc = m->kcache + (size_t)l * nkv * m->c.max_ctx * hd;
         float* vc = m->vcache + (size_t)l * nkv * m->c.max_ctx * hd;
         const bool prof = m->prof_stride > 0 && (l % m->prof_stride) == 0 && m->prof_used + 2 <= m->prof_ev.size();
-        if (fuse && vh_comm_xchg_next(m->comm, H, 0, vhk_dec_consumer_blocks(1, 0, H, I), &xa, st) != VH_OK)
+        if (fuse && vh_comm_xchg_next(m->comm, H, 0, vhk_dec_consumer_blocks(q8 ? 4 : 1, 0, H, I), &xa, st) != VH_OK)
             return fail(VH_E_COMM, "fused exchange failed: %s", vh_comm_last_error());
         if (fused_attn) {
             VhDecAblk a{};
@@ -1196,14 +1271,23 @@ static int decode_one_step(vh_mixtral* m, hipStream_t st) {
                                                      : m->lm_grid;
         if (prof) (void)hipEventRecord(m->prof_ev[m->prof_used], st);
         {
-            VH_TRY(vhk_dec_gateup(st, m->xb, m->delta_attn, m->xa, w.ffn_norm, eps, w.wrouter, E, w.w1, w.w3, I, H,
-                                  m->route, m->hbuf, 0, fuse ? &xa : nullptr), "dec gateup");
+            if (q8) {
+                VH_TRY(vhk_dec_gateup_i8(st, m->xb, m->delta_attn, m->xa, w.ffn_norm, eps, w.wrouter, E, q8->w1, q8->s1, q8->w3, q8->s3,
+                                         I, H, m->route, m->hbuf, 0, fuse ? &xa : nullptr), "dec gateup");
+            } else {
+                VH_TRY(vhk_dec_gateup(st, m->xb, m->delta_attn, m->xa, w.ffn_norm, eps, w.wrouter, E, w.w1, w.w3, I, H,
+                                      m->route, m->hbuf, 0, fuse ? &xa : nullptr), "dec gateup");
+            }
             if (prof) { (void)hipEventRecord(m->prof_ev[m->prof_used + 1], st); m->prof_used += 2; }
             if (fuse) {
                 if (vh_comm_xchg_next(m->comm, H, 1, xm_blocks, &xm, st) != VH_OK) return fail(VH_E_COMM, "fused exchange failed: %s", vh_comm_last_error());
                 have_xm = true;
             }
-            VH_TRY(vhk_dec_down(st, m->hbuf, m->route, w.w2, H, I, m->delta_moe, fuse ? &xm : nullptr), "dec down");
+            if (q8) {
+                VH_TRY(vhk_dec_down_i8(st, m->hbuf, m->route, q8->w2, q8->s2, H, I, H, m->delta_moe, fuse ? &xm : nullptr), "dec down");
+            } else {
+                VH_TRY(vhk_dec_down(st, m->hbuf, m->route, w.w2, H, I, m->delta_moe, fuse ? &xm : nullptr), "dec down");
+            }
         }
         if (!fuse && m->allreduce(m->delta_moe, H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
     }
@@ -1339,6 +1423,7 @@ static int decode_iteration(vh_mixtral* m, hipStream_t st, const int* ids, int n
     }
     for (int l = 0; l < m->c.n_layers; ++l) {
         const vh_mixtral_layer& w = m->L[l];
+        const vh_mixtral_experts_i8* q8 = m->Q.empty() ? nullptr : &m->Q[l];
         float* kc = m->kcache + (size_t)l * nkv * m->c.max_ctx * hd;
         float* vc = m->vcache + (size_t)l * nkv * m->c.max_ctx * hd;
         for (int g0 = 0; g0 < n; g0 += VH_BMAX) {
@@ -1370,13 +1455,19 @@ static int decode_iteration(vh_mixtral* m, hipStream_t st, const int* ids, int n
             MoeGemms moe;
             int rc = moe_gemms(m, st, w, n, &moe);
             if (rc != VH_OK) return rc;
-            VH_TRY(vhk_gemm_ps(st, moe.gate_up), "gate/up gemm");
+            VH_TRY(moe_gate_up(st, moe), "gate/up gemm");
             if ((rc = moe_down(m, st, w, moe, n, 0, H, m->ptmp)) != VH_OK) return rc;
             if (tp && m->allreduce(m->ptmp, (long)n * H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
         } else {
             for (int g0 = 0; g0 < n; g0 += VH_BMAX) {
                 const int gn = n - g0 < VH_BMAX ? n - g0 : VH_BMAX;
                     for (int b = 0; b < gn; ++b) {
+                        if (q8) {
+                            VH_TRY(vhk_dec_gateup_i8(st, xb[g0 + b], da[g0 + b], xa[g0 + b], w.ffn_norm, eps, w.wrouter, E, q8->w1, q8->s1,
+                                                     q8->w3, q8->s3, I, H, m->l_route[b], m->l_hbuf[b], 0), "dec gateup");
+                            VH_TRY(vhk_dec_down_i8(st, m->l_hbuf[b], m->l_route[b], q8->w2, q8->s2, H, I, H, dm[g0 + b]), "dec down");
+                            continue;
+                        }
                         VH_TRY(vhk_dec_gateup(st, xb[g0 + b], da[g0 + b], xa[g0 + b], w.ffn_norm, eps, w.wrouter, E, w.w1, w.w3, I, H,
                                               m->l_route[b], m->l_hbuf[b], 0), "dec gateup");
                         VH_TRY(vhk_dec_down(st, m->l_hbuf[b], m->l_route[b], w.w2, H, I, dm[g0 + b]), "dec down");

@@ -653,6 +653,45 @@ __global__ __launch_bounds__(256, 4) void k_dec_ablk(const VhDecAblk a) {
 // loops over 2*RP-row groups (RP gate + RP up rows of one expert) and relies on the co-resident
 // blocks of its CU for the overlap of one block's reduction with another's loads (a second register
 // buffer per block measured slower, 91 vs 84 us: it costs two waves per SIMD of occupancy; r01, git history).
+// x = x_in + delta, RMSNorm (its factor `inv` deferred), router logits (bf16 Wg), softmax, top-2 with renormalised weights:
+// every gate|up block (bf16 and int8 experts alike) runs this prologue; block bi == 0 stores x_out and route_out.
+template <int NJ>
+__device__ __forceinline__ void dec_route(const int bi, const float* __restrict__ x_in, const float* __restrict__ delta,
+                                          float* __restrict__ x_out, const float* __restrict__ norm_w, float eps,
+                                          const uint16_t* __restrict__ Wg, int E, int K, int* __restrict__ route_out,
+                                          const VhXchg& cx, float* red, float (&xr)[NJ][8], float& inv, int& e0, int& e1) {
+    const uint16_t* rrows[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) rrows[e] = Wg + (size_t)min(e, E - 1) * K;
+    uint4 wr[8][NJ];
+    gemv_issue<NJ, 8>(rrows, K, wr);
+    float vals[9];
+    vals[8] = load_add_norm<NJ>(x_in, delta, norm_w, bi == 0 ? x_out : nullptr, K, xr, &cx, /*store_block=*/true);
+    float lg[8];
+    gemv_fma<NJ, 8>(wr, xr, lg);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) vals[e] = lg[e];
+    block256_sum<9>(vals, red);
+    inv = rsqrtf(vals[8] / (float)K + eps);
+    float mx = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { vals[e] *= inv; if (e < E) mx = fmaxf(mx, vals[e]); }
+    float pr[8], sum = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { pr[e] = (e < E) ? expf(vals[e] - mx) : 0.f; sum += pr[e]; }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) pr[e] = pr[e] / sum;
+    float b0 = -1.f, b1 = -1.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) if (e < E && pr[e] > b0) { b0 = pr[e]; e0 = e; }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) if (e < E && e != e0 && pr[e] > b1) { b1 = pr[e]; e1 = e; }
+    if (bi == 0 && threadIdx.x == 0) {
+        const float t = b0 + b1;
+        route_out[0] = e0; route_out[1] = e1;
+        route_out[2] = __float_as_int(b0 / t); route_out[3] = __float_as_int(b1 / t);
+    }
+}
 template <int NJ, int RP>
 __device__ __forceinline__ void dec_gateup_body(const int bi, const int gn, const float* __restrict__ x_in,
                                                 const float* __restrict__ delta, float* __restrict__ x_out,
@@ -662,39 +701,7 @@ __device__ __forceinline__ void dec_gateup_body(const int bi, const int gn, cons
     float xr[NJ][8];
     float inv;
     int e0 = 0, e1 = 0;
-    {
-        const uint16_t* rrows[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) rrows[e] = Wg + (size_t)min(e, E - 1) * K;
-        uint4 wr[8][NJ];
-        gemv_issue<NJ, 8>(rrows, K, wr);
-        float vals[9];
-        vals[8] = load_add_norm<NJ>(x_in, delta, norm_w, bi == 0 ? x_out : nullptr, K, xr, &cx, /*store_block=*/true);
-        float lg[8];
-        gemv_fma<NJ, 8>(wr, xr, lg);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) vals[e] = lg[e];
-        block256_sum<9>(vals, red);
-        inv = rsqrtf(vals[8] / (float)K + eps);
-        float mx = -INFINITY;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { vals[e] *= inv; if (e < E) mx = fmaxf(mx, vals[e]); }
-        float pr[8], sum = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { pr[e] = (e < E) ? expf(vals[e] - mx) : 0.f; sum += pr[e]; }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) pr[e] = pr[e] / sum;
-        float b0 = -1.f, b1 = -1.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) if (e < E && pr[e] > b0) { b0 = pr[e]; e0 = e; }
-#pragma unroll
-        for (int e = 0; e < 8; ++e) if (e < E && e != e0 && pr[e] > b1) { b1 = pr[e]; e1 = e; }
-        if (bi == 0 && threadIdx.x == 0) {
-            const float t = b0 + b1;
-            route_out[0] = e0; route_out[1] = e1;
-            route_out[2] = __float_as_int(b0 / t); route_out[3] = __float_as_int(b1 / t);
-        }
-    }
+    dec_route<NJ>(bi, x_in, delta, x_out, norm_w, eps, Wg, E, K, route_out, cx, red, xr, inv, e0, e1);
 
     const int per_slot = I / RP;
     const int n_iter = 2 * per_slot;
@@ -785,6 +792,136 @@ __global__ __launch_bounds__(256) void k_dec_down(const float* __restrict__ hbuf
         for (int r = 0; r < R; ++r) if (threadIdx.x == r) v = tot[r];
         if (px.world) xchg_put(px, n0 + threadIdx.x, v);
         else out[n0 + threadIdx.x] = v;
+    }
+}
+
+// ---- int8 experts: the same two launches on int8 weights with one fp32 scale per output row -------------------
+// A thread's chunk c = t + 256 j is now 8 BYTES (8 weights) of a row: the activation register layout xr[NJ][8] and NJ are those
+// of the bf16 kernels.  A load carries half the bytes, so the blocks take twice the rows (gate|up 8 + 8, down 4 per expert):
+// the same bytes and the same weight registers in flight per thread as the bf16 forms.  Row r's dot product is
+// (sum_k x_k q_k) * s[r] in fp32; q -> fp32 is exact (|q| <= 127).
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+template <int NJ, int R>
+__device__ __forceinline__ void gemv_issue_i8(const int8_t* const (&rows)[R], int K, uint2 (&w)[R][NJ]) {
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int c = threadIdx.x + j * 256;
+            if (c * 8 < K) {
+                const u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(rows[r] + (size_t)c * 8));
+                w[r][j] = make_uint2(v.x, v.y);
+            } else {
+                w[r][j] = make_uint2(0, 0);
+            }
+        }
+}
+__device__ __forceinline__ float dot8_i8_f32(const uint2& w, const float* x) {
+    float a = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a = fmaf((float)((int)(w.x << (24 - 8 * i)) >> 24), x[i], a);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a = fmaf((float)((int)(w.y << (24 - 8 * i)) >> 24), x[4 + i], a);
+    return a;
+}
+template <int NJ, int R>
+__device__ __forceinline__ void gemv_fma_i8(const uint2 (&w)[R][NJ], const float (&xr)[NJ][8], float (&acc)[R]) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        float a = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) a += dot8_i8_f32(w[r][j], xr[j]);
+        acc[r] = a;
+    }
+}
+
+// router (bf16, as k_dec_gateup) + gate|up of the two chosen experts in groups of RP gate + RP up rows:
+// h = silu(g inv s1) * (u inv s3), inv the deferred RMSNorm factor
+template <int NJ, int RP>
+__global__ __launch_bounds__(256) void k_dec_gateup_i8(const float* __restrict__ x_in, const float* __restrict__ delta,
+                                                       float* __restrict__ x_out, const float* __restrict__ norm_w,
+                                                       float eps, const uint16_t* __restrict__ Wg, int E,
+                                                       const int8_t* __restrict__ W1, const float* __restrict__ s1,
+                                                       const int8_t* __restrict__ W3, const float* __restrict__ s3,
+                                                       int I, int K, int* __restrict__ route_out,
+                                                       float* __restrict__ hbuf, const VhXchg cx) {
+    __shared__ float red[4 * (2 * RP > 9 ? 2 * RP : 9)];
+    xchg_reduce(cx);
+    const int bi = blockIdx.x, gn = gridDim.x;
+    float xr[NJ][8];
+    float inv;
+    int e0 = 0, e1 = 0;
+    dec_route<NJ>(bi, x_in, delta, x_out, norm_w, eps, Wg, E, K, route_out, cx, red, xr, inv, e0, e1);
+    const int per_slot = I / RP;
+    const int n_iter = 2 * per_slot;
+    for (int it = bi; it < n_iter; it += gn) {
+        const int slot = it / per_slot;
+        const int i0 = (it - slot * per_slot) * RP;
+        const size_t r0 = (size_t)(slot ? e1 : e0) * I + i0;
+        const int8_t* rows[2 * RP];
+#pragma unroll
+        for (int r = 0; r < RP; ++r) {
+            rows[r] = W1 + (r0 + r) * K;
+            rows[RP + r] = W3 + (r0 + r) * K;
+        }
+        uint2 w[2 * RP][NJ];
+        gemv_issue_i8<NJ, 2 * RP>(rows, K, w);
+        float acc[2 * RP];
+        gemv_fma_i8<NJ, 2 * RP>(w, xr, acc);
+        block256_sum<2 * RP>(acc, red);
+        if (threadIdx.x < RP) {
+            float g = 0.f, u = 0.f;
+#pragma unroll
+            for (int r = 0; r < RP; ++r) if (threadIdx.x == r) { g = acc[r]; u = acc[RP + r]; }
+            const size_t ri = r0 + threadIdx.x;
+            hbuf[(size_t)slot * I + i0 + threadIdx.x] = silu_f(g * inv * s1[ri]) * (u * inv * s3[ri]);
+        }
+    }
+}
+
+// down GEMV of both experts on int8 rows: out[n] = w0 s2[e0][n] (q_e0[n] . h0) + w1 s2[e1][n] (q_e1[n] . h1).  W2 / s2 point at
+// row 0 of this call's rows (a column slice of [Ntot][I]); rstride = Ntot rows per expert
+template <int NJ, int R>
+__global__ __launch_bounds__(256) void k_dec_down_i8(const float* __restrict__ hbuf, const int* __restrict__ route,
+                                                     const int8_t* __restrict__ W2, const float* __restrict__ s2, int N, int I,
+                                                     long rstride, float* __restrict__ out, const VhXchg px) {
+    __shared__ float red[4 * 2 * R];             // block256_sum<2 R>: the two experts' row sums stay apart (one scale each)
+    const int e0 = route[0], e1 = route[1];
+    const float w0 = __int_as_float(route[2]), w1 = __int_as_float(route[3]);
+    const int n0 = blockIdx.x * R;
+    const int8_t* rows0[R];
+    const int8_t* rows1[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        rows0[r] = W2 + ((size_t)e0 * rstride + min(n0 + r, N - 1)) * I;
+        rows1[r] = W2 + ((size_t)e1 * rstride + min(n0 + r, N - 1)) * I;
+    }
+    uint2 wa[R][NJ], wb[R][NJ];
+    gemv_issue_i8<NJ, R>(rows0, I, wa);
+    gemv_issue_i8<NJ, R>(rows1, I, wb);
+    float ta[R], tb[R];
+    {
+        float xr[NJ][8];
+        load_x<NJ>(hbuf, I, xr);
+        gemv_fma_i8<NJ, R>(wa, xr, ta);
+    }
+    {
+        float xr[NJ][8];
+        load_x<NJ>(hbuf + (size_t)I, I, xr);
+        gemv_fma_i8<NJ, R>(wb, xr, tb);
+    }
+    float tot[2 * R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) { tot[r] = ta[r]; tot[R + r] = tb[r]; }
+    block256_sum<2 * R>(tot, red);
+    if (threadIdx.x < R && n0 + threadIdx.x < N) {
+        float a = 0.f, b = 0.f;
+#pragma unroll
+        for (int r = 0; r < R; ++r) if (threadIdx.x == r) { a = tot[r]; b = tot[R + r]; }
+        const int n = n0 + threadIdx.x;
+        const float v = fmaf(w1, b * s2[(size_t)e1 * rstride + n], w0 * (a * s2[(size_t)e0 * rstride + n]));
+        if (px.world) xchg_put(px, n, v);
+        else out[n] = v;
     }
 }
 
@@ -1180,8 +1317,9 @@ static int launch_dec_gemv(hipStream_t st, const float* x_in, const float* delta
 constexpr int DEC_GEMV_R = 8;
 // (r06: groups of 7 + 7 rows for tensor-parallel shards — 512 groups = ONE round on 512 blocks at I = 1792 instead of 2-3 rounds of 4 + 4 —
 // measured SLOWER at every degree: one rank's TP = 8 / 4 / 2 shard 1.316 / 1.831 / 2.871 against 1.287 / 1.788 / 2.790 ms per token; removed)
-static int dec_gateup_grid(int I) {
-    constexpr int rp = 4;
+// int8 experts: 8 + 8 rows per gate|up group and 4 rows per expert in the down blocks (the bf16 kernels' bytes in flight)
+constexpr int DEC_I8_RP = 8, DEC_I8_R = 4;
+static int dec_gateup_grid(int I, int rp = 4) {   // rp: gate (= up) rows per group of the kernel (4 bf16, 8 int8)
     // 1.5 persistent blocks per CU: every block pays the router prologue (96 KB of L2 reads), so fewer, longer-lived
     // blocks win — r01: 79 us at 512 blocks vs 83 at 1024 and 82 at 1280; r02 (cheaper block reductions): whole-token rate
     // 196.6 / 205.7 / 210.5 / 207.6 / 207.0 / 208.7 / 207.4 tok/s at 256 / 320 / 384 / 448 / 512 / 768 / 1024 blocks
@@ -1201,6 +1339,7 @@ int vhk_dec_consumer_blocks(int which, int N, int K, int I) {
     (void)K;
     if (which == 0) return (N + DEC_GEMV_R - 1) / DEC_GEMV_R;
     if (which == 1) return dec_gateup_grid(I);
+    if (which == 4) return dec_gateup_grid(I, DEC_I8_RP);   // gate|up on int8 experts
     if (which == 3) return N;   // fused attention block: at least the fused-QKV blocks (N = their count) come first
     return N;   // LM head: the caller's grid
 }
@@ -1285,6 +1424,32 @@ int vhk_dec_down(hipStream_t st, const float* hbuf, const int* route, const uint
     return pick_nj(I, [&](auto nj) {
         hipLaunchKernelGGL((k_dec_down<decltype(nj)::value, R>), dim3((N + R - 1) / R), dim3(256), 0, st, hbuf, route,
                            W2, N, I, out, px);
+        return 0;
+    });
+}
+
+int vhk_dec_gateup_i8(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
+                      const uint16_t* Wg, int E, const int8_t* W1, const float* s1, const int8_t* W3, const float* s3, int I, int K,
+                      int* route_out, float* hbuf, int grid, const VhXchg* cxp) {
+    if (E > 8 || E < 2 || I % DEC_I8_RP != 0 || K % 8 != 0) return -1;
+    const int n_iter = 2 * (I / DEC_I8_RP);
+    const VhXchg cx = xchg_or_none(cxp);
+    if (grid <= 0) grid = dec_gateup_grid(I, DEC_I8_RP);
+    if (grid > n_iter) grid = n_iter;
+    return pick_nj(K, [&](auto nj) {
+        constexpr int NJ = decltype(nj)::value;
+        hipLaunchKernelGGL((k_dec_gateup_i8<NJ, DEC_I8_RP>), dim3(grid), dim3(256), 0, st, x_in, delta, x_out, norm_w, eps, Wg, E,
+                           W1, s1, W3, s3, I, K, route_out, hbuf, cx);
+        return 0;
+    });
+}
+int vhk_dec_down_i8(hipStream_t st, const float* hbuf, const int* route, const int8_t* W2, const float* s2, int N, int I,
+                    long row_stride, float* out, const VhXchg* pxp) {
+    if (I % 8 != 0 || N < 1 || row_stride < N) return -1;
+    const VhXchg px = xchg_or_none(pxp);
+    return pick_nj(I, [&](auto nj) {
+        hipLaunchKernelGGL((k_dec_down_i8<decltype(nj)::value, DEC_I8_R>), dim3((N + DEC_I8_R - 1) / DEC_I8_R), dim3(256), 0, st,
+                           hbuf, route, W2, s2, N, I, row_stride, out, px);
         return 0;
     });
 }

@@ -620,6 +620,31 @@ __global__ __launch_bounds__(256) void k_gather_rows(float* __restrict__ seq_x, 
         out[c] = v;
     }
 }
+// ---- int8 expert weights: per-row absmax quantisation --------------------------------------------------------
+// s[r] = max_k |w[r,k]| / 127, q = clamp(rint(w / s), -127, 127) (0 for an all-zero row), both divisions IEEE (the numpy
+// restatement in tests/q8_ref.py is matched bit for bit).  The scale is taken over all `cols`; only the columns
+// [col0, col0 + ncols) are written (a tensor-parallel rank's slice of w2 with the full-row scale).  One block per row.
+__global__ __launch_bounds__(256) void k_quant_rows_i8(const uint16_t* __restrict__ w, int cols, long ld_src, int col0, int ncols,
+                                                       int8_t* __restrict__ q, long ld_dst, float* __restrict__ s) {
+    __shared__ float red[8];
+    const long r = blockIdx.x;
+    const uint16_t* row = w + r * ld_src;
+    float mx = 0.f;
+    for (int k = threadIdx.x; k < cols; k += 256) mx = fmaxf(mx, fabsf(bf16_to_f32(row[k])));
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    const float sc = __fdiv_rn(mx, 127.0f);
+    if (threadIdx.x == 0) s[r] = sc;
+    int8_t* out = q + r * ld_dst;
+    for (int k = threadIdx.x; k < ncols; k += 256) {
+        float v = 0.f;
+        if (sc != 0.f) v = fminf(fmaxf(rintf(__fdiv_rn(bf16_to_f32(row[col0 + k]), sc)), -127.f), 127.f);
+        out[k] = (int8_t)(int)v;
+    }
+}
+
 }  // namespace
 
 int vhk_layernorm(hipStream_t st, const float* x, long ldx, float* y, long ldy, const float* w, const float* b,
@@ -646,6 +671,14 @@ int vhk_add_halves(hipStream_t st, float* x, const float* a, const float* b, int
     if (cols % 8 != 0) return -1;
     if (rows == 0) return 0;
     hipLaunchKernelGGL(k_add_halves, dim3(grid_for((long)rows * (cols / 4), 256)), dim3(256), 0, st, x, a, b, rows, cols / 4);
+    return 0;
+}
+int vhk_quant_rows_i8(hipStream_t st, const uint16_t* w, long rows, int cols, long ld_src, int col0, int ncols, int8_t* q,
+                      long ld_dst, float* s) {
+    if (rows < 0 || rows > 0x7fffffffL || cols < 1 || ld_src < cols || col0 < 0 || ncols < 1 || col0 + ncols > cols || ld_dst < ncols)
+        return -1;
+    if (rows == 0) return 0;
+    hipLaunchKernelGGL(k_quant_rows_i8, dim3((unsigned)rows), dim3(256), 0, st, w, cols, ld_src, col0, ncols, q, ld_dst, s);
     return 0;
 }
 int vhk_cast_bf16_f32(hipStream_t st, const uint16_t* in, float* out, long n) {

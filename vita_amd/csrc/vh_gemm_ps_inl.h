@@ -67,6 +67,7 @@ struct TileCtx {
     int n0;                          // first output column of the tile
     int k0, nk;                      // first K stage and stage count of this K split
     int ks;                          // K split index
+    int e;                           // group (expert) of the tile: int8 weights and their scales are addressed from it
     const uint16_t* Wb; const uint16_t* Wu;
 };
 
@@ -75,9 +76,12 @@ struct TileCtx {
 // NW = waves of the block (all of them store rows), HAS_ACC: the calling wave holds accumulators (the loader waves of the
 // specialised kernel do not: they only take part in the barriers and the row stores), LDS_BYTES = the block's LDS (the rings are
 // free after the K loop: the caller has passed a barrier behind the last fragment read).
-template <bool GLU, int RTMAX, int RTW, int NW, int LDS_BYTES, bool HAS_ACC>
+// SC (int8 weights): column n of the tile's group is multiplied by sc[n] (GLU: gate by sc, up by sc_up, before SiLU * up;
+// plain: the partial sum of the K slab, before the other epilogue terms).  sc / sc_up point at the group's scales.
+template <bool GLU, int RTMAX, int RTW, int NW, int LDS_BYTES, bool HAS_ACC, bool SC = false>
 __device__ __forceinline__ void tile_epilogue(const VhGemmPsArgs& p, const TileCtx& t, unsigned char* lds, const int lane,
-                                              const int wid, const int wm, const int wn, f32x4 (&acc)[RTW][4]) {
+                                              const int wid, const int wm, const int wn, f32x4 (&acc)[RTW][4],
+                                              const float* sc = nullptr, const float* sc_up = nullptr) {
     // The C^T accumulators give a lane 4 consecutive columns of ONE token: stored directly, a wave instruction touches 16
     // token rows x 64 B, rows tens of KB apart (r02).  For the K-split projections that is 40-70 MB of such stores per
     // launch, and it is where the slow boxes of the pool lose their time: QKV 133 us with the stores, 57 us without
@@ -100,8 +104,17 @@ __device__ __forceinline__ void tile_epilogue(const VhGemmPsArgs& p, const TileC
 #pragma unroll
                 for (int c = 0; c < 2; ++c) {
                     f32x4 v;
+                    if constexpr (SC) {
+                        const int n = t.n0 + wn * 32 + c * 16 + jc;
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = silu_f(acc[i][c][r]) * acc[i][c + 2][r];
+                        for (int r = 0; r < 4; ++r) {
+                            const int nn = n + r < p.N ? n + r : p.N - 1;   // columns past N: computed on clamped rows, never stored
+                            v[r] = silu_f(acc[i][c][r] * sc[nn]) * (acc[i][c + 2][r] * sc_up[nn]);
+                        }
+                    } else {
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] = silu_f(acc[i][c][r]) * acc[i][c + 2][r];
+                    }
                     *reinterpret_cast<f32x4*>(rowp + (wn * 32 + c * 16 + jc) * 4) = v;
                 }
             } else {
@@ -154,6 +167,7 @@ __device__ __forceinline__ void tile_epilogue(const VhGemmPsArgs& p, const TileC
                 for (int r = 0; r < 4; ++r) {
                     float tv = a[r];
                     if (n + r < p.N) {
+                        if constexpr (SC) tv *= sc[n + r];
                         if (p.bias) tv += p.bias[n + r];
                         tv = apply_act(tv, p.act);
                         if (p.scale) tv *= p.scale[n + r];
@@ -308,6 +322,7 @@ __device__ __forceinline__ void for_each_tile(const VhGemmPsArgs& p, F&& f) {
         }
         t.n0 = nt * NOUT;
         t.ks = ks;
+        t.e = e;
         t.k0 = (int)(((long)nk_total * ks) / KS);
         t.nk = (int)(((long)nk_total * (ks + 1)) / KS) - t.k0;
         t.Wb = p.W + (size_t)e * p.w_group_stride;

@@ -34,14 +34,17 @@ namespace {
 #include "vh_gemm_ps_inl.h"
 
 #define SP_WAVES 12
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;   // 8 int8 weights (one piece of the int8 stager)
 #define SP_NSLOT 4
 #ifndef SP_PRIO
 #define SP_PRIO 1          // s_setprio level of the MFMA waves (static).  0 / 1 / 3 measured (profiles/r04_sp_prio.txt): 520 / 505 / 502 us gate|up
 #endif
 
-template <bool GLU, int RTMAX, int RTW, int RTA, bool NTW>
+// I8: int8 weights (q) — the stagers load 8 bytes per piece and convert them to bf16 (exact: |q| <= 127) as they store
+// the SAME LDS image; the epilogue applies the group's column scales.  Everything else is the bf16 kernel's.
+template <bool GLU, int RTMAX, int RTW, int RTA, bool NTW, bool I8 = false>
 __device__ __forceinline__ void run_tile_sp(const VhGemmPsArgs& p, const TileCtx& t, unsigned char* lds, const int lane,
-                                            const int wid) {
+                                            const int wid, const VhPsI8* q8 = nullptr) {
     constexpr int A_BUF = RTMAX * 2 * MG_SUB;    // one activation stage: hi sub-tiles then lo sub-tiles
     constexpr int W_BASE = 2 * A_BUF;
     constexpr int LDS_BYTES = 2 * A_BUF + SP_NSLOT * MG_SLOT;
@@ -116,11 +119,109 @@ __device__ __forceinline__ void run_tile_sp(const VhGemmPsArgs& p, const TileCtx
         if (wm == 0) loop(std::integral_constant<int, RTW>{});
         else loop(std::integral_constant<int, RTA>{});
         __builtin_amdgcn_s_barrier();                 // every wave is done with the rings
-        tile_epilogue<GLU, RTMAX, RTW, SP_WAVES, LDS_BYTES, true>(p, t, lds, lane, wid, wm, wn, acc);
+        if constexpr (I8) {
+            tile_epilogue<GLU, RTMAX, RTW, SP_WAVES, LDS_BYTES, true, true>(p, t, lds, lane, wid, wm, wn, acc,
+                                                                             q8->s + (size_t)t.e * q8->s_group_stride,
+                                                                             GLU ? q8->s_up + (size_t)t.e * q8->s_group_stride : nullptr);
+        } else {
+            tile_epilogue<GLU, RTMAX, RTW, SP_WAVES, LDS_BYTES, true>(p, t, lds, lane, wid, wm, wn, acc);
+        }
         return;
     }
 
-    if (wid < 10) {
+    if (I8 && wid < 10) {
+        // ================================ int8 weight stagers: the schedule of the bf16 stagers below ===================
+        // piece q = 2 * s16 + u as there; its 16-byte bf16 chunk (lane & 7) ^ (row >> 1) is 8 BYTES of the int8 row.  The 32 pieces
+        // are held as loaded (64 VGPRs) and converted one at a time as they are stored.
+        const int g = wid - 8;
+        const size_t goff = (size_t)t.e * p.w_group_stride;
+        const unsigned char* w_gate = reinterpret_cast<const unsigned char*>(q8->W) + goff;
+        const unsigned char* w_up = reinterpret_cast<const unsigned char*>(GLU ? q8->W_up : q8->W) + goff;
+        const uint32_t ldw1 = (uint32_t)p.ldw;
+        uint32_t wcol[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) wcol[u] = (uint32_t)(((lane & 7) ^ (((u * 8 + lrow) >> 1) & 7)) * 8);
+        u32x2 wreg[32];
+#pragma unroll
+        for (int q = 0; q < 32; ++q) wreg[q] = u32x2{0u, 0u};
+        auto ld8 = [&](const unsigned char* base, int s16, int u, int lr) __attribute__((always_inline)) {
+            int n = GLU ? t.n0 + (s16 >> 2) * 32 + (s16 & 1) * 16 + u * 8 + lr : t.n0 + s16 * 16 + u * 8 + lr;
+            if (n > p.N - 1) n = p.N - 1;                                // clamped rows: products never stored
+            const uint32_t o = (uint32_t)n * ldw1 + wcol[u];
+            if (NTW) return __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(base + o));
+            return *reinterpret_cast<const u32x2*>(base + o);
+        };
+        auto cvt = [](const u32x2 v) __attribute__((always_inline)) {   // 8 int8 -> 8 bf16 (exact: the fp32 value's upper half)
+            u32x4 o;
+#pragma unroll
+            for (int h = 0; h < 4; ++h) {
+                const uint32_t wd = h < 2 ? v.x : v.y;
+                const uint32_t a = __float_as_uint((float)((int)(wd << (24 - 16 * (h & 1))) >> 24));
+                const uint32_t b = __float_as_uint((float)((int)(wd << (16 - 16 * (h & 1))) >> 24));
+                o[h] = (a >> 16) | (b & 0xffff0000u);
+            }
+            return o;
+        };
+        auto w_load = [&](int kt) __attribute__((always_inline)) {
+            const int kc = kt < t.nk ? kt : t.nk - 1;
+            const size_t kb = (size_t)(t.k0 + kc) * 64;
+            int lr = lrow;
+            asm volatile("" : "+v"(lr));
+#pragma unroll
+            for (int q = 0; q < 32; ++q) {
+                const int s16 = q >> 1, u = q & 1;
+                wreg[q] = ld8(((GLU && (s16 & 2)) ? w_up : w_gate) + kb, s16, u, lr);
+            }
+        };
+        unsigned char* const wr_dst0 = lds + W_BASE + lane * 16;
+        auto w_store = [&](int kt) __attribute__((always_inline)) {
+#pragma unroll
+            for (int q = 0; q < 32; ++q) {
+                const int s16 = q >> 1, u = q & 1;
+                *reinterpret_cast<u32x4*>(wr_dst0 + (((2 * kt) & 3) + (s16 >> 3)) * MG_SLOT + (s16 & 7) * MG_SUB + u * 1024) = cvt(wreg[q]);
+            }
+        };
+        {
+            const size_t kb = (size_t)t.k0 * 64;
+            int lr = lrow;
+            asm volatile("" : "+v"(lr));
+#pragma unroll
+            for (int qq = 0; qq < 16; ++qq) {
+                const int s16 = 8 * g + (qq >> 1), u = qq & 1;
+                wreg[qq] = ld8(((GLU && (s16 & 2)) ? w_up : w_gate) + kb, s16, u, lr);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int qq = 0; qq < 16; ++qq) {
+                const int s16 = qq >> 1, u = qq & 1;
+                *reinterpret_cast<u32x4*>(wr_dst0 + g * MG_SLOT + s16 * MG_SUB + u * 1024) = cvt(wreg[qq]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        w_load(1 + g);
+        __builtin_amdgcn_sched_barrier(0);
+        int k = g;
+        if (g == 1) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+        }
+        for (; k < t.nk; k += 2) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            if (k + 1 < t.nk) {
+                w_store(k + 1);
+                __builtin_amdgcn_sched_barrier(0);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                __builtin_amdgcn_sched_barrier(0);
+                w_load(k + 3);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+    } else if (wid < 10) {
         // ================================ weight stagers (stage parity g) =======================================
         const int g = wid - 8;
         const unsigned char* w_gate = reinterpret_cast<const unsigned char*>(t.Wb);
@@ -252,7 +353,13 @@ __device__ __forceinline__ void run_tile_sp(const VhGemmPsArgs& p, const TileCtx
         __builtin_amdgcn_s_barrier();
     }
     f32x4 none[RTW][4];
-    tile_epilogue<GLU, RTMAX, RTW, SP_WAVES, LDS_BYTES, false>(p, t, lds, lane, wid, 0, 0, none);
+    if constexpr (I8) {
+        tile_epilogue<GLU, RTMAX, RTW, SP_WAVES, LDS_BYTES, false, true>(p, t, lds, lane, wid, 0, 0, none,
+                                                                          q8->s + (size_t)t.e * q8->s_group_stride,
+                                                                          GLU ? q8->s_up + (size_t)t.e * q8->s_group_stride : nullptr);
+    } else {
+        tile_epilogue<GLU, RTMAX, RTW, SP_WAVES, LDS_BYTES, false>(p, t, lds, lane, wid, 0, 0, none);
+    }
 }
 
 
@@ -278,7 +385,64 @@ void k_gemm_sp(const VhGemmPsArgs p) {
     });
 }
 
+// int8 weights: the same kernel with the int8 stagers and the scaled epilogue
+template <bool GLU, int RTMAX, bool NTW>
+__global__ __launch_bounds__(64 * SP_WAVES) __attribute__((amdgpu_waves_per_eu(3, 3)))
+void k_gemm_sp_i8(const VhGemmPsArgs p, const VhPsI8 q8) {
+    constexpr int A_BUF = RTMAX * 2 * MG_SUB;
+    static_assert(2 * A_BUF + SP_NSLOT * MG_SLOT <= MG_LDS && (RTMAX % 2) == 0, "LDS budget / ring geometry");
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * A_BUF + SP_NSLOT * MG_SLOT];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for_each_tile<GLU, RTMAX>(p, [&](const TileCtx& t) __attribute__((always_inline)) {
+        switch (t.rt) {
+#define SP_CASE(RT)                                                                                                   \
+    case RT:                                                                                                          \
+        if constexpr (RTMAX >= RT) run_tile_sp<GLU, RTMAX, (RT + 1) / 2, RT / 2, NTW, true>(p, t, lds, lane, wid, &q8); \
+        break;
+            SP_CASE(1) SP_CASE(2) SP_CASE(3) SP_CASE(4) SP_CASE(5) SP_CASE(6)
+            SP_CASE(7) SP_CASE(8) SP_CASE(9) SP_CASE(10) SP_CASE(11) SP_CASE(12)
+#undef SP_CASE
+            default: break;
+        }
+    });
+}
+
 }  // namespace
+
+int vhk_gemm_ps_i8(hipStream_t st, const VhGemmPsArgs& a0, const VhPsI8& q) {
+    VhGemmPsArgs a = a0;
+    if (a.K <= 0 || a.K % 64 != 0 || a.M < 0 || a.N <= 0 || (a.lda % 8) != 0 || (a.ldw % 8) != 0) return -1;
+    if (a.W || a.W_up || !q.W || !q.s || (q.W_up != nullptr) != (q.s_up != nullptr)) return -1;
+    if (!a.A_hi || !a.A_lo || (!a.C && !a.C_hi) || (a.C_hi && !a.C_lo)) return -1;
+    const bool glu = q.W_up != nullptr;
+    if (a.ksplit == 0) a.ksplit = 1;
+    if (a.ksplit < -8) return -1;
+    if ((a.ksplit > 1 || a.ksplit < 0) && (glu || a.bias || a.scale || a.resid || a.act != VH_ACT_NONE || a.C_hi || !a.C)) return -1;
+    if (a.ksplit < 0 && !a.nslab_out) return -1;
+    if (a.ksplit > (a.K >> 6)) return -1;
+    if (a.group_off && a.ngroups > 8) return -1;
+    if ((size_t)a.ldw * (size_t)a.N >= (1ull << 32)) return -1;      // 32-bit per-lane byte offsets inside one group
+    if (a.M == 0) return 0;
+    int grid = vh_num_cus() & ~7;
+    if (grid < 8) grid = 8;
+    if (!a.group_off && a.ksplit >= 1 && a.rt_cap == 0) {
+        const int nrt = (a.M + 15) >> 4, NT = (a.N + (glu ? 127 : 255)) / (glu ? 128 : 256);
+        for (int c = 3; c < 12; ++c)
+            if ((long)((nrt + c - 1) / c) * NT * a.ksplit <= grid) { a.rt_cap = c; break; }
+    }
+    const int px = vh_tuning()->ps_xcd < 0 ? 3 : vh_tuning()->ps_xcd;
+    a.xcd_group = a.group_off ? ((glu ? (px >> 1) : px) & 1) : 0;
+    const bool nt = vh_tuning()->ps_nt > 0;
+    if (glu) {
+        if (nt) hipLaunchKernelGGL((k_gemm_sp_i8<true, 12, true>), dim3(grid), dim3(64 * SP_WAVES), 0, st, a, q);
+        else hipLaunchKernelGGL((k_gemm_sp_i8<true, 12, false>), dim3(grid), dim3(64 * SP_WAVES), 0, st, a, q);
+    } else {
+        if (nt) hipLaunchKernelGGL((k_gemm_sp_i8<false, 12, true>), dim3(grid), dim3(64 * SP_WAVES), 0, st, a, q);
+        else hipLaunchKernelGGL((k_gemm_sp_i8<false, 12, false>), dim3(grid), dim3(64 * SP_WAVES), 0, st, a, q);
+    }
+    return 0;
+}
 
 // arguments already checked by vhk_gemm_ps (vh_gemm_ps.hip)
 int vhk_gemm_sp(hipStream_t st, const VhGemmPsArgs& a, int grid, bool nt) {

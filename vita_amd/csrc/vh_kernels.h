@@ -101,7 +101,7 @@ int vh_comm_is_loopback(const vh_comm* c);        // a single-rank communicator 
 // cx (nullable): the delta is the result of a fused exchange (then `delta` is ignored); px (nullable): push the outputs
 int vhk_dec_qkv(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
                 const uint16_t* W, int N, int K, float* out, const VhXchg* cx = nullptr);
-int vhk_dec_consumer_blocks(int which, int N, int K, int I);   // grid of a consumer launch (0 qkv, 1 gate|up, 2 lm head, 3 fused attention block): bounds nred
+int vhk_dec_consumer_blocks(int which, int N, int K, int I);   // grid of a consumer launch (0 qkv, 1 gate|up, 2 lm head, 3 fused attention block, 4 int8 gate|up): bounds nred
 int vhk_dec_attn(hipStream_t st, const float* qkv, float* kcache, float* vcache, const int* pos_ptr,
                  const float* rope_cos, const float* rope_sin, float* part_o, float* part_ml, int* cnt,
                  float* attn_out, int nq, int nkv, int max_ctx, int max_splits, int ctx_host, float scale,
@@ -162,6 +162,13 @@ int vhk_dec_gateup(hipStream_t st, const float* x_in, const float* delta, float*
                    float* hbuf, int grid, const VhXchg* cx = nullptr);
 int vhk_dec_down(hipStream_t st, const float* hbuf, const int* route, const uint16_t* W2, int N, int I, float* out,
                  const VhXchg* px = nullptr);
+// int8 experts (per-output-row scales s[e][row]): the same launches on int8 weights, (sum_k x_k q_k) * s in fp32
+int vhk_dec_gateup_i8(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
+                      const uint16_t* Wg, int E, const int8_t* W1, const float* s1, const int8_t* W3, const float* s3, int I, int K,
+                      int* route_out, float* hbuf, int grid, const VhXchg* cx = nullptr);
+// W2 / s2: the first of the N rows this call computes (a column slice of the experts' [Ntot][I]); row_stride = rows per expert (Ntot)
+int vhk_dec_down_i8(hipStream_t st, const float* hbuf, const int* route, const int8_t* W2, const float* s2, int N, int I,
+                    long row_stride, float* out, const VhXchg* px = nullptr);
 int vhk_dec_lmhead(hipStream_t st, const float* x_in, const float* delta, const float* norm_w, float eps,
                    const uint16_t* W, int V, int K, float* logits, float* blk_val, int* blk_idx, int grid,
                    const int* ngen_ptr, int hist_rows, int v0, int Vfull, const VhXchg* cx = nullptr,
@@ -223,6 +230,17 @@ struct VhGemmPsArgs {
 };
 int vhk_gemm_ps(hipStream_t st, const VhGemmPsArgs& a);
 int vhk_gemm_sp(hipStream_t st, const VhGemmPsArgs& a, int grid, bool nt);   // vh_gemm_sp.hip: 12-wave specialised form (arguments already checked)
+// int8 expert weights: a.W / a.W_up are null, a.ldw / a.w_group_stride count int8 elements; the stager converts
+// q to bf16 (exact) into the same LDS image and the epilogue multiplies column n of group e by s[e * s_group_stride + n]
+// (GLU: gate by s, up by s_up, before SiLU * up).  Always the specialised form.
+struct VhPsI8 {
+    const int8_t* W; const int8_t* W_up;
+    const float* s; const float* s_up; long s_group_stride;
+};
+int vhk_gemm_ps_i8(hipStream_t st, const VhGemmPsArgs& a, const VhPsI8& q);
+// w[rows][ld_src] bf16 -> q[rows][ld_dst] int8 (columns [col0, col0 + ncols)) + s[rows] fp32, the scale over all `cols`
+int vhk_quant_rows_i8(hipStream_t st, const uint16_t* w, long rows, int cols, long ld_src, int col0, int ncols, int8_t* q,
+                      long ld_dst, float* s);
 int vhk_split_planes(hipStream_t st, const float* x, long ldx, uint16_t* hi, uint16_t* lo, long ldo, int rows,
                      int cols);
 

@@ -80,8 +80,12 @@ def load_pretrained_model(model_path, model_base, model_name, model_type, load_8
                           device_map="auto", device="cuda", **kwargs):
     if model_type not in {"mixtral-8x7b"}:
         raise ValueError(f"Unknown Model Type {model_type}")          # builder.py:25-26
-    if load_8bit or load_4bit:
-        raise NotImplementedError("bitsandbytes quantisation is not part of the HIP path (bf16 weights)")
+    if load_4bit:
+        raise NotImplementedError("4-bit quantisation is not part of the HIP path")
+    # load_8bit: the MoE experts (88 % of a token's weight bytes) as int8 with per-output-row scales, quantised on the device
+    # (DESIGN 5.5).  Not bitsandbytes' LLM.int8(): activations stay fp32 and there is no outlier split.
+    if load_8bit:
+        kwargs["experts_int8"] = True
     if model_base is not None or "lora" in (model_name or "").lower():
         warnings.warn("LoRA merge is a training-side feature and is not reproduced; loading merged weights only")
     from transformers import AutoTokenizer

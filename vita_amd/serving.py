@@ -135,8 +135,11 @@ def expanded_token_ids(sentinel_ids, audio_frames, *, image_token_index, audio_t
 class LLM:
     def __init__(self, model, dtype=None, tensor_parallel_size=1, trust_remote_code=True, gpu_memory_utilization=None,
                  disable_custom_all_reduce=True, limit_mm_per_prompt=None, max_new_tokens=1024, device="cuda",
-                 max_num_seqs=0, kv_pool_tokens=None, **_):
+                 max_num_seqs=0, kv_pool_tokens=None, quantization=None, **_):
         from .model.builder import load_pretrained_model
+        # vLLM's quantization="experts_int8": the MoE experts as int8 with per-output-row scales
+        if quantization not in (None, "experts_int8"):
+            raise ValueError(f"quantization={quantization!r}: vita_amd supports None and 'experts_int8'")
         world = int(os.environ.get("WORLD_SIZE", "1"))
         if tensor_parallel_size != 1 and tensor_parallel_size != world:
             raise RuntimeError(
@@ -152,7 +155,7 @@ class LLM:
         self.tokenizer, self.model, self.image_processor, _ = load_pretrained_model(
             model, None, os.path.basename(str(model).rstrip("/")), "mixtral-8x7b", device=device,
             max_new_tokens=max_new_tokens, max_seqs=int(max_num_seqs), kv_pool_tokens=kv_pool_tokens,
-            gpu_memory_utilization=gpu_memory_utilization, **kw)
+            gpu_memory_utilization=gpu_memory_utilization, load_8bit=quantization == "experts_int8", **kw)
         self.collective = "none"
         if world > 1:
             from .parallel import setup_tensor_parallel
@@ -507,6 +510,7 @@ class AsyncEngineArgs:
     kv_pool_tokens: Optional[int] = None     # size of the paged KV pool; default: max_num_seqs x (<= 1024-token prompt + max_new_tokens),
                                              # bounded by gpu_memory_utilization of the free memory (VITAMixtralForCausalLM.default_kv_pool_tokens)
     device: str = "cuda"
+    quantization: Optional[str] = None       # None or "experts_int8" (LLM)
 
 
 class AsyncLLMEngine:
@@ -538,7 +542,7 @@ class AsyncLLMEngine:
         llm = LLM(args.model, dtype=args.dtype, tensor_parallel_size=args.tensor_parallel_size,
                   gpu_memory_utilization=args.gpu_memory_utilization,
                   limit_mm_per_prompt=args.limit_mm_per_prompt, max_new_tokens=args.max_new_tokens, device=args.device,
-                  max_num_seqs=args.max_num_seqs, kv_pool_tokens=pool)
+                  max_num_seqs=args.max_num_seqs, kv_pool_tokens=pool, quantization=args.quantization)
         return cls(llm, max_num_seqs=args.max_num_seqs, **kw)
 
     async def get_tokenizer(self):
