@@ -327,12 +327,30 @@ int vh_mixtral_reset(vh_mixtral_t* m, void* stream);     /* n_generated = 0, pos
  *   seq_alloc   -> slot id >= 0, or VH_E_FULL
  *   seq_prefill    appends S embedded tokens at the sequence's current position and leaves its next greedy token in
  *                  seq_tokens[0] (n_generated restarts at 0, as vh_mixtral_prefill); VH_E_FULL when pages run out
+ *   seq_prefill_batch  the same for several sequences in one pass over the weights (below)
  *   seq_decode     one greedy step for each listed sequence, in order, on `stream` (a continuous-batching iteration)
  *   seq_free       returns the pages;  vh_mixtral_reset frees every sequence */
 int vh_mixtral_seq_alloc(vh_mixtral_t* m);
 int vh_mixtral_seq_free(vh_mixtral_t* m, int seq);
 int vh_mixtral_seq_prefill(vh_mixtral_t* m, int seq, const float* embeds, int S, float* logits_out, void* stream);
 int vh_mixtral_seq_decode(vh_mixtral_t* m, const int* seqs /* host */, int n, void* stream);
+/* seq_prefill for n distinct live sequences in ONE pass over the weights (what vLLM's scheduler does with the prompts of queued
+ * requests up to max_num_batched_tokens; here the bound is max_prefill).  embeds: device fp32 [sum(lens)][hidden], the segments'
+ * rows back to back in list order.  Segment i appends lens[i] tokens at sequence seqs[i]'s current position (0 for a new sequence,
+ * > 0 for a later chunk or turn) and leaves that sequence's next token in its seq_tokens[0] (n_generated restarts at 0), drawn with
+ * THAT sequence's sampling parameters.  logits_out (nullable): device fp32 [n][vocab], row i = the scores of segment i's last
+ * position.  Afterwards the state is what n vh_mixtral_seq_prefill calls in list order leave.
+ *   The WHOLE call is checked before anything is enqueued or allocated: 1 <= n <= max_seqs, every slot live and not poisoned, no
+ * slot twice, every lens[i] >= 1, sum(lens) <= max_prefill, every position + lens[i] < max_ctx; VH_E_FULL when the pool cannot
+ * hold all segments (vh_mixtral_pages_free and every vh_mixtral_seq_pos are then what they were).  A failure after the first
+ * enqueue poisons exactly the listed sequences.  n == 1 IS vh_mixtral_seq_prefill.
+ *   Numerics: the rows of a sequence go through the same kernels and the same per-row arithmetic as alone, but not necessarily in
+ * the same fp32 summation order (the K split of the projections is chosen on the device from the tile count of the pass, the
+ * attention launcher picks its kernel from the launch size — as for batched decode iterations).  Ids and scores of a sequence
+ * agree with the fp32 oracle of THAT SEQUENCE ALONE within the project's bar (ids equal, scores atol 1e-3); they are not
+ * bit-identical with the one-by-one path.  K / V tile images stay a feature of the one-segment pass. */
+int vh_mixtral_seq_prefill_batch(vh_mixtral_t* m, const int* seqs /* host */, const int* lens /* host */, int n,
+                                 const float* embeds, float* logits_out, void* stream);
 int vh_mixtral_pages_free(const vh_mixtral_t* m);
 int vh_mixtral_seq_pos(const vh_mixtral_t* m, int seq);                  /* tokens in the sequence's KV cache, -1 = not live */
 const int* vh_mixtral_seq_tokens(const vh_mixtral_t* m, int seq);        /* device int[max_new]  */

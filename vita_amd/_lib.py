@@ -187,6 +187,7 @@ SIGNATURES = {
     "vh_mixtral_seq_alloc": (c_int, [c_void_p]),
     "vh_mixtral_seq_free": (c_int, [c_void_p, c_int]),
     "vh_mixtral_seq_prefill": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "vh_mixtral_seq_prefill_batch": (c_int, [c_void_p, C.POINTER(c_int), C.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p]),
     "vh_mixtral_seq_decode": (c_int, [c_void_p, C.POINTER(c_int), c_int, c_void_p]),
     "vh_mixtral_pages_free": (c_int, [c_void_p]),
     "vh_mixtral_seq_pos": (c_int, [c_void_p, c_int]),

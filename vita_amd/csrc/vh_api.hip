@@ -362,6 +362,8 @@ struct vh_mixtral {
     std::vector<Seq> seqs;
     std::vector<int> free_pages;
     std::vector<int> batch_ids_host;   // slot list last uploaded to seq_batch (storage reserved once)
+    std::vector<VhSeg> segs_host;      // segment descriptors of the current batched prefill pass (storage reserved once: uploads read from it)
+    VhSeg* seq_segs = nullptr;         // [max_seqs] the same on the device
     float* seq_x = nullptr;            // [max_seqs][4][H]: xa, xb, delta_attn, delta_moe
     int *seq_counters = nullptr, *seq_tokens = nullptr, *seq_table = nullptr, *seq_batch = nullptr;
     // scratch "lanes" 1..VH_BMAX-1 of the per-step buffers (lane 0 = the single-sequence ones) for batched decode iterations
@@ -417,6 +419,8 @@ struct vh_mixtral {
         for (int pg = n_pages() - 1; pg >= 0; --pg) free_pages.push_back(pg);   // page 0 is handed out first
         batch_ids_host.clear();
         batch_ids_host.reserve(seqs.size() + 1);
+        segs_host.clear();
+        segs_host.reserve(seqs.size() + 1);
     }
     int rccl_gen = 0;           // bumped by vh_mixtral_cancel_rccl: a pending vh_mixtral_init_rccl then discards its communicator
     int poisoned = 0;           // a decode step failed half-way: only prefill / reset may follow
@@ -476,6 +480,7 @@ struct vh_mixtral {
             seq_tokens = cv.take<int>(n * (c.max_new > 0 ? c.max_new : 1));
             seq_table = cv.take<int>(n * max_splits);
             seq_batch = cv.take<int>(n);
+            seq_segs = cv.take<VhSeg>(n);   // 24 bytes per slot: the segments of a batched prefill pass
             l_qkv[0] = qkv; l_part_o[0] = part_o; l_part_ml[0] = part_ml; l_attn_out[0] = attn_out; l_attn_cnt[0] = attn_cnt;
             l_hbuf[0] = hbuf; l_route[0] = route; l_blk_val[0] = blk_val; l_blk_idx[0] = blk_idx; l_cand[0] = cand;
             for (int b = 1; b < VH_BMAX; ++b) {
@@ -878,18 +883,46 @@ static int moe_down(vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, co
     return VH_OK;
 }
 
-static int prefill_impl(vh_mixtral* m, const float* embeds, int Sn, int pos0, float* logits_out, float* hidden_dbg,
+// One pass over the weights for the rows of nseg segments, back to back in embeds.  One segment: the engine's CURRENT sequence (the
+// default state, or the slot the caller bound).  Several: distinct slots (seq), addressed in place — everything row-wise runs on all
+// Sn rows at once; RoPE + KV write and attention take the segment descriptors, the head runs per slot through batched_head.
+struct PfSeg { int seq, len, pos0; };
+static int batched_head(vh_mixtral* m, hipStream_t st, const int* ids, int n, const float* const* x_in, const float* const* delta,
+                        int mode, const int* set_pos, float* logits_out);
+static int prefill_impl(vh_mixtral* m, const float* embeds, const PfSeg* sg, int nseg, float* logits_out, float* hidden_dbg,
                         hipStream_t st) {
+    int Sn = 0, kmax = 0;
+    for (int i = 0; i < nseg; ++i) {
+        if (sg[i].len < 1) return fail(VH_E_SHAPE, "prefill length %d outside [1,%d]", sg[i].len, m->c.max_prefill);
+        if (sg[i].pos0 < 0 || sg[i].pos0 + sg[i].len >= m->c.max_ctx) return fail(VH_E_SHAPE, "prefill exceeds KV capacity %d", m->c.max_ctx);
+        Sn += sg[i].len;
+        if (sg[i].pos0 + sg[i].len > kmax) kmax = sg[i].pos0 + sg[i].len;
+    }
     if (Sn < 1 || Sn > m->c.max_prefill) return fail(VH_E_SHAPE, "prefill length %d outside [1,%d]", Sn, m->c.max_prefill);
-    if (pos0 < 0 || pos0 + Sn >= m->c.max_ctx) return fail(VH_E_SHAPE, "prefill exceeds KV capacity %d", m->c.max_ctx);
+    const bool multi = nseg > 1;
+    const int pos0 = sg[0].pos0;
     const int H = m->H, nq = m->nq, nkv = m->nkv, hd = m->hd, KO = nq * hd;
     const bool tp = m->c.tp_world > 1 || vh_tuning()->force_allreduce;
     const float scale = 1.0f / sqrtf((float)hd);
     int rc;
     if (hipMemcpyAsync(m->px, embeds, (size_t)Sn * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
         return fail(VH_E_HIP, "prefill: embed copy failed");
-    if (hipMemsetAsync(m->counters + 1, 0, 3 * sizeof(int), st) != hipSuccess) return fail(VH_E_HIP, "memset failed");
-    m->poisoned = 0;
+    if (multi) {
+        // the descriptors go up once, before layer 0, from storage that outlives the copy; every listed slot starts as the one bound
+        // sequence does below (counters 1-3 zeroed)
+        m->segs_host.resize(nseg);
+        int row0 = 0;
+        for (int i = 0; i < nseg; ++i) {
+            m->segs_host[i] = VhSeg{row0, sg[i].len, sg[i].pos0, 0, m->seq_table + (size_t)sg[i].seq * m->max_splits};
+            row0 += sg[i].len;
+            if (hipMemsetAsync(m->seq_counters + 4 * sg[i].seq + 1, 0, 3 * sizeof(int), st) != hipSuccess) return fail(VH_E_HIP, "memset failed");
+        }
+        if (hipMemcpyAsync(m->seq_segs, m->segs_host.data(), (size_t)nseg * sizeof(VhSeg), hipMemcpyHostToDevice, st) != hipSuccess)
+            return fail(VH_E_HIP, "prefill: segment descriptor upload failed");
+    } else {
+        if (hipMemsetAsync(m->counters + 1, 0, 3 * sizeof(int), st) != hipSuccess) return fail(VH_E_HIP, "memset failed");
+        m->poisoned = 0;
+    }
     if (m->c.vocab_n > 0 && m->c.tp_world > 1 &&
         hipMemsetAsync(m->logits, 0, (size_t)m->hist_rows() * m->V * sizeof(float), st) != hipSuccess)
         return fail(VH_E_HIP, "memset failed");   // vocab-sharded head: a kept score row holds THIS rank's slice, zeros elsewhere
@@ -913,7 +946,7 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, int Sn, int pos0, fl
     const bool attn_planes = stream_attn && vh_tuning()->prefill_fuse_rows != 0 && (hd == 64 || hd == 128);
     // (r06) one-shot prefills whose attention is the flash kernel get K / V as MFMA-ready tile images from the RoPE pass
     bool use_img = false;
-    if (stream_attn && pos0 == 0 && m->kv_img && (Sn + 63) / 64 <= m->img_tiles && vh_tuning()->attn_img != 0) {
+    if (!multi && stream_attn && pos0 == 0 && m->kv_img && (Sn + 63) / 64 <= m->img_tiles && vh_tuning()->attn_img != 0) {
         VhAttnArgs q{};
         q.Sq = Sn; q.Sk = Sn; q.d = hd; q.Hq = nq; q.Hkv = nkv; q.B = 1; q.causal = 1;
         use_img = vhk_attn_fa_applies(q) != 0;
@@ -947,6 +980,9 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, int Sn, int pos0, fl
             if (use_img)   // one-shot prefill under the flash kernel: RoPE + cache write + the K / V tile images in one pass
                 VH_TRY(vhk_rope_kv_img(st, m->py, m->nqkv, m->pq, kc, vc, m->rope_cos, m->rope_sin, Sn, nq, nkv, m->c.max_ctx,
                                        m->table, m->pnslab + 1, g.c_split_stride, m->kv_img, m->img_tiles), "rope + images");
+            else if (multi)   // all segments in one launch: row -> (segment, position, page row) from the descriptors
+                VH_TRY(vhk_rope_kv_segs(st, m->py, m->nqkv, m->pq, kc, vc, m->rope_cos, m->rope_sin, Sn, m->seq_segs, nseg, nq, nkv,
+                                        m->c.max_ctx, m->pnslab + 1, g.c_split_stride), "rope");
             else
                 VH_TRY(vhk_rope_kv(st, m->py, m->nqkv, m->pq, kc, vc, m->rope_cos, m->rope_sin, Sn, pos0, nq, nkv,
                                    m->c.max_ctx, m->table, m->pnslab + 1, g.c_split_stride), "rope");
@@ -956,8 +992,12 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, int Sn, int pos0, fl
             g.A = m->pxn; g.lda = H; g.a_rows = Sn; g.nseg = 1; g.seglen = H;
             g.W = w.wqkv; g.ldw = H; g.C = m->pqkv; g.ldc = m->nqkv; g.M = Sn; g.N = m->nqkv; g.K = H;
             VH_TRY(vhk_gemm(st, g), "qkv gemm");
-            VH_TRY(vhk_rope_kv(st, m->pqkv, m->nqkv, m->pq, kc, vc, m->rope_cos, m->rope_sin, Sn, pos0, nq, nkv,
-                               m->c.max_ctx, m->table, nullptr, 0), "rope");
+            if (multi)
+                VH_TRY(vhk_rope_kv_segs(st, m->pqkv, m->nqkv, m->pq, kc, vc, m->rope_cos, m->rope_sin, Sn, m->seq_segs, nseg, nq, nkv,
+                                        m->c.max_ctx, nullptr, 0), "rope");
+            else
+                VH_TRY(vhk_rope_kv(st, m->pqkv, m->nqkv, m->pq, kc, vc, m->rope_cos, m->rope_sin, Sn, pos0, nq, nkv,
+                                   m->c.max_ctx, m->table, nullptr, 0), "rope");
         }
         // ---- attention
         VhAttnArgs a{};
@@ -968,6 +1008,10 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, int Sn, int pos0, fl
         a.B = 1; a.Hq = nq; a.Hkv = nkv; a.Sq = Sn; a.Sk = pos0 + Sn; a.d = hd;
         a.causal = 1; a.q_off = pos0; a.klen = pos0 + Sn; a.chunk = 0; a.left = -1; a.scale = scale;
         a.ktable = m->table; a.kv_rows = m->c.max_ctx;
+        if (multi) {   // every segment against its own sequence's pages, one call
+            a.segs = m->seq_segs; a.segs_host = m->segs_host.data(); a.nseg = nseg;
+            a.Sk = kmax; a.klen = kmax; a.q_off = 0; a.ktable = nullptr;
+        }
         if (use_img) { a.kv_img = m->kv_img; a.img_tiles = m->img_tiles; }
         if (attn_planes) { a.O = nullptr; a.O_hi = m->ph_hi; a.O_lo = m->ph_lo; a.ldo_split = KO; }
         VH_TRY(vhk_attn(st, a), "attention");
@@ -1045,10 +1089,22 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, int Sn, int pos0, fl
     }
     // logits of the last position only (the reference computes all S rows and uses the last:
     // vita_mixtral.py:171-172 + HF greedy argmax(logits[:, -1]))
-    if ((rc = head_and_select(m, st, m->px + (size_t)(Sn - 1) * H, nullptr, /*mode=*/0, /*set_pos=*/pos0 + Sn)) != VH_OK) return rc;
-    m->host_pos = pos0 + Sn;
-    if (logits_out)
-        (void)hipMemcpyAsync(logits_out, m->logits, (size_t)m->V * sizeof(float), hipMemcpyDeviceToDevice, st);
+    if (multi) {
+        // the first token of every segment: final norm + LM head + select on the segments' last rows, each with its slot's sampling,
+        // counters and next-embedding row (the batched head of a decode iteration; host positions advance in the caller)
+        std::vector<int> ids(nseg), set_pos(nseg);
+        std::vector<const float*> xin(nseg), dl(nseg, nullptr);
+        for (int i = 0; i < nseg; ++i) {
+            ids[i] = sg[i].seq; set_pos[i] = sg[i].pos0 + sg[i].len;
+            xin[i] = m->px + (size_t)(m->segs_host[i].row0 + sg[i].len - 1) * H;
+        }
+        if ((rc = batched_head(m, st, ids.data(), nseg, xin.data(), dl.data(), /*mode=*/0, set_pos.data(), logits_out)) != VH_OK) return rc;
+    } else {
+        if ((rc = head_and_select(m, st, m->px + (size_t)(Sn - 1) * H, nullptr, /*mode=*/0, /*set_pos=*/pos0 + Sn)) != VH_OK) return rc;
+        m->host_pos = pos0 + Sn;
+        if (logits_out)
+            (void)hipMemcpyAsync(logits_out, m->logits, (size_t)m->V * sizeof(float), hipMemcpyDeviceToDevice, st);
+    }
     hipError_t e = hipGetLastError();          // also what an event / copy enqueue above ((void) calls) left behind
     if (e != hipSuccess) return fail(VH_E_HIP, "prefill: %s", hipGetErrorString(e));
     return VH_OK;
@@ -1161,7 +1217,8 @@ int vh_mixtral_prefill(vh_mixtral_t* m, const float* embeds, int Sn, int pos0, f
                        void* stream) {
     if (!m || !embeds) return fail(VH_E_ARG, "vh_mixtral_prefill: null pointer");
     if (m->live_seqs() > 0) return fail(VH_E_ARG, "vh_mixtral_prefill: sequences own pages of the KV pool (free them or reset)");
-    return prefill_impl(m, embeds, Sn, pos0, logits_out, hidden_dbg, S(stream));
+    const PfSeg one{-1, Sn, pos0};
+    return prefill_impl(m, embeds, &one, 1, logits_out, hidden_dbg, S(stream));
 }
 
 // Vocab-sharded head: this rank's best per-block candidate (value, index; a 4-float key when sampled) goes into its slot of
@@ -1381,10 +1438,126 @@ int vh_mixtral_seq_prefill(vh_mixtral_t* m, int s, const float* embeds, int Sn, 
                               s, (pos0 + Sn + 63) / 64 - m->seqs[s].npages);
     if (pr != 0) return fail(VH_E_HIP, "page table upload failed");
     m->bind(s);
-    const int rc = prefill_impl(m, embeds, Sn, pos0, logits_out, nullptr, st);
+    const PfSeg one{s, Sn, pos0};
+    const int rc = prefill_impl(m, embeds, &one, 1, logits_out, nullptr, st);
     if (rc != VH_OK) m->poisoned = 1;
     m->unbind();
     return rc;
+}
+
+int vh_mixtral_seq_prefill_batch(vh_mixtral_t* m, const int* seqs, const int* lens, int n, const float* embeds, float* logits_out,
+                                 void* stream) {
+    const char* what = "vh_mixtral_seq_prefill_batch";
+    if (!m || !seqs || !lens || !embeds) return fail(VH_E_ARG, "%s: null pointer", what);
+    if (n < 1 || n > (int)m->seqs.size()) return fail(VH_E_ARG, "%s: %d segments outside [1,%d]", what, n, (int)m->seqs.size());
+    hipStream_t st = S(stream);
+    // the whole call is checked before anything is enqueued or allocated
+    long rows = 0, pages = 0;
+    for (int i = 0; i < n; ++i) {
+        const int rc = seq_ok(m, seqs[i], what);
+        if (rc != VH_OK) return rc;
+        const vh_mixtral::Seq& q = m->seqs[seqs[i]];
+        if (q.poisoned) return fail(VH_E_ARG, "sequence %d: a previous step failed; free it", seqs[i]);
+        for (int j = 0; j < i; ++j)
+            if (seqs[j] == seqs[i]) return fail(VH_E_ARG, "%s: sequence %d is listed twice", what, seqs[i]);
+        if (lens[i] < 1) return fail(VH_E_SHAPE, "%s: segment %d has %d rows", what, i, lens[i]);
+        if (q.host_pos + (long)lens[i] >= m->c.max_ctx)
+            return fail(VH_E_SHAPE, "prefill of %d tokens at %d exceeds the pool", lens[i], q.host_pos);
+        rows += lens[i];
+        const int need = (q.host_pos + lens[i] + 63) / 64;
+        if (need > q.npages) pages += need - q.npages;
+    }
+    if (rows > m->c.max_prefill) return fail(VH_E_SHAPE, "%s: %ld rows exceed max_prefill %d", what, rows, m->c.max_prefill);
+    if (pages > (long)m->free_pages.size())
+        return fail(VH_E_FULL, "KV pool exhausted: %d pages free, the %d segments need %ld more", (int)m->free_pages.size(), n, pages);
+    if (n == 1) return vh_mixtral_seq_prefill(m, seqs[0], embeds, lens[0], logits_out, stream);
+    std::vector<PfSeg> sg(n);
+    std::vector<int> had(n);
+    for (int i = 0; i < n; ++i) had[i] = m->seqs[seqs[i]].npages;
+    for (int i = 0; i < n; ++i) {
+        vh_mixtral::Seq& q = m->seqs[seqs[i]];
+        sg[i] = PfSeg{seqs[i], lens[i], q.host_pos};
+        if (m->ensure_pages(seqs[i], q.host_pos + lens[i], st) != 0) {
+            for (int j = i; j >= 0; --j) {          // pages taken for this call go back, in the order they would be handed out again
+                vh_mixtral::Seq& r = m->seqs[seqs[j]];
+                while (r.npages > had[j]) m->free_pages.push_back(r.pages[--r.npages]);
+            }
+            return fail(VH_E_HIP, "page table upload failed");
+        }
+    }
+    const int rc = prefill_impl(m, embeds, sg.data(), n, logits_out, nullptr, st);
+    for (int i = 0; i < n; ++i) {
+        vh_mixtral::Seq& q = m->seqs[seqs[i]];
+        if (rc != VH_OK) q.poisoned = 1;        // enqueued in part: exactly the listed sequences are lost
+        else q.host_pos += lens[i];
+    }
+    return rc;
+}
+
+// Final norm + LM head + token select for n sequence slots (ids), in groups of up to VH_BMAX per pass over the table: row b is
+// x_in[b] (+ delta[b]; all null or all set), drawn with slot ids[b]'s sampling parameters at its own draw index; the token, the
+// counters and the next embedding land in the slot.  mode 1: a decode step (append, pos++); mode 0: the end of a prefill (first token,
+// pos = set_pos[b]).  logits_out (nullable): device fp32 [n][vocab], row b = the scores of x_in[b] (a vocab-sharded head: this rank's
+// slice, zeros elsewhere).  Shared by decode_iteration and the batched prefill pass.
+static int batched_head(vh_mixtral* m, hipStream_t st, const int* ids, int n, const float* const* x_in, const float* const* delta,
+                        int mode, const int* set_pos, float* logits_out) {
+    const int H = m->H;
+    const float eps = m->c.rms_eps;
+    const bool sharded = m->c.vocab_n > 0 && m->c.tp_world > 1;
+    if (logits_out && sharded &&
+        (hipMemsetAsync(m->samp_rows, 0, (size_t)VH_BMAX * m->V * sizeof(float), st) != hipSuccess ||
+         hipMemsetAsync(m->logits, 0, (size_t)m->V * sizeof(float), st) != hipSuccess))
+        return fail(VH_E_HIP, "memset failed");
+    for (int g0 = 0; g0 < n; g0 += VH_BMAX) {
+        const int gn = n - g0 < VH_BMAX ? n - g0 : VH_BMAX;
+        VhDecBatchVec hv{};
+        VhDecBatchHead hdp{};
+        VhDecSampleJob sj{};
+        bool filt[VH_BMAX] = {};
+        hv.n = gn;
+        sj.V = m->V; sj.hist_rows = 1;
+        for (int b = 0; b < gn; ++b) {
+            const VhSampleParams& sp = m->seqs[ids[g0 + b]].samp;
+            int* cnt = m->seq_counters + 4 * ids[g0 + b];
+            hv.x_in[b] = x_in[g0 + b]; hv.delta[b] = delta[g0 + b];
+            hdp.blk_val[b] = m->l_blk_val[b]; hdp.blk_idx[b] = m->l_blk_idx[b];
+            hdp.ngen[b] = cnt + 1;
+            filt[b] = sampling_filters(sp, m->V);
+            if (!filt[b]) hdp.sample[b] = sp;
+            if (filt[b] || logits_out) hdp.logits[b] = m->samp_rows + (size_t)b * m->V;
+            if (filt[b]) {
+                const int j = sj.n++;
+                sj.logits[j] = gn >= 2 ? hdp.logits[b] : m->logits; sj.ngen[j] = cnt + 1;
+                sj.blk_val[j] = m->l_blk_val[b]; sj.blk_idx[j] = m->l_blk_idx[b]; sj.sample[j] = sp;
+            }
+        }
+        if (gn >= 2) {   // one pass over the table for the group: 97 us (four activation rows, always) against n x 70
+            VH_TRY(vhk_decb_lmhead(st, hv, m->final_norm, eps, m->lm_head, m->Vn, H, hdp, m->lm_grid, m->v0), "batched lm_head");
+        } else {
+            VH_TRY(vhk_dec_lmhead(st, x_in[g0], delta[g0], m->final_norm, eps, m->lm_head, m->Vn, H, m->logits, m->l_blk_val[0],
+                                  m->l_blk_idx[0], m->lm_grid, hdp.ngen[0], 1, m->v0, m->V, nullptr, &hdp.sample[0]), "lm_head");
+        }
+        if (logits_out)   // before the filter kernel's turn: it reads the rows, it does not change them
+            for (int b = 0; b < gn; ++b)
+                (void)hipMemcpyAsync(logits_out + (size_t)(g0 + b) * m->V, gn >= 2 ? hdp.logits[b] : m->logits, (size_t)m->V * sizeof(float),
+                                     hipMemcpyDeviceToDevice, st);
+        if (sj.n > 0) VH_TRY(vhk_dec_sample(st, sj), "sample");   // one workgroup per filtered sequence of the group
+        for (int b = 0; b < gn; ++b) {
+            const int sb = g0 + b;
+            int* cnt = m->seq_counters + 4 * ids[sb];
+            int nblk = filt[b] ? 1 : m->lm_grid;
+            const int keyed = m->seqs[ids[sb]].samp.T > 0.0 ? 1 : 0;
+            if (sharded && !filt[b]) {
+                nblk = m->c.tp_world;
+                const int rc = exchange_candidates(m, st, m->l_blk_val[b], m->l_blk_idx[b], m->l_cand[b], nblk, keyed);
+                if (rc != VH_OK) return rc;
+            }
+            VH_TRY(vhk_dec_select(st, m->l_blk_val[b], m->l_blk_idx[b], nblk, m->embed, H, m->V, m->seq_x + (size_t)ids[sb] * 4 * H, cnt, cnt + 1,
+                                  m->seq_tokens + (size_t)ids[sb] * (m->c.max_new > 0 ? m->c.max_new : 1), m->c.max_new, mode,
+                                  set_pos ? set_pos[sb] : 0, keyed), "select");
+        }
+    }
+    return VH_OK;
 }
 
 // One decode ITERATION of n concurrent sequences (n <= max_seqs, all distinct).  The attention side (fused QKV GEMV,
@@ -1402,11 +1575,9 @@ static int decode_iteration(vh_mixtral* m, hipStream_t st, const int* ids, int n
     const float eps = m->c.rms_eps;
     const bool tp = m->c.tp_world > 1 || vh_tuning()->force_allreduce;
     std::vector<float*> xa(n), xb(n), da(n), dm(n);
-    std::vector<int*> cnt(n);
     for (int b = 0; b < n; ++b) {
         float* x = m->seq_x + (size_t)ids[b] * 4 * H;
         xa[b] = x; xb[b] = x + H; da[b] = x + 2 * H; dm[b] = x + 3 * H;
-        cnt[b] = m->seq_counters + 4 * ids[b];
     }
     const int moe_min = vh_tuning()->batch_moe_min;
     const bool stream_moe = moe_min > 0 && n >= moe_min && n <= m->c.max_prefill && H <= 4096 && (H % 64) == 0 && (I % 64) == 0;
@@ -1477,48 +1648,9 @@ static int decode_iteration(vh_mixtral* m, hipStream_t st, const int* ids, int n
                 if (m->allreduce(dm[b], H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
         }
     }
-    const bool sharded = m->c.vocab_n > 0 && m->c.tp_world > 1;
-    for (int g0 = 0; g0 < n; g0 += VH_BMAX) {
-        const int gn = n - g0 < VH_BMAX ? n - g0 : VH_BMAX;
-        VhDecBatchVec hv{};
-        VhDecBatchHead hdp{};
-        VhDecSampleJob sj{};
-        bool filt[VH_BMAX] = {};
-        hv.n = gn;
-        sj.V = m->V; sj.hist_rows = 1;
-        for (int b = 0; b < gn; ++b) {
-            const VhSampleParams& sp = m->seqs[ids[g0 + b]].samp;
-            hv.x_in[b] = xa[g0 + b]; hv.delta[b] = dm[g0 + b];
-            hdp.blk_val[b] = m->l_blk_val[b]; hdp.blk_idx[b] = m->l_blk_idx[b];
-            hdp.ngen[b] = cnt[g0 + b] + 1;
-            filt[b] = sampling_filters(sp, m->V);
-            if (!filt[b]) hdp.sample[b] = sp;
-            else {
-                hdp.logits[b] = m->samp_rows + (size_t)b * m->V;
-                const int j = sj.n++;
-                sj.logits[j] = gn >= 2 ? hdp.logits[b] : m->logits; sj.ngen[j] = cnt[g0 + b] + 1;
-                sj.blk_val[j] = m->l_blk_val[b]; sj.blk_idx[j] = m->l_blk_idx[b]; sj.sample[j] = sp;
-            }
-        }
-        if (gn >= 2) {   // one pass over the table for the group: 97 us (four activation rows, always) against n x 70
-            VH_TRY(vhk_decb_lmhead(st, hv, m->final_norm, eps, m->lm_head, m->Vn, H, hdp, m->lm_grid, m->v0), "batched lm_head");
-        } else {
-            VH_TRY(vhk_dec_lmhead(st, xa[g0], dm[g0], m->final_norm, eps, m->lm_head, m->Vn, H, m->logits, m->l_blk_val[0],
-                                  m->l_blk_idx[0], m->lm_grid, cnt[g0] + 1, 1, m->v0, m->V, nullptr, &hdp.sample[0]), "lm_head");
-        }
-        if (sj.n > 0) VH_TRY(vhk_dec_sample(st, sj), "sample");   // one workgroup per filtered sequence of the group
-        for (int b = 0; b < gn; ++b) {
-            const int sb = g0 + b;
-            int nblk = filt[b] ? 1 : m->lm_grid;
-            const int keyed = m->seqs[ids[sb]].samp.T > 0.0 ? 1 : 0;
-            if (sharded && !filt[b]) {
-                nblk = m->c.tp_world;
-                const int rc = exchange_candidates(m, st, m->l_blk_val[b], m->l_blk_idx[b], m->l_cand[b], nblk, keyed);
-                if (rc != VH_OK) return rc;
-            }
-            VH_TRY(vhk_dec_select(st, m->l_blk_val[b], m->l_blk_idx[b], nblk, m->embed, H, m->V, xa[sb], cnt[sb], cnt[sb] + 1,
-                                  m->seq_tokens + (size_t)ids[sb] * (m->c.max_new > 0 ? m->c.max_new : 1), m->c.max_new, 1, 0, keyed), "select");
-        }
+    {
+        const int rc = batched_head(m, st, ids, n, xa.data(), dm.data(), /*mode=*/1, nullptr, nullptr);
+        if (rc != VH_OK) return rc;
     }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(VH_E_HIP, "batched decode: %s", hipGetErrorString(e));

@@ -575,7 +575,7 @@ __device__ __forceinline__ void fa_glds16(const unsigned char* base, uint32_t of
 template <int MODE, bool IMG, int RT>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void k_attn_fa(const VhAttnArgs p) {
-    constexpr bool CAUSAL = MODE >= 1, PAGED = MODE == 2;
+    constexpr bool CAUSAL = MODE >= 1, PAGED = MODE >= 2, SEG = MODE == 3;   // 3: causal + page tables, one SEGMENT (VhSeg) per batch coordinate
     constexpr int D = 128, NC = D / 16, VQ = NC / 4, C32 = D / 32;
     constexpr int PL = 64 * D * 2;                 // bytes of one plane of one 64-key tile
     constexpr int MGW = 8 + NC * 4;
@@ -589,11 +589,19 @@ void k_attn_fa(const VhAttnArgs p) {
     const int lr = lane & 15, lg = lane >> 4;
     int qx, hk, b;
     at_block_coords(p.xcd_map, qx, hk, b);                    // (y = KV head here: the blocks of a KV head share its tile images)
-    const int qb = (int)gridDim.x - 1 - qx;                   // heaviest (latest rows under the causal mask) blocks first
+    // SEG: batch coordinate = segment of the pass: its own query rows (from row row0 of Q / O), first position, key count and page
+    // table; the grid is as wide as the longest segment, the blocks past this segment's last query tile leave (block-uniform, before
+    // any barrier).  Nothing depends on which segment's blocks run first.
+    const int Sq = SEG ? p.segs[b].len : p.Sq, q_off = SEG ? p.segs[b].pos0 : p.q_off;
+    const int* const ktable = SEG ? p.segs[b].table : p.ktable;
+    const int qtiles = SEG ? (Sq + 16 * RT - 1) / (16 * RT) : (int)gridDim.x;
+    if (SEG && qx >= qtiles) return;
+    const size_t row0 = SEG ? (size_t)p.segs[b].row0 : (size_t)b * p.Sq;   // first row of the block's queries in the O planes
+    const int qb = qtiles - 1 - qx;                           // heaviest (latest rows under the causal mask) blocks first
     const int h = hk * 4 + rg, q0 = qb * 16 * RT;
-    const int qlast = min(q0 + 16 * RT, p.Sq) - 1;
+    const int qlast = min(q0 + 16 * RT, Sq) - 1;
 
-    const float* Qb = p.Q + (size_t)b * p.bsq + (size_t)h * p.hsq;
+    const float* Qb = p.Q + (SEG ? row0 * p.ldq : (size_t)b * p.bsq) + (size_t)h * p.hsq;
     const float* Kb = p.K + (size_t)b * p.bsk + (size_t)hk * p.hsk;
     const float* Vb = p.V + (size_t)b * p.bsk + (size_t)hk * p.hsv;
 
@@ -601,7 +609,7 @@ void k_attn_fa(const VhAttnArgs p) {
     bf16x8 qh[RT][C32], ql[RT][C32];
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt) {
-        const int q = min(q0 + 16 * rt + lr, p.Sq - 1);        // rows past Sq compute on a copy of the last row, never stored
+        const int q = min(q0 + 16 * rt + lr, Sq - 1);        // rows past Sq compute on a copy of the last row, never stored
 #pragma unroll
         for (int c = 0; c < C32; ++c) {
             const float* src = Qb + (size_t)q * p.ldq + 32 * c + 8 * lg;
@@ -609,8 +617,8 @@ void k_attn_fa(const VhAttnArgs p) {
         }
     }
 
-    const int kend = min(p.Sk, p.klen);
-    const int kloop = CAUSAL ? min(kend, qlast + p.q_off + 1) : kend;       // keys the block's rows can see
+    const int kend = SEG ? q_off + Sq : min(p.Sk, p.klen);
+    const int kloop = CAUSAL ? min(kend, qlast + q_off + 1) : kend;       // keys the block's rows can see
     const int ntiles = (kloop + 63) >> 6;
 
     float m[RT][4], l[RT][4];
@@ -631,7 +639,7 @@ void k_attn_fa(const VhAttnArgs p) {
     f32x4 st[8];
     auto row_of = [&](int key) __attribute__((always_inline)) {
         key = min(key, klast);
-        if (PAGED) key = p.ktable[key >> 6] * 64 + (key & 63);
+        if (PAGED) key = ktable[key >> 6] * 64 + (key & 63);
         return (unsigned)key;
     };
     // (Two parts each — K: keys 0-31 / 32-63 of the tile; V: columns 0-63 / 64-127.)  Ablations of the first form, conversion + LDS writes
@@ -741,7 +749,7 @@ void k_attn_fa(const VhAttnArgs p) {
                 __builtin_amdgcn_sched_barrier(0);
             }
             // ---- online softmax in D layout (the direct kernel's) --------------------------------------------------------------
-            const bool full_tile = kt0 + AT_KT <= (CAUSAL ? min(kend, q0 + p.q_off + 1) : kend);
+            const bool full_tile = kt0 + AT_KT <= (CAUSAL ? min(kend, q0 + q_off + 1) : kend);
             bf16x8 ph[RT], pl[RT];
 #pragma unroll
             for (int rt = 0; rt < RT; ++rt) {                        // (the wave's ONE patch serves its row tiles in turn: LDS executes a wave's operations in order)
@@ -751,7 +759,7 @@ void k_attn_fa(const VhAttnArgs p) {
                     const int q = q0 + 16 * rt + lg * 4 + r;
                     float s0v = sacc[rt][0][r], s1v = sacc[rt][1][r];
                     if (!full_tile) {
-                        const int klim = CAUSAL ? min(kend, q + p.q_off + 1) : kend;
+                        const int klim = CAUSAL ? min(kend, q + q_off + 1) : kend;
                         s0v = (kt0 + lr < klim) ? s0v : -INFINITY;
                         s1v = (kt0 + 16 + lr < klim) ? s1v : -INFINITY;
                     }
@@ -835,13 +843,13 @@ void k_attn_fa(const VhAttnArgs p) {
         }
     }
 
-    float* Ob = p.O ? p.O + (size_t)b * p.bso + (size_t)h * D : nullptr;
+    float* Ob = p.O ? p.O + (SEG ? row0 * p.ldo : (size_t)b * p.bso) + (size_t)h * D : nullptr;
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         const int q = q0 + 16 * rt + lg * 4 + r;
-        if (q >= p.Sq) continue;
+        if (q >= Sq) continue;
         const float inv = (l[rt][r] > 0.f) ? 1.0f / l[rt][r] : 0.f;
 #pragma unroll
         for (int j = 0; j < VQ; ++j) {
@@ -851,7 +859,7 @@ void k_attn_fa(const VhAttnArgs p) {
                 uint32_t hi[2], lo[2];
                 at_split2(v[0], v[1], hi[0], lo[0]);
                 at_split2(v[2], v[3], hi[1], lo[1]);
-                const size_t at = ((size_t)b * p.Sq + q) * p.ldo_split + (size_t)h * D + lr * NC + 4 * j;
+                const size_t at = (row0 + q) * p.ldo_split + (size_t)h * D + lr * NC + 4 * j;
                 *reinterpret_cast<uint2*>(p.O_hi + at) = make_uint2(hi[0], hi[1]);
                 *reinterpret_cast<uint2*>(p.O_lo + at) = make_uint2(lo[0], lo[1]);
             }
@@ -869,10 +877,53 @@ int vhk_attn_fa_applies(const VhAttnArgs& a) {
     return (vh_tuning()->attn_fa == 2 || blocks * 2 >= vh_num_cus()) ? 1 : 0;
 }
 
+// Segments of several paged sequences in one call (VhAttnArgs::segs): the flash kernel takes them all in ONE launch when the blocks
+// of all segments together fill half the chip (or attn_fa = 2); any other geometry runs the kernel vhk_attn picks for a segment alone,
+// once per segment.
+static int attn_segments(hipStream_t st, const VhAttnArgs& a) {
+    if (!a.segs || !a.segs_host || !a.causal || a.B != 1 || a.P || a.chunk > 0 || !a.K || !a.V || !a.Q) return -1;
+    long blocks = 0;
+    int max_tiles = 0, rows = 0;
+    for (int i = 0; i < a.nseg; ++i) {
+        const VhSeg& g = a.segs_host[i];
+        if (g.len < 1 || g.pos0 < 0 || g.row0 != rows || !g.table) return -1;     // back to back, in order
+        rows += g.len;
+        const int tiles = (g.len + 15) / 16;
+        blocks += (long)tiles * a.Hkv;
+        if (tiles > max_tiles) max_tiles = tiles;
+    }
+    if (rows != a.Sq) return -1;
+    auto al16 = [](const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; };
+    const long pool = a.kv_rows > 0 ? a.kv_rows : (1L << 24), ldmax = a.ldk > a.ldv ? a.ldk : a.ldv;
+    const int fa = vh_tuning()->attn_fa;
+    const bool fa_ok = vh_tuning()->attn_impl == 0 && fa != 0 && a.d == 128 && a.Hq == 4 * a.Hkv && al16(a.Q) && al16(a.K) && al16(a.V) &&
+                       al16(a.O) && (!a.O_hi || (a.O_lo && (a.ldo_split % 4) == 0 && al16(a.O_hi) && al16(a.O_lo))) && (a.O || a.O_hi) &&
+                       ((a.ldq | a.hsq | a.ldk | a.hsk | a.ldv | a.hsv | a.ldo) % 4) == 0 &&
+                       pool < (1L << 24) && ldmax > 0 && ldmax < (1L << 24) && (pool * ldmax + a.d) * 4 < (1L << 32);
+    if (fa_ok && (fa == 2 || blocks * 2 >= vh_num_cus())) {
+        hipLaunchKernelGGL((k_attn_fa<3, false, 1>), dim3(max_tiles, a.Hkv, a.nseg), dim3(512), 0, st, a);
+        return 0;
+    }
+    for (int i = 0; i < a.nseg; ++i) {
+        const VhSeg& g = a.segs_host[i];
+        VhAttnArgs s = a;
+        s.segs = nullptr; s.segs_host = nullptr; s.nseg = 0;
+        s.Q = a.Q + (size_t)g.row0 * a.ldq;
+        if (a.O) s.O = a.O + (size_t)g.row0 * a.ldo;
+        if (a.O_hi) { s.O_hi = a.O_hi + (size_t)g.row0 * a.ldo_split; s.O_lo = a.O_lo + (size_t)g.row0 * a.ldo_split; }
+        s.Sq = g.len; s.q_off = g.pos0; s.Sk = g.pos0 + g.len; s.klen = s.Sk; s.ktable = g.table;
+        s.kv_img = nullptr; s.img_tiles = 0;
+        const int rc = vhk_attn(st, s);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+
 int vhk_attn(hipStream_t st, const VhAttnArgs& a_in) {
     VhAttnArgs a = a_in;
     a.xcd_map = vh_tuning()->attn_xcd != 0 ? 1 : 0;
     if (a.Sq <= 0 || a.Sk <= 0 || a.Hq % a.Hkv != 0) return -1;
+    if (a.nseg > 0) return attn_segments(st, a);
     const bool rel = a.P != nullptr;
     const int want = vh_tuning()->attn_ksplit;
     const int kl = a.klen < a.Sk ? a.klen : a.Sk;

@@ -315,18 +315,30 @@ __global__ void k_audio_conv1(const float* __restrict__ feats, const float* __re
 
 // ---- Mixtral prefill: rotate-half RoPE on q,k and KV-cache write ------------------------
 // qkv rows: [q (nq*128) | k (nkv*128) | v (nkv*128)]; token s sits at position pos0+s.
+// SEG: the rows belong to nseg segments of different paged sequences (VhSeg, row0 ascending): the row's segment is found by
+// bisection, its position is pos0 + (row - row0) and its page table the segment's.
+template <bool SEG>
 __global__ void k_rope_kv(const float* __restrict__ qkv, long ldqkv, float* __restrict__ q_out,
                           float* __restrict__ kcache, float* __restrict__ vcache,
                           const float* __restrict__ rope_cos, const float* __restrict__ rope_sin, int S, int pos0,
                           int nq, int nkv, int max_ctx, const int* __restrict__ table,
-                          const int* __restrict__ nslab_dev, long slab_stride) {
+                          const int* __restrict__ nslab_dev, long slab_stride, const VhSeg* __restrict__ segs, int nseg) {
     const int nh = nq + 2 * nkv;
     const long total = (long)S * nh * 64;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int d = (int)(i & 63);
         const int hh = (int)((i >> 6) % nh);
         const int s = (int)(i / ((long)nh * 64));
-        const int pos = pos0 + s;
+        int pos = pos0 + s;
+        if (SEG) {
+            int lo = 0, hi = nseg - 1;                     // last segment whose row0 <= s
+            while (lo < hi) {
+                const int mid = (lo + hi + 1) >> 1;
+                if (segs[mid].row0 <= s) lo = mid; else hi = mid - 1;
+            }
+            pos = segs[lo].pos0 + (s - segs[lo].row0);
+            table = segs[lo].table;
+        }
         const int row = table ? table[pos >> 6] * 64 + (pos & 63) : pos;   // paged KV cache: physical row of this position
         const float* src = qkv + (size_t)s * ldqkv + hh * 128;
         float a = src[d], bq = src[d + 64];
@@ -716,8 +728,19 @@ int vhk_rope_kv(hipStream_t st, const float* qkv, long ldqkv, float* q_out, floa
                 const float* rope_cos, const float* rope_sin, int S, int pos0, int nq, int nkv, int max_ctx,
                 const int* table, const int* nslab_dev, long slab_stride) {
     if (S == 0) return 0;
-    hipLaunchKernelGGL(k_rope_kv, dim3(grid_for((long)S * (nq + 2 * nkv) * 64, 256)), dim3(256), 0, st, qkv, ldqkv,
-                       q_out, kcache, vcache, rope_cos, rope_sin, S, pos0, nq, nkv, max_ctx, table, nslab_dev, slab_stride);
+    hipLaunchKernelGGL(k_rope_kv<false>, dim3(grid_for((long)S * (nq + 2 * nkv) * 64, 256)), dim3(256), 0, st, qkv, ldqkv,
+                       q_out, kcache, vcache, rope_cos, rope_sin, S, pos0, nq, nkv, max_ctx, table, nslab_dev, slab_stride,
+                       (const VhSeg*)nullptr, 0);
+    return 0;
+}
+int vhk_rope_kv_segs(hipStream_t st, const float* qkv, long ldqkv, float* q_out, float* kcache, float* vcache,
+                     const float* rope_cos, const float* rope_sin, int S, const VhSeg* segs, int nseg, int nq, int nkv,
+                     int max_ctx, const int* nslab_dev, long slab_stride) {
+    if (S == 0) return 0;
+    if (!segs || nseg < 1) return -1;
+    hipLaunchKernelGGL(k_rope_kv<true>, dim3(grid_for((long)S * (nq + 2 * nkv) * 64, 256)), dim3(256), 0, st, qkv, ldqkv,
+                       q_out, kcache, vcache, rope_cos, rope_sin, S, 0, nq, nkv, max_ctx, (const int*)nullptr, nslab_dev,
+                       slab_stride, segs, nseg);
     return 0;
 }
 int vhk_rope_kv_img(hipStream_t st, const float* qkv, long ldqkv, float* q_out, float* kcache, float* vcache,

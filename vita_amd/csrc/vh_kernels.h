@@ -244,6 +244,14 @@ int vhk_quant_rows_i8(hipStream_t st, const uint16_t* w, long rows, int cols, lo
 int vhk_split_planes(hipStream_t st, const float* x, long ldx, uint16_t* hi, uint16_t* lo, long ldo, int rows,
                      int cols);
 
+// ---- rows of several sequences in one prefill pass (vh_mixtral_seq_prefill_batch) ----------------------------
+// Segment i of the pass: rows [row0, row0 + len) are the tokens at positions [pos0, pos0 + len) of ONE sequence whose KV pages
+// `table` lists (device int[], 64-token pages).  Everything row-wise ignores the segments; RoPE + KV write and attention read them.
+struct VhSeg {
+    int row0, len, pos0, pad_;
+    const int* table;
+};
+
 // ---- attention (vh_attn.hip) --------------------------------------------------------
 struct VhAttnArgs {
     const float* Q; long ldq; long hsq;   // Q[(b*Sq + q)*ldq + h*hsq + d]   (b strides below)
@@ -267,6 +275,11 @@ struct VhAttnArgs {
     // causal prefills (q_off == 0, Sk == Sq, B == 1); ignored otherwise (K / V must always be valid too).
     const unsigned char* kv_img; int img_tiles;
     int xcd_map;                          // set by vhk_attn (vh_tune "attn_xcd"): block -> (q tile, head, batch) with all q tiles of a head on one XCD
+    // optional: causal attention of `nseg` segments of DIFFERENT paged sequences in one call (B = 1, causal, Q / O rows in pass order;
+    // Sq = rows of the pass).  Segment i replaces Sq / q_off / klen / Sk / ktable by len / pos0 / pos0 + len / its table and starts at
+    // row row0.  segs: device array (the flash kernel takes the segment from the block's batch coordinate); segs_host: the same on the
+    // host (sizes the grid; kernels without a segmented form are launched once per segment).
+    const VhSeg* segs; const VhSeg* segs_host; int nseg;
 };
 int vhk_attn(hipStream_t st, const VhAttnArgs& a);
 int vhk_attn_fa_applies(const VhAttnArgs& a);    // 1 when vhk_attn would run the flash kernel (k_attn_fa) for these arguments
@@ -286,6 +299,10 @@ int vhk_audio_conv1(hipStream_t st, const float* feats, const float* mean, const
 int vhk_rope_kv(hipStream_t st, const float* qkv, long ldqkv, float* q_out, float* kcache, float* vcache,
                 const float* rope_cos, const float* rope_sin, int S, int pos0, int nq, int nkv, int max_ctx,
                 const int* table, const int* nslab_dev, long slab_stride);   // nslab_dev: qkv is *nslab_dev partial slabs
+// the same for the S rows of nseg segments (device descriptors): row -> (segment, position, physical page row) by lookup
+int vhk_rope_kv_segs(hipStream_t st, const float* qkv, long ldqkv, float* q_out, float* kcache, float* vcache,
+                     const float* rope_cos, const float* rope_sin, int S, const VhSeg* segs, int nseg, int nq, int nkv,
+                     int max_ctx, const int* nslab_dev, long slab_stride);
 // the same for a one-shot prefill (positions 0 .. S-1) whose attention is the flash kernel: additionally writes the K / V tile images
 // (VhAttnArgs::kv_img) — one block per (64-row tile, KV head) converts the tile once, where it is produced (nq == 4 * nkv)
 int vhk_rope_kv_img(hipStream_t st, const float* qkv, long ldqkv, float* q_out, float* kcache, float* vcache,

@@ -270,6 +270,26 @@ class MixtralEngine:
               "vh_mixtral_seq_prefill")
         return self.gather_vocab(out) if out is not None else None
 
+    def seq_prefill_batch(self, seqs, embeds_list, want_logits=False):
+        """seq_prefill for several distinct sequences in ONE pass over the weights (vh_mixtral_seq_prefill_batch): embeds_list[i]
+        [S_i, hidden] is appended to sequence seqs[i]; the rows of all of them together must fit max_prefill.  want_logits: the
+        [len(seqs), vocab] rows of the segments' last positions.  The call is checked as a whole before anything is enqueued: a
+        VitaHipError raised for a bad list or a full pool leaves every sequence and the pool as they were."""
+        if len(seqs) != len(embeds_list) or len(seqs) < 1:
+            raise ValueError("seq_prefill_batch: one embeds tensor per sequence, at least one")
+        for e in embeds_list:
+            if e.dtype != torch.float32 or not e.is_cuda or e.dim() != 2:
+                raise TypeError("embeds must be float32 GPU tensors [S, hidden]")
+        n = len(seqs)
+        embeds = embeds_list[0].contiguous() if n == 1 else torch.cat(list(embeds_list), dim=0)
+        ids = (C.c_int * n)(*[int(x) for x in seqs])
+        lens = (C.c_int * n)(*[int(e.shape[0]) for e in embeds_list])
+        out = torch.empty((n, self.c.vocab), dtype=torch.float32, device=self.device) if want_logits else None
+        check(self.lib.vh_mixtral_seq_prefill_batch(self.h, ids, lens, n, embeds.data_ptr(),
+                                                    out.data_ptr() if out is not None else None, self._stream()),
+              "vh_mixtral_seq_prefill_batch")
+        return self.gather_vocab(out) if out is not None else None
+
     def seq_decode(self, seqs):
         """one greedy step for every listed sequence (one continuous-batching iteration)."""
         arr = (C.c_int * len(seqs))(*[int(x) for x in seqs])

@@ -323,7 +323,9 @@ class ContinuousBatcher:
       add(request_id, embeds, max_tokens, eos)   queue a request (FIFO)
       step() -> [(request_id, new_token_ids, finished, finish_reason)]   one iteration:
           1. admit waiting requests while a sequence slot is free and the pool holds the prompt's pages plus one page of
-             headroom per running sequence (prefill is one C call per admitted request);
+             headroom per running sequence; the admitted prompts are then prefilled in groups of up to max_prefill rows, a
+             group of two or more in ONE pass over the weights (seq_prefill_batch: vLLM's max_num_batched_tokens), a
+             group of one — or a re-prompt longer than max_prefill, in chunks — by seq_prefill;
           2. if the running sequences need more new pages than the pool has, preempt the youngest ones (free their pages,
              re-queue them at the front with prompt + generated tokens as the new prompt: vLLM's recompute preemption);
           3. `window` greedy decode steps for every running sequence (one C call per step), ONE host synchronisation,
@@ -342,7 +344,7 @@ class ContinuousBatcher:
         self.waiting = collections.deque()
         self.running = []                 # admission order
         self.errors = {}                  # request id -> exception of a request that failed alone (event reason "error")
-        self.stats = {"iterations": 0, "prefills": 0, "preemptions": 0, "decode_steps": 0, "failed": 0}
+        self.stats = {"iterations": 0, "prefills": 0, "prefill_calls": 0, "preemptions": 0, "decode_steps": 0, "failed": 0}
 
     def add(self, request_id, embeds, max_tokens, eos=(), sampling=None):
         """sampling: None (greedy) or the keywords of MixtralEngine.seq_set_sampling without draw0 (see sampling_of)."""
@@ -377,6 +379,7 @@ class ContinuousBatcher:
         emb, mp = r["emb"], int(self.eng.max_prefill)
         for s0 in range(0, int(emb.shape[0]), mp):
             self.eng.seq_prefill(r["seq"], emb[s0:s0 + mp])
+            self.stats["prefill_calls"] += 1
 
     def _fail(self, r, exc, events):
         """ONE request failed (its prompt does not fit, its prefill was rejected): it ends with an "error" event, nobody else
@@ -385,16 +388,52 @@ class ContinuousBatcher:
         self.stats["failed"] += 1
         events.append((r["id"], [], True, "error"))
 
+    def _start(self, r, events, prefilled=False):
+        """r holds a slot: prefill it (unless a group call already did) and let it run; a failure ends r alone."""
+        if not prefilled:
+            try:
+                self._prefill(r)
+            except Exception as e:
+                self.eng.seq_free(r["seq"])
+                r["seq"] = None
+                self._fail(r, e, events)
+                return
+        r["fresh"] = True                    # its first token (tokens[0]) is not reported yet
+        self.running.append(r)
+        self.stats["prefills"] += 1
+
+    def _prefill_group(self, group, events):
+        """the admitted requests of one group, in admission order: two or more in one pass over the weights.  A group call that
+        raises is retried request by request (a rejected call touched nothing; after a later failure seq_prefill starts again
+        at the sequence's unchanged position), so only the culprit ends with an "error" event."""
+        done = False
+        if len(group) >= 2:
+            try:
+                self.eng.seq_prefill_batch([r["seq"] for r in group], [r["emb"] for r in group])
+                self.stats["prefill_calls"] += 1
+                done = True
+            except Exception:
+                done = False
+        for r in group:
+            self._start(r, events, prefilled=done)
+        group.clear()
+
     def _admit(self):
         events = []
-        while self.waiting and len(self.running) < self.max_batch:
+        mp = int(self.eng.max_prefill)
+        can_batch = hasattr(self.eng, "seq_prefill_batch")
+        group, rows = [], 0       # admitted (slot taken, pages promised), prefill deferred to the group's call
+        while self.waiting and len(self.running) + len(group) < self.max_batch:
             r = self.waiting[0]
-            need = self._pages(r["emb"].shape[0] + 1) + len(self.running)       # + one page of headroom per runner
-            if need > self.eng.pages_free():
-                if not self.running:
+            # the pool as it will be once the group is prefilled: the pages promised to its prompts are gone, its members run
+            free = self.eng.pages_free() - sum(self._pages(g["emb"].shape[0]) for g in group)
+            n_run = len(self.running) + len(group)
+            need = self._pages(r["emb"].shape[0] + 1) + n_run                   # + one page of headroom per runner
+            if need > free:
+                if n_run == 0:
                     self.waiting.popleft()
                     self._fail(r, RuntimeError(f"request {r['id']}: prompt needs {need} KV pages, the pool has "
-                                               f"{self.eng.pages_free()}"), events)
+                                               f"{free}"), events)
                     continue
                 break
             self.waiting.popleft()
@@ -413,16 +452,18 @@ class ContinuousBatcher:
                     r["seq"] = None
                     self._fail(r, e, events)
                     continue
-            try:
-                self._prefill(r)
-            except Exception as e:
-                self.eng.seq_free(r["seq"])
-                r["seq"] = None
-                self._fail(r, e, events)
+            S = int(r["emb"].shape[0])
+            if not can_batch or S > mp:          # no batched entry point / a re-prompt that goes in chunks: alone, in order
+                self._prefill_group(group, events)
+                rows = 0
+                self._start(r, events)
                 continue
-            r["fresh"] = True                    # its first token (tokens[0]) is not reported yet
-            self.running.append(r)
-            self.stats["prefills"] += 1
+            if rows + S > mp:                    # the next prompt would take the group's rows past max_prefill: close it
+                self._prefill_group(group, events)
+                rows = 0
+            group.append(r)
+            rows += S
+        self._prefill_group(group, events)
         return events
 
     def _preempt_for(self, steps):
