@@ -2,9 +2,17 @@
 """bench.py — BASELINE.json's metric on MI355X: greedy-decode tokens/s (+ prefill / encoder ms) of the
 VITA-Mixtral-8x7B geometry on a 1 image + 10 s audio + text prompt, tensor-parallel over N GPUs.
 
-  python bench.py --gpus 1 --steps 64 --warmup 8
+  python bench.py --gpus 1 --steps 64 --warmup 8            the headline figure and nothing else
+  python bench.py --gpus 1 --steps 64 --warmup 8 --full     ... and everything else this file measures
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-         bench.py --gpus N --steps K --warmup W
+         bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does only what `value` needs: it builds the model, runs ONE encoder + prefill pass (the KV cache the decode
+steps read), W warm-up steps and the K timed steps, writes --dump-outputs and prints the line (`metric`, `value`,
+`ms_per_step`, the decode `roofline` sampled inside the timed steps, `gpu_state` of the decode phase).  --full adds the
+legs that take runs of their own, after and around the same timed steps: repeated encoder / prefill passes (`prefill_ms`,
+`ttft_ms`, `phase_min_ms`, `gpu_state` of the prefill), `roofline_prefill`, the demo's generate() call, --batch and
+`cpu_baseline`.  The timed steps, their inputs and `value` are the same in both.
 
 A "step" is one greedy decode step (one pass of the decode hot path over the whole model for one
 token).  Warm-up steps are untimed; exactly K steps are timed between barrier + synchronize pairs,
@@ -12,7 +20,7 @@ inputs (weights, KV cache, prompt) resident in HBM; value = K / max-over-ranks t
 ONE JSON line.  Data and weights are synthetic (no checkpoint offline): weights of the released geometry from the
 counter-based hash generator (vh_fill_hash_bf16 / oracle/hashw.py: sums of four 6-bit fields, ~N(0, 0.018^2), exact in
 bf16, the same bits on the device and in the CPU oracle), a random 448x448 image, a seeded 10 s waveform, random prompt
-ids.  Next to `value` (the engine's decode loop, no host work inside the timed region) the line carries
+ids.  Next to `value` (the engine's decode loop, no host work inside the timed region) the --full line carries
 `generate_tokens_per_s`: the reference demo's own call — model.generate(..., stopping_criteria=[KeywordsStoppingCriteria])
 (video_audio_demo.py:257-270) — timed end to end, and `gpu_state`: shader clock / socket power sampled while the prefill
 and decode phases run (prefill time moves by up to 30 % from box to box at identical code: profiles/r03_layout_box_*.jsonl)."""
@@ -334,10 +342,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=8)
-    ap.add_argument("--phase-warmup", type=int, default=2, help="untimed encoder+prefill passes")
-    ap.add_argument("--phase-iters", type=int, default=7, help="timed encoder+prefill passes (median and min reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything that is not the headline figure: timed encoder + prefill passes, the prefill kernel's "
+                         "roofline, the demo's generate() call, --batch and the CPU baseline (a plain run only times the decode steps)")
+    ap.add_argument("--phase-warmup", type=int, default=None, help="with --full: untimed encoder+prefill passes (default 2)")
+    ap.add_argument("--phase-iters", type=int, default=None,
+                    help="with --full: timed encoder+prefill passes (median and min reported; default 7)")
     ap.add_argument("--layers", type=int, default=0, help="debug only: fewer layers (result marked invalid)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out (a plain run has none)")
     ap.add_argument("--collective", default="auto", choices=["auto", "ipc", "rccl", "torch"],
                     help="auto = the library's IPC all-reduce, else native RCCL, else torch.distributed (ranks agree)")
     ap.add_argument("--launch-check", action="store_true",
@@ -364,7 +376,7 @@ def main():
                     help="debug: number of 448x448 tiles / video frames in the prompt (default 1 = configs[2]; 4-16 is the "
                          "video shape of configs[4])")
     ap.add_argument("--text-tokens", type=int, default=32, help="debug: length of the user text (default 32 = configs[2])")
-    ap.add_argument("--batch", default="", help="also measure B concurrent sequences over the paged KV cache, e.g. 2,4 "
+    ap.add_argument("--batch", default="", help="with --full: also measure B concurrent sequences over the paged KV cache, e.g. 2,4 "
                     "(SURVEY 8(f)#1; reported under \"concurrent\", the headline value stays batch 1)")
     ap.add_argument("--tune", default="", help="debug: kernel-variant knobs key=val[,key=val] (vh_tune)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
@@ -372,6 +384,13 @@ def main():
                          "scores of the last step — as DIR/<name>.npy (float64 / float32); the inputs are seeded, so two builds "
                          "compare output for output")
     args = ap.parse_args()
+    if not args.full:
+        moved = [f for f, given in (("--batch", args.batch), ("--phase-iters", args.phase_iters is not None),
+                                    ("--phase-warmup", args.phase_warmup is not None)) if given]
+        if moved:
+            ap.error(f"{', '.join(moved)}: measured only with --full")
+    args.phase_warmup = 2 if args.phase_warmup is None else args.phase_warmup
+    args.phase_iters = 7 if args.phase_iters is None else args.phase_iters
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -495,32 +514,44 @@ def main():
                               "prefill_ms": e[3].elapsed_time(e[4]), "n_audio_tokens": int(aud["inputs_embeds"].shape[1])}
 
     gpu_state = GpuStateSampler(local_rank)
-    for _ in range(max(1, args.phase_warmup)):                         # warm-up of the encoder + prefill path
-        S, _ = encode_and_prefill()
-    gpu_state.start("prefill_phase")
-    runs = [encode_and_prefill()[1] for _ in range(max(1, args.phase_iters))]
-    gpu_state.stop()
-    if gpu_state.files and not args.layers:
-        # clock / power settle over hundreds of ms (and the hwmon power is a moving average): keep the prefill running for
-        # ~1.5 s and keep only what was sampled in the second half — the state the timed prefill passes converge to
-        gpu_state.start("prefill_steady")
-        t_end = time.perf_counter() + 1.5
-        while time.perf_counter() < t_end:
-            eng.prefill(emb_last)
-            torch.cuda.synchronize()
+
+    def measure_phases():
+        """--full: the encoder + prefill passes timed (median / min of --phase-iters), clock and power while they run, and the
+        dominant prefill kernel against the roofline.  Every pass prefills the same prompt, so the KV cache it leaves the decode
+        steps is the one a single pass leaves."""
+        for _ in range(max(1, args.phase_warmup)):                     # warm-up of the encoder + prefill path
+            S, _ = encode_and_prefill()
+        gpu_state.start("prefill_phase")
+        runs = [encode_and_prefill()[1] for _ in range(max(1, args.phase_iters))]
         gpu_state.stop()
-        buf = gpu_state.samples["prefill_steady"]
-        del buf[:len(buf) // 2]
-    # the dominant PREFILL kernel (MoE gate|up grouped GEMM), timed live with HIP events the engine records on its own stream
-    # around each of the layers' launches (the prefill half of the metric recomputable from this line alone)
-    eng.profile(stride=-1, max_samples=4 * t.num_hidden_layers + 8)
-    for _ in range(3):
-        eng.prefill(emb_last)
-    torch.cuda.synchronize()
-    pf_ms, pf_n = eng.profile_read()
-    eng.profile(stride=0)
-    phase = {k: float(np.median([r[k] for r in runs])) for k in ("vit_proj_ms", "audio_ms", "encode_ms", "prefill_ms")}
-    phase_min = {k: float(min(r[k] for r in runs)) for k in ("vit_proj_ms", "audio_ms", "encode_ms", "prefill_ms")}
+        if gpu_state.files and not args.layers:
+            # clock / power settle over hundreds of ms (and the hwmon power is a moving average): keep the prefill running for
+            # ~1.5 s and keep only what was sampled in the second half — the state the timed prefill passes converge to
+            gpu_state.start("prefill_steady")
+            t_end = time.perf_counter() + 1.5
+            while time.perf_counter() < t_end:
+                eng.prefill(emb_last)
+                torch.cuda.synchronize()
+            gpu_state.stop()
+            buf = gpu_state.samples["prefill_steady"]
+            del buf[:len(buf) // 2]
+        # the dominant PREFILL kernel (MoE gate|up grouped GEMM), timed live with HIP events the engine records on its own stream
+        # around each of the layers' launches (VERDICT r03 #8: the prefill half of the metric recomputable from this line alone)
+        eng.profile(stride=-1, max_samples=4 * t.num_hidden_layers + 8)
+        for _ in range(3):
+            eng.prefill(emb_last)
+        torch.cuda.synchronize()
+        pf_ms, pf_n = eng.profile_read()
+        eng.profile(stride=0)
+        return S, runs, pf_ms, pf_n
+
+    if args.full:
+        S, runs, pf_ms, pf_n = measure_phases()
+        phase = {k: float(np.median([r[k] for r in runs])) for k in ("vit_proj_ms", "audio_ms", "encode_ms", "prefill_ms")}
+        phase_min = {k: float(min(r[k] for r in runs)) for k in ("vit_proj_ms", "audio_ms", "encode_ms", "prefill_ms")}
+    else:
+        S, run = encode_and_prefill()                                  # one pass: the prompt's KV cache, nothing timed
+        runs = [run]
     assert runs[-1]["n_audio_tokens"] == n_aud_tok                     # the last run's KV cache feeds the decode below
 
     def barrier():
@@ -557,7 +588,7 @@ def main():
 
     # ---- the demo's own call: model.generate() with the keyword stopping criterion, end to end ------------------------------
     gen = None
-    if not args.emulate_tp:
+    if args.full and not args.emulate_tp:
         from vita_amd.host.prompt import KeywordsStoppingCriteria
         n_new = K + Wm                                                   # fits the engine's max_new (K + Wm + 8)
         crit = KeywordsStoppingCriteria(["</s>"], _BenchTokenizer(), input_ids)
@@ -630,12 +661,11 @@ def main():
                                                     t.num_local_experts * 3 * I_r * t.hidden_size)
                         + 2 * packed["lm_head"].numel())               # all experts are touched at S >> 8
 
-    rf_prefill = prefill_kernel_roofline(int(S), t.num_local_experts, I_r, t.hidden_size, t.num_hidden_layers, pf_ms, pf_n, world)
     if rank == 0:
         out = {
             "metric": "decode_tokens_per_s", "value": round(tok_s, 3), "unit": "tokens/s", "n_gpus": world,
             "steps": K, "warmup": Wm, "ms_per_step": round(ms_step, 4), "host_enqueue_ms_per_step": round(t_host * 1e3 / K, 4),
-            "higher_is_better": True,
+            "higher_is_better": True, "full": args.full,
             "scaling": "strong", "vs_baseline": None, "dtype": "bf16 weights, f32 activations/accumulate",
             "data": "synthetic",
             "config": {"workload": ("BASELINE configs[2]: 1 image (448x448, 1 tile -> 256 tokens)" if args.frames == 1 else
@@ -649,19 +679,6 @@ def main():
                        # and O rows as work items with granule hand-offs), "three-launches" = QKV, attention, O projection
                        "decode_schedule": eng.decode_schedule(),
                        "launches_per_layer": 3 if eng.decode_schedule() == "fused-attention-block" else 5},
-            "prefill_ms": round(phase["prefill_ms"], 3), "vit_projector_ms": round(phase["vit_proj_ms"], 3),
-            "audio_encoder_ms": round(phase["audio_ms"], 3),
-            # time to first token of one request: encoders (concurrent) + projector + splice, then the prefill; `ttft_serial_ms` is the
-            # r01-r05 definition (each tower timed alone, summed, splice not counted)
-            "encode_ms": round(phase["encode_ms"], 3),
-            "ttft_ms": round(phase["prefill_ms"] + phase["encode_ms"], 3),
-            "ttft_serial_ms": round(phase["prefill_ms"] + phase["vit_proj_ms"] + phase["audio_ms"], 3),
-            "phase_min_ms": {k: round(v, 3) for k, v in phase_min.items()}, "phase_iters": len(runs),
-            "prefill_roofline": {"bound": "hbm", "algorithmic_bytes": prefill_bytes,
-                                 "floor_ms": round(prefill_bytes / HBM_PEAK_GBPS / 1e6, 3),
-                                 "frac": round(prefill_bytes / HBM_PEAK_GBPS / 1e6 / phase["prefill_ms"], 4),
-                                 "note": "every expert is touched at this S: all backbone weights read once per rank "
-                                         "(SURVEY 8(d)); MFMA floor is lower"},
             "decode_effective_GBps_per_gpu": round(eff, 1),
             "decode_effective_frac_of_8TBps": round(eff / HBM_PEAK_GBPS, 4),
             "roofline": {"bound": "hbm", "kernel": "k_dec_gateup (router + gate|up GEMV of the 2 routed experts)",
@@ -677,10 +694,27 @@ def main():
                          "traffic": pmc_traffic("k_dec_gateup") if world == 1 else None,
                          "traffic_source": (f"{traffic_source()} (static: rocprofv3 --pmc FETCH_SIZE pass of this kernel, "
                                             "counters cannot be read inside this process)") if world == 1 else None},
-            "roofline_prefill": rf_prefill,
             "gpu_state": gpu_state.summary(),
             "build_s": round(t_build, 1),
         }
+        if args.full:
+            out.update({
+                "prefill_ms": round(phase["prefill_ms"], 3), "vit_projector_ms": round(phase["vit_proj_ms"], 3),
+                "audio_encoder_ms": round(phase["audio_ms"], 3),
+                # time to first token of one request: encoders (concurrent) + projector + splice, then the prefill; `ttft_serial_ms` is the
+                # r01-r05 definition (each tower timed alone, summed, splice not counted)
+                "encode_ms": round(phase["encode_ms"], 3),
+                "ttft_ms": round(phase["prefill_ms"] + phase["encode_ms"], 3),
+                "ttft_serial_ms": round(phase["prefill_ms"] + phase["vit_proj_ms"] + phase["audio_ms"], 3),
+                "phase_min_ms": {k: round(v, 3) for k, v in phase_min.items()}, "phase_iters": len(runs),
+                "prefill_roofline": {"bound": "hbm", "algorithmic_bytes": prefill_bytes,
+                                     "floor_ms": round(prefill_bytes / HBM_PEAK_GBPS / 1e6, 3),
+                                     "frac": round(prefill_bytes / HBM_PEAK_GBPS / 1e6 / phase["prefill_ms"], 4),
+                                     "note": "every expert is touched at this S: all backbone weights read once per rank "
+                                             "(SURVEY 8(d)); MFMA floor is lower"},
+                "roofline_prefill": prefill_kernel_roofline(int(S), t.num_local_experts, I_r, t.hidden_size, t.num_hidden_layers,
+                                                            pf_ms, pf_n, world),
+            })
         if gen:
             out["generate_tokens_per_s"] = gen["tokens_per_s_after_first_token"]
             out["generate"] = gen
@@ -701,7 +735,7 @@ def main():
             out["OTHER_WORKLOAD_frames"] = args.frames      # not the metric's configuration: video-shaped prompt
         if args.one_device or args.backend != "nccl":
             out["INVALID_debug_backend"] = f"{args.backend}, one_device={args.one_device}"
-        if not args.no_cpu_baseline and world == 1:   # the CPU leg is timed once, at N=1 (torchrun also pins OMP to 1 thread)
+        if args.full and not args.no_cpu_baseline and world == 1:   # the CPU leg is timed once, at N=1 (torchrun also pins OMP to 1 thread)
             try:
                 out["cpu_baseline"] = cpu_baseline(VitaConfig(), ctx=int(S), request=req)
             except Exception as e:  # never lose the GPU line to a host-side problem

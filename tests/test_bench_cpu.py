@@ -111,6 +111,20 @@ def test_bench_self_launches_its_ranks():
     assert j["launch_check"] and j["n_gpus"] == 2 and j["allreduce_sum"] == j["expected"] == 3.0
 
 
+def test_bench_full_option_gates_what_is_not_the_headline():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times the decode steps only; whatever else the bench measures sits behind
+    --full.  The option exists, and the options that ask for a moved leg are refused without it (at argument parsing, before
+    any device is touched) rather than silently ignored."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    bench = [sys.executable, os.path.join(root, "bench.py")]
+    h = subprocess.run(bench + ["--help"], capture_output=True, text=True, timeout=300)
+    assert h.returncode == 0 and "--full" in h.stdout, h.stderr[-2000:]
+    for extra in (["--batch", "2"], ["--phase-iters", "3"], ["--phase-warmup", "1"]):
+        r = subprocess.run(bench + ["--gpus", "1", "--steps", "2", "--warmup", "1"] + extra, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and extra[0] in r.stderr and "--full" in r.stderr, (extra, r.returncode, r.stderr[-2000:])
+
+
 def test_gpu_state_sampler_and_generate_leg_helpers(tmp_path):
     """r03 bench additions: the clock / power sampler degrades to {"available": False} without the amdgpu hwmon files and
     summarises fake ones; the synthetic tokenizer drives the reference's KeywordsStoppingCriteria (tail ids and text)."""
