@@ -106,7 +106,12 @@ int vh_gemm_ps_i8(const vh_gemm_ps_args* args, const int8_t* W, const float* s, 
 /* vh_attention: softmax(scale * Q K^T [+ (Q+v) P^T]) V with causal / pad / chunk masks.
  * Replaces InternAttention._naive_attn (modeling_intern_vit.py:158-177), Whale
  * MultiHeadedAttention.forward score/softmax/PV (attention.py:380-416) and HF
- * eager_attention_forward for the Mixtral prefill.  head_dim 64 or 128.               */
+ * eager_attention_forward for the Mixtral prefill.  head_dim 64 or 128.
+ * klens (nullable, device int[B]): batch b masks keys >= klens[b] — the per-utterance pad mask of a padded batch (Whale
+ * `~make_pad_mask(xs_lens)`, whale/module/encoder/encoder.py:140-147; the serving plugin's one tower pass over padded clips,
+ * web_demo/vllm_tools/vllm_file/mixtral.py:1043-1052); klen then carries max_b klens[b] (the launcher sizes the key split from it).
+ * Honoured by the fp32 direct kernel (every rel-pos call; plain calls under vh_tune("attn_impl", 2) or a chunk mask); causal or
+ * paged calls and the bf16 x 3 / flash kernels refuse it with VH_E_ARG.  klens == NULL: exactly the scalar-klen call. */
 typedef struct {
     const float* Q; long ldq; long hsq;
     const float* K; long ldk; long hsk;
@@ -118,6 +123,7 @@ typedef struct {
     int B, Hq, Hkv, Sq, Sk, d;
     int causal, q_off, klen, chunk, left;
     float scale;
+    const int* klens;
 } vh_attn_args;
 int vh_attention(const vh_attn_args* args, void* stream);
 
@@ -129,7 +135,9 @@ int vh_attention(const vh_attn_args* args, void* stream);
  * TransformerEncoderLayer.forward (whale/module/encoder/transformer.py, rel-pos attention whale/module/layer/attention.py:358-419:
  * P = linear_pos(pos_emb), pos_bias_u / pos_bias_v, pad / chunk mask; ReLU).  h_in is LN(x; this layer's norm1): from
  * vh_layernorm for the first layer, from the previous call's h_out afterwards.  Attention runs inside each of the B
- * sequences of M / B rows; keys >= klen are masked (klen < 0: none).  Scratch (caller-owned): qkv [M, 3C], attn [M, C], hmid [M, C], mid [M, F], ws (split-K slabs,
+ * sequences of M / B rows; keys >= klen are masked (klen < 0: none); klens (nullable, device int[B]) masks keys >= klens[b] in
+ * sequence b instead (vh_attn_args.klens; klen then holds their maximum).  Rel-pos attention takes any B: P is indexed by the
+ * position inside a sequence.  Scratch (caller-owned): qkv [M, 3C], attn [M, C], hmid [M, C], mid [M, F], ws (split-K slabs,
  * >= 32 M max(C, F) bytes recommended; 0 disables the split).
  * planes = 1 (r04; no rel-pos, ws >= 4 M C bytes): the rows that only feed the next Linear travel as the bf16 hi/lo planes vh_gemm_ps consumes — h_in / h_out,
  * attn and hmid then hold two planes each, hi [M][C] followed by lo [M][C] (mid: [M][F] twice), in the same M C 4 (M F 4) bytes — and the four Linears run on the
@@ -148,6 +156,7 @@ typedef struct {
     const float* P; long ldp; const float* bias_u; const float* bias_v; int klen, chunk, left;
     float* qkv; float* attn; float* hmid; float* mid; float* ws; size_t ws_bytes;
     int planes;
+    const int* klens;
 } vh_encoder_layer_args;
 int vh_encoder_layer(const vh_encoder_layer_args* args, void* stream);
 
@@ -192,6 +201,18 @@ int vh_vit_pixel_shuffle(const float* x, float* out, int n, int grid, int hid, f
 /* Whale GlobalCMVN + first Conv2d + ReLU, channels-last (cmvn.py:29-32; subsampling.py:28-31). */
 int vh_audio_conv1(const float* feats, const float* mean, const float* istd, const uint16_t* w, const float* b,
                    float* out, int T, int F, int C, void* stream);
+/* The same for B clips padded to a common length T in ONE launch: feats [B][T][F] -> out [B][T1][F1][C], clip after clip — the
+ * front of the serving plugin's single tower pass over a padded batch (vllm_file/mixtral.py:861-886, 1043-1052; per clip the
+ * arithmetic of vh_audio_conv1, bit for bit). */
+int vh_audio_conv1_batch(const float* feats, const float* mean, const float* istd, const uint16_t* w, const float* b,
+                         float* out, int B, int T, int F, int C, void* stream);
+/* Tail of the padded batch: `xs = xs.masked_fill_(~mask_pad, 0)` in front of the adapter (whale/init_model.py:121-127, the
+ * CNNSubsampling adapter then pads k - 1 zero frames on the right, adapter.py:93-136).  x [B][S][cols] (row stride ldx) ->
+ * y [B][S + gap][cols] (row stride ldy): row s < klens[b] of clip b is copied, rows [klens[b], S + gap) are zeros, so that a
+ * strided window over y that starts inside clip b never reads a neighbour's rows.  klens: device int[B]; cols % 4 == 0,
+ * 16-byte aligned rows; x and y must not overlap. */
+int vh_audio_mask_rows(const float* x, long ldx, float* y, long ldy, const int* klens, int B, int S, int gap, int cols,
+                       void* stream);
 
 /* embed_tokens gather + image/audio splice (vita_arch.py:237-321); kind 0 text,1 image,2 audio. */
 int vh_embed_splice(const int* src_kind, const int* src_idx, const uint16_t* embed, const float* img_feats,

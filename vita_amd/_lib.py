@@ -52,6 +52,7 @@ class AttnArgs(C.Structure):
         ("B", c_int), ("Hq", c_int), ("Hkv", c_int), ("Sq", c_int), ("Sk", c_int), ("d", c_int),
         ("causal", c_int), ("q_off", c_int), ("klen", c_int), ("chunk", c_int), ("left", c_int),
         ("scale", c_float),
+        ("klens", c_void_p),
     ]
 
 
@@ -69,6 +70,7 @@ class EncoderLayerArgs(C.Structure):
         ("P", c_void_p), ("ldp", c_long), ("bias_u", c_void_p), ("bias_v", c_void_p), ("klen", c_int), ("chunk", c_int), ("left", c_int),
         ("qkv", c_void_p), ("attn", c_void_p), ("hmid", c_void_p), ("mid", c_void_p), ("ws", c_void_p), ("ws_bytes", c_size_t),
         ("planes", c_int),
+        ("klens", c_void_p),
     ]
 
 
@@ -143,6 +145,9 @@ SIGNATURES = {
     "vh_vit_pixel_shuffle": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p]),
     "vh_audio_conv1": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                c_void_p]),
+    "vh_audio_conv1_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                     c_void_p]),
+    "vh_audio_mask_rows": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "vh_embed_splice": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "vh_router_top2": (c_int, [c_void_p, c_long, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vh_moe_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,

@@ -140,7 +140,7 @@ int vh_attention(const vh_attn_args* a, void* stream) {
     g.bsq = a->bsq; g.bsk = a->bsk; g.bso = a->bso;
     g.B = a->B; g.Hq = a->Hq; g.Hkv = a->Hkv; g.Sq = a->Sq; g.Sk = a->Sk; g.d = a->d;
     g.causal = a->causal; g.q_off = a->q_off; g.klen = a->klen; g.chunk = a->chunk; g.left = a->left;
-    g.scale = a->scale;
+    g.scale = a->scale; g.klens = a->klens;
     if (a->P && (!a->bias_u || !a->bias_v)) return fail(VH_E_ARG, "vh_attention: rel-pos needs bias_u/bias_v");
     if ((a->ldk % 4) || (a->ldv % 4) || (a->hsk % 4) || (a->hsv % 4) || (a->bsk % 4) ||
         (reinterpret_cast<uintptr_t>(a->K) & 15) || (reinterpret_cast<uintptr_t>(a->V) & 15) ||
@@ -149,7 +149,9 @@ int vh_attention(const vh_attn_args* a, void* stream) {
     if ((a->ldq % 4) || (a->hsq % 4) || (a->bsq % 4) || (a->ldo % 4) || (a->bso % 4) || (reinterpret_cast<uintptr_t>(a->Q) & 15) ||
         (reinterpret_cast<uintptr_t>(a->O) & 15) || (a->d != 64 && a->d != 128) || (a->P && a->d != 64))
         return fail(VH_E_SHAPE, "vh_attention: Q/O rows must be 16-byte aligned, head_dim 64 or 128 (rel-pos: 64)");
-    return check_launch("vh_attention", vhk_attn(S(stream), g));
+    const int rc = vhk_attn(S(stream), g);
+    if (rc == -2) return fail(VH_E_ARG, "vh_attention: klens is honoured by the fp32 direct kernel only (rel-pos, a chunk mask or attn_impl 2; not causal, not paged)");
+    return check_launch("vh_attention", rc);
 }
 
 int vh_layernorm(const float* x, long ldx, float* y, long ldy, const float* w, const float* b, int rows, int cols,
@@ -204,7 +206,17 @@ int vh_vit_pixel_shuffle(const float* x, float* out, int n, int grid, int hid, f
 }
 int vh_audio_conv1(const float* feats, const float* mean, const float* istd, const uint16_t* w, const float* b,
                    float* out, int T, int F, int C, void* stream) {
-    return check_launch("vh_audio_conv1", vhk_audio_conv1(S(stream), feats, mean, istd, w, b, out, T, F, C));
+    return check_launch("vh_audio_conv1", vhk_audio_conv1(S(stream), feats, mean, istd, w, b, out, 1, T, F, C));
+}
+int vh_audio_conv1_batch(const float* feats, const float* mean, const float* istd, const uint16_t* w, const float* b,
+                         float* out, int B, int T, int F, int C, void* stream) {
+    if (!feats || !mean || !istd || !w || !b || !out) return fail(VH_E_ARG, "vh_audio_conv1_batch: null pointer");
+    return check_launch("vh_audio_conv1_batch", vhk_audio_conv1(S(stream), feats, mean, istd, w, b, out, B, T, F, C));
+}
+int vh_audio_mask_rows(const float* x, long ldx, float* y, long ldy, const int* klens, int B, int Sn, int gap, int cols,
+                       void* stream) {
+    if (!x || !y || !klens) return fail(VH_E_ARG, "vh_audio_mask_rows: null pointer");
+    return check_launch("vh_audio_mask_rows", vhk_audio_mask_rows(S(stream), x, ldx, y, ldy, klens, B, Sn, gap, cols));
 }
 int vh_embed_splice(const int* src_kind, const int* src_idx, const uint16_t* embed, const float* img_feats,
                     const float* aud_feats, float* out, int Sn, int H, void* stream) {
@@ -1130,7 +1142,7 @@ int vh_encoder_layer(const vh_encoder_layer_args* a, void* stream) {
         return fail(VH_E_SHAPE, "vh_encoder_layer: M %d B %d C %d F %d heads %d", M, a->B, Cw, F, a->heads);
     const int d = Cw / a->heads, Sq = M / a->B;
     if (d != 64 && d != 128) return fail(VH_E_SHAPE, "vh_encoder_layer: head_dim %d (64 or 128)", d);
-    if (a->P && (!a->bias_u || !a->bias_v || a->B != 1)) return fail(VH_E_ARG, "vh_encoder_layer: rel-pos needs bias_u / bias_v and B = 1");
+    if (a->P && (!a->bias_u || !a->bias_v)) return fail(VH_E_ARG, "vh_encoder_layer: rel-pos needs bias_u / bias_v");
     if (a->h_out && !a->next_w) return fail(VH_E_ARG, "vh_encoder_layer: h_out without next_w");
     hipStream_t st = S(stream);
     auto lin = [&](const float* A, int K, const uint16_t* W, int N, const float* bias, int act, const float* scale, const float* resid,
@@ -1191,7 +1203,10 @@ int vh_encoder_layer(const vh_encoder_layer_args* a, void* stream) {
         g.klen = (a->klen >= 0 && a->klen < Sq) ? a->klen : Sq; g.chunk = a->chunk; g.left = a->left;
         g.scale = 1.0f / sqrtf((float)d);
         g.P = a->P; g.ldp = a->ldp; g.hsp = d; g.bias_u = a->bias_u; g.bias_v = a->bias_v;
-        VH_TRY(vhk_attn(st, g), "encoder attention");
+        g.klens = a->klens;
+        const int rc = vhk_attn(st, g);
+        if (rc == -2) return fail(VH_E_ARG, "vh_encoder_layer: klens needs the fp32 direct attention kernel (rel-pos, a chunk mask or attn_impl 2)");
+        VH_TRY(rc, "encoder attention");
     }
     if (planes) {
         const int ks1 = ks_for(Cw, Cw), ks2 = ks_for(Cw, F);

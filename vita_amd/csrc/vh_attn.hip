@@ -103,7 +103,7 @@ __global__ __launch_bounds__(64 * KS) __attribute__((amdgpu_waves_per_eu(WPE, WP
         }
     }
 
-    const int kend = min(p.Sk, p.klen);
+    const int kend = min(p.Sk, p.klens ? p.klens[b] : p.klen);   // per-batch pad mask of a padded batch (uniform: one scalar load)
     int kloop = kend;
     if (p.causal) kloop = min(kloop, min(q0 + 15, p.Sq - 1) + p.q_off + 1);
 
@@ -923,7 +923,9 @@ int vhk_attn(hipStream_t st, const VhAttnArgs& a_in) {
     VhAttnArgs a = a_in;
     a.xcd_map = vh_tuning()->attn_xcd != 0 ? 1 : 0;
     if (a.Sq <= 0 || a.Sk <= 0 || a.Hq % a.Hkv != 0) return -1;
-    if (a.nseg > 0) return attn_segments(st, a);
+    if (a.nseg > 0) return a.klens ? -2 : attn_segments(st, a);
+    // per-batch key lengths: the pad mask of the fp32 direct kernel only (no causal / paged form, not in the bf16 x 3 / flash kernels)
+    if (a.klens && (a.causal || a.ktable)) return -2;
     const bool rel = a.P != nullptr;
     const int want = vh_tuning()->attn_ksplit;
     const int kl = a.klen < a.Sk ? a.klen : a.Sk;
@@ -953,6 +955,7 @@ int vhk_attn(hipStream_t st, const VhAttnArgs& a_in) {
             if (rows >= (1L << 24) || ldmax >= (1L << 24) || ldmax < 0 || (rows * ldmax + a.d) * 4 >= (1L << 32)) mode = -1;
         }
         if (!rel && vh_tuning()->attn_impl == 0 && mode >= 0) {
+            if (a.klens) return -2;
             // flash form (K / V tiles shared through LDS by the four query heads of a KV head): d = 128 with the 4 : 1 grouping; taken when
             // its blocks (16 rows x 4 heads) still fill half the chip, or when forced (attn_fa = 2: tests)
             const int fa = vh_tuning()->attn_fa;

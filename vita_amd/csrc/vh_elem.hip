@@ -291,25 +291,45 @@ __global__ void k_vit_pixel_shuffle(const float* __restrict__ x, float* __restri
 // ---- Whale front end: GlobalCMVN + Conv2d(1,C,3,2) + ReLU, channels-last output ---------
 // out[t1, f1, c] = relu(b[c] + sum_{kh,kw} w[c,kh,kw] * ((x[2t1+kh, 2f1+kw] - mean)*istd))
 // (cmvn.py:29-32, subsampling.py:28-31)
+// B clips of a common padded length T, clip after clip on both sides (B = 1: the single clip): t1 below is the row
+// clip * T1 + t1' of the output, and its window starts at input row clip * T + 2 t1' — inside the clip by construction.
 __global__ void k_audio_conv1(const float* __restrict__ feats, const float* __restrict__ mean,
                               const float* __restrict__ istd, const uint16_t* __restrict__ w,
-                              const float* __restrict__ b, float* __restrict__ out, int T, int F, int C) {
+                              const float* __restrict__ b, float* __restrict__ out, int B, int T, int F, int C) {
     const int T1 = (T - 3) / 2 + 1, F1 = (F - 3) / 2 + 1;
-    const long total = (long)T1 * F1 * C;
+    const long total = (long)B * T1 * F1 * C;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
         const int c = (int)(i % C);
         const int f1 = (int)((i / C) % F1);
-        const int t1 = (int)(i / ((long)C * F1));
+        const int row = (int)(i / ((long)C * F1));
+        const int clip = row / T1, t1 = row - clip * T1;
+        const float* __restrict__ fc = feats + (long)clip * T * F;
         float acc = 0.f;
 #pragma unroll
         for (int kh = 0; kh < 3; ++kh)
 #pragma unroll
             for (int kw = 0; kw < 3; ++kw) {
                 const int f = 2 * f1 + kw;
-                const float xv = (feats[(long)(2 * t1 + kh) * F + f] - mean[f]) * istd[f];
+                const float xv = (fc[(long)(2 * t1 + kh) * F + f] - mean[f]) * istd[f];
                 acc = fmaf(bf16_to_f32(w[c * 9 + kh * 3 + kw]), xv, acc);
             }
         out[i] = fmaxf(acc + b[c], 0.f);
+    }
+}
+
+// ---- Whale tail of a padded batch: masked_fill_(~mask_pad, 0) into a layout with `gap` zero rows behind every clip ----
+// y[b][s][:] = s < klens[b] ? x[b][s][:] : 0 for s in [0, S + gap)   (init_model.py:121-127; the gap is the adapter's right padding)
+__global__ void k_audio_mask_rows(const float* __restrict__ x, long ldx, float* __restrict__ y, long ldy,
+                                  const int* __restrict__ klens, int B, int S, int gap, int cols4) {
+    const int So = S + gap;
+    const long total = (long)B * So * cols4;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int c4 = (int)(i % cols4);
+        const long row = i / cols4;
+        const int b = (int)(row / So), s = (int)(row - (long)b * So);
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (s < S && s < klens[b]) v = *reinterpret_cast<const float4*>(x + ((long)b * S + s) * ldx + 4 * c4);
+        *reinterpret_cast<float4*>(y + row * ldy + 4 * c4) = v;
     }
 }
 
@@ -717,11 +737,20 @@ int vhk_vit_pixel_shuffle(hipStream_t st, const float* x, float* out, int n, int
     return 0;
 }
 int vhk_audio_conv1(hipStream_t st, const float* feats, const float* mean, const float* istd, const uint16_t* w,
-                    const float* b, float* out, int T, int F, int C) {
-    if (T < 3 || F < 3) return -1;
-    const long total = (long)((T - 3) / 2 + 1) * ((F - 3) / 2 + 1) * C;
-    hipLaunchKernelGGL(k_audio_conv1, dim3(grid_for(total, 256)), dim3(256), 0, st, feats, mean, istd, w, b, out, T, F,
+                    const float* b, float* out, int B, int T, int F, int C) {
+    if (B < 1 || T < 3 || F < 3) return -1;
+    const long total = (long)B * ((T - 3) / 2 + 1) * ((F - 3) / 2 + 1) * C;
+    if ((long)B * ((T - 3) / 2 + 1) >= (1L << 31)) return -1;
+    hipLaunchKernelGGL(k_audio_conv1, dim3(grid_for(total, 256)), dim3(256), 0, st, feats, mean, istd, w, b, out, B, T, F,
                        C);
+    return 0;
+}
+int vhk_audio_mask_rows(hipStream_t st, const float* x, long ldx, float* y, long ldy, const int* klens, int B, int S, int gap,
+                        int cols) {
+    if (B < 1 || S < 1 || gap < 0 || cols < 4 || (cols % 4) != 0 || (ldx % 4) != 0 || (ldy % 4) != 0 || ldx < cols || ldy < cols) return -1;
+    if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(y) & 15)) return -1;
+    const long total = (long)B * (S + gap) * (cols / 4);
+    hipLaunchKernelGGL(k_audio_mask_rows, dim3(grid_for(total, 256)), dim3(256), 0, st, x, ldx, y, ldy, klens, B, S, gap, cols / 4);
     return 0;
 }
 int vhk_rope_kv(hipStream_t st, const float* qkv, long ldqkv, float* q_out, float* kcache, float* vcache,

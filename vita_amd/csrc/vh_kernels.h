@@ -280,8 +280,9 @@ struct VhAttnArgs {
     // row row0.  segs: device array (the flash kernel takes the segment from the block's batch coordinate); segs_host: the same on the
     // host (sizes the grid; kernels without a segmented form are launched once per segment).
     const VhSeg* segs; const VhSeg* segs_host; int nseg;
+    const int* klens;                     // nullable, device int[B]: batch b masks keys >= klens[b] (klen = their maximum); fp32 direct kernel only
 };
-int vhk_attn(hipStream_t st, const VhAttnArgs& a);
+int vhk_attn(hipStream_t st, const VhAttnArgs& a);     // 0, -1 (shape) or -2 (klens with a kernel / mask flavour that has no per-batch form)
 int vhk_attn_fa_applies(const VhAttnArgs& a);    // 1 when vhk_attn would run the flash kernel (k_attn_fa) for these arguments
 
 // ---- element-wise / index kernels (vh_elem.hip) -------------------------------------
@@ -295,7 +296,9 @@ int vhk_vit_assemble(hipStream_t st, const float* patches, const uint16_t* cls, 
                      int ntok, int hid);
 int vhk_vit_pixel_shuffle(hipStream_t st, const float* x, float* out, int n, int grid, int hid, float mul);
 int vhk_audio_conv1(hipStream_t st, const float* feats, const float* mean, const float* istd, const uint16_t* w,
-                    const float* b, float* out, int T, int F, int C);
+                    const float* b, float* out, int B, int T, int F, int C);
+int vhk_audio_mask_rows(hipStream_t st, const float* x, long ldx, float* y, long ldy, const int* klens, int B, int S, int gap,
+                        int cols);
 int vhk_rope_kv(hipStream_t st, const float* qkv, long ldqkv, float* q_out, float* kcache, float* vcache,
                 const float* rope_cos, const float* rope_sin, int S, int pos0, int nq, int nkv, int max_ctx,
                 const int* table, const int* nslab_dev, long slab_stride);   // nslab_dev: qkv is *nslab_dev partial slabs

@@ -13,6 +13,11 @@ Two identical engines (replicas: no tensor traffic between them) alternate betwe
   * an engine polls its own stop flag between decode windows and abandons its answer when it is set (:354-366);
   * finished sentences (split on punctuation) go to the output queue, the finished turn to the shared history.
 
+Conversation mode (`conversation=True`, off by default): a turn is answered with the last `history_turns` finished turns in
+its prompt (`merge_current_and_history`, web_interactive_demo.py:297-302, 604-680) — the history's audio clips stay in
+`multi_modal_data` ahead of the current clip, its images are dropped — and the merged prompt is re-tokenised with the engine's
+placeholder ids (:308).  The history keeps the UNMERGED request: prompt, multi_modal_data, response.
+
 `worker_loop` is the per-engine process body; it only needs an object with
 `generate_stream(inputs, sampling_params, request_id, should_stop) -> iterator of RequestOutput` (vita_amd.serving.LLM
 has it), so the protocol is unit-tested on the CPU with scripted engines and on the GPU with two real engines.
@@ -22,8 +27,78 @@ import queue as _queue
 import time
 import uuid
 
+from .host.prompt import SYSTEM_PROMPTS, tokenizer_image_audio_token
+
 NEGATIVE_PREFIX = "<2>"
 SENTENCE_END = [",", "，", ".", "。", "?", "\n", "？", "!", "！", "、"]
+IMAGE_TOKEN, VIDEO_TOKEN = "<image>", "<video>"
+USER_PREFIX, BOT_PREFIX, TURN_END = "user:", "bot:", "</s>\n"
+MODALITIES = ("image", "audio", "video")
+
+
+def demo_system_prompt(request):
+    """The interactive demo's system block for a request (web_interactive_demo.py:611-627): the media prompt — the VIDEO
+    one for an image as well — or the plain one; the demo spells the model's name "Vita" where the offline templates
+    (host/prompt.py) say "VITA", otherwise the strings are the same."""
+    mm = request.get("multi_modal_data") or {}
+    which = 1 if ("video" in mm or "image" in mm) else 2
+    return "system:" + SYSTEM_PROMPTS[which].replace("your name is VITA", "your name is Vita", 1) + TURN_END
+
+
+def _strip_state_space(text):
+    return text.replace("<1> ", "<1>").replace("<2> ", "<2>")
+
+
+def merge_current_and_history(history, request, skip_history_vision=False, move_image_token_to_start=False):
+    """The prompt and modal data of `request` with the turns of `history` in front (web_interactive_demo.py:604-680; same
+    results).  `request` is updated in place and returned, as the reference does.  history entries: {"prompt", "response"[,
+    "multi_modal_data"]}.  An empty history only frames the prompt and leaves the modal data alone."""
+    system = demo_system_prompt(request)
+    ask = USER_PREFIX + request["prompt"] + TURN_END + BOT_PREFIX
+    if len(history) == 0:
+        request["prompt"] = _strip_state_space(system + ask)
+        return request
+    text, data = system, {m: [] for m in MODALITIES}
+    kept = [m for m in MODALITIES if not (skip_history_vision and m in ("image", "video"))]
+    for turn in history:
+        if "prompt" not in turn or "response" not in turn:
+            raise AssertionError("a history turn needs its prompt and its response")
+        said = turn["prompt"]
+        if skip_history_vision:
+            said = said.replace(IMAGE_TOKEN, "").replace(VIDEO_TOKEN, "")
+        text += USER_PREFIX + said + TURN_END + BOT_PREFIX + turn["response"] + TURN_END
+        for m in kept:
+            data[m].extend((turn.get("multi_modal_data") or {}).get(m, []))
+    text += ask
+    for m in MODALITIES:
+        data[m].extend((request.get("multi_modal_data") or {}).get(m, []))
+    data = {m: v for m, v in data.items() if len(v)}
+    if move_image_token_to_start:
+        n = text.count(IMAGE_TOKEN)
+        body = text.replace(IMAGE_TOKEN, "").replace(system, "")
+        # str.lstrip takes a character SET: like the reference, this also eats leading letters of the first words that are in "user:"
+        text = system + USER_PREFIX + IMAGE_TOKEN * n + body.lstrip(USER_PREFIX)
+    request["prompt"] = _strip_state_space(text)
+    request["multi_modal_data"] = data
+    return request
+
+
+def conversation_inputs(llm, history, request, history_turns=1):
+    """What a conversation-mode turn hands to the engine: `request` merged with the last `history_turns` turns (history vision
+    skipped, image tokens moved to the start: web_interactive_demo.py:297-302) and, when the engine has a tokenizer, the
+    merged prompt as `prompt_token_ids` with the engine's placeholder ids (:308).  `request` itself is not modified."""
+    turns = list(history)[-int(history_turns):] if int(history_turns) > 0 else []
+    merged = dict(request)
+    if "multi_modal_data" in merged:
+        merged["multi_modal_data"] = {k: list(v) if isinstance(v, (list, tuple)) else [v]
+                                      for k, v in merged["multi_modal_data"].items()}
+    merged = merge_current_and_history(turns, merged, skip_history_vision=True, move_image_token_to_start=True)
+    tok = getattr(llm, "tokenizer", None)
+    if tok is not None and "prompt" in merged:
+        merged["prompt_token_ids"] = tokenizer_image_audio_token(
+            merged["prompt"], tok, image_token_index=int(getattr(llm, "image_token_index", 51000)),
+            audio_token_index=int(getattr(llm, "audio_token_index", 51001)))
+    return merged
 
 
 def judge_negative(text):
@@ -40,8 +115,11 @@ def clear_queue(q):
 
 def worker_loop(llm_id, make_llm, sampling_params, inputs_queue, outputs_queue, stop_event, other_stop_event,
                 worker_ready, wait_workers_ready, start_event, other_start_event, start_event_lock, interrupt_signal,
-                global_history, shutdown_event, stats_queue=None, history_limit=0, poll_s=0.005):
-    """Body of one engine process (web_interactive_demo.py:105-379)."""
+                global_history, shutdown_event, stats_queue=None, history_limit=0, poll_s=0.005, conversation=False,
+                history_turns=1):
+    """Body of one engine process (web_interactive_demo.py:105-379).  conversation=True: every turn is merged with the last
+    `history_turns` history entries before it reaches the engine (conversation_inputs); off, the engine receives exactly what
+    was submitted."""
     llm = make_llm()
     worker_ready.set()
     while not shutdown_event.is_set():
@@ -62,10 +140,21 @@ def worker_loop(llm_id, make_llm, sampling_params, inputs_queue, outputs_queue, 
             start_event.clear()
         t_take = time.perf_counter()
         current = dict(inputs)
+        error = None
+        if conversation:
+            try:
+                inputs = conversation_inputs(llm, global_history, current, history_turns)
+            except Exception as e:     # a malformed request is answered like a failed one below; the baton was already passed on
+                error = f"{type(e).__name__}: {e}"
+                print(f"[duplex worker {llm_id}] request failed: {error}", flush=True)
+                if stats_queue is not None:
+                    stats_queue.put({"id": llm_id, "request": current.get("request_id"), "take_to_first_chunk_s": None,
+                                     "first_chunk_to_end_s": None, "n_tokens": 0, "interrupted": False, "negative": True,
+                                     "n_chunks": 0, "error": error})
+                continue
         results, pending, first_positive, t_first = [], "", True, None
         previous, n_tokens = "", 0
         st = {"speaking": False}     # the stop flag only counts once this engine has taken the floor (:354)
-        error = None
         stream = llm.generate_stream(inputs, sampling_params, request_id=uuid.uuid4().hex,
                                      should_stop=lambda: st["speaking"] and stop_event.is_set())
         try:
@@ -104,7 +193,8 @@ def worker_loop(llm_id, make_llm, sampling_params, inputs_queue, outputs_queue, 
             outputs_queue.put({"id": llm_id, "response": pending})
         current["response"] = "".join(results)
         if current["response"]:
-            global_history.append({k: v for k, v in current.items() if k in ("prompt", "response")})
+            keep = ("prompt", "response", "multi_modal_data") if conversation else ("prompt", "response")
+            global_history.append({k: v for k, v in current.items() if k in keep})
             if history_limit and len(global_history) > history_limit:
                 del global_history[0]
         if stats_queue is not None:
@@ -128,8 +218,10 @@ def _engine_process(llm_id, llm_factory, factory_args, sampling_params, shared, 
 class DuplexServer:
     """Two engine processes + the shared queues / events of web_interactive_demo.py:914-1029."""
 
-    def __init__(self, llm_factory, factory_args=(), sampling_params=None, history_limit=0, ctx="spawn", engines_share_device=True):
-        """engines_share_device: the two replicas drive the same GPU (the default assumption; pass False when the factory places
+    def __init__(self, llm_factory, factory_args=(), sampling_params=None, history_limit=0, ctx="spawn", engines_share_device=True,
+                 conversation=False, history_turns=1):
+        """conversation / history_turns: answer every turn with the last `history_turns` finished turns in its prompt (worker_loop).
+        engines_share_device: the two replicas drive the same GPU (the default assumption; pass False when the factory places
         them on different devices, as the reference's demo does: cuda_devices "0,1" / "2,3", web_interactive_demo.py:958,981)."""
         self.mpc = mp.get_context(ctx)
         self.mgr = self.mpc.Manager()
@@ -150,6 +242,8 @@ class DuplexServer:
                           start_event=start[i], other_start_event=start[1 - i], start_event_lock=self.lock,
                           interrupt_signal=self.interrupt, global_history=self.history,
                           shutdown_event=self.shutdown, stats_queue=self.stats, history_limit=history_limit)
+            if conversation:
+                shared.update(conversation=True, history_turns=int(history_turns))
             p = self.mpc.Process(target=_engine_process, args=(i, llm_factory, factory_args, sampling_params, shared, engines_share_device),
                                  daemon=True)
             p.start()

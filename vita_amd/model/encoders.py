@@ -422,8 +422,83 @@ class WhaleAudioEncoder(_HipModule):
         if speech.ndim != 3:
             raise AssertionError("speech must be [B, T, D]")                                   # encoder.py:137
         lens = [int(round(float(x))) for x in speech_lengths.reshape(-1).tolist()]
-        embs, masks = [], []
-        for b in range(speech.shape[0]):
-            e, m = self.encode_one(speech[b].contiguous(), lens[b])
-            embs.append(e); masks.append(m)
-        return {"inputs_embeds": torch.stack(embs, 0), "attention_mask": torch.stack(masks, 0)}
+        if speech.shape[0] >= 2:
+            e, m = self.encode_batch(speech.contiguous(), lens)
+            return {"inputs_embeds": e, "attention_mask": m}
+        e, m = self.encode_one(speech[0].contiguous(), lens[0])
+        return {"inputs_embeds": e[None], "attention_mask": m[None]}
+
+    def _batch_rows(self, B, T1, F1, T2):
+        """row maps of the padded batch: conv2's and the adapter's window starts for clip after clip.  conv2 reads rows
+        [2 t, 2 t + 2] of its own clip's T1 (2 (T2 - 1) + 2 <= T1 - 1); the adapter reads k rows from 2 t of a clip laid out
+        with k - 1 zero rows behind it (audio_mask_rows), its right padding — no window reaches a neighbour."""
+        key = ("batch", B, T1, F1)
+        if key not in self._idx_cache:
+            rows, _, _, segrow = self._conv2_rows(T1, F1)
+            rows3, T3 = self._adapter_rows(T2)
+            gap = self.acfg.adapter_kernel - 1
+            off = torch.arange(B, dtype=torch.int32, device=self._device)[:, None]
+            self._idx_cache[key] = ((rows[None] + off * (T1 * F1)).reshape(-1).contiguous(),
+                                    (rows3[None] + off * (T2 + gap)).reshape(-1).contiguous(), T3, gap, segrow)
+        return self._idx_cache[key]
+
+    @torch.no_grad()
+    def encode_batch(self, speech, lens):
+        """B clips padded to a common length in ONE tower pass (the serving plugin's padded batch under a mask,
+        vllm_file/mixtral.py:861-886, 1043-1052): speech fp32 [B, T, 80] on the device, lens[b] valid frames.  Every
+        row-wise operator sees B * T' rows, attention runs inside each clip with its own key length (klens), rows past a clip's
+        length are zeroed in front of the adapter.  Returns (embeds [B, T'', H], mask [B, T''] bool); a clip's valid rows are
+        those of encode_one(speech[b], lens[b]) up to fp32 summation order."""
+        a, w = self.acfg, self.w
+        C, nh = a.hidden_size, a.num_attention_heads
+        dk = C // nh
+        B, T = int(speech.shape[0]), int(speech.shape[1])
+        if self.normalized_input:
+            if "mean0" not in w:
+                w["mean0"], w["istd1"] = torch.zeros_like(w["mean"]), torch.ones_like(w["istd"])
+            mean, istd = w["mean0"], w["istd1"]
+        else:
+            mean, istd = w["mean"], w["istd"]
+        y1, T1, F1 = ops.audio_conv1_batch(speech, mean, istd, w["c1_w"], w["c1_b"])            # [B*T1*F1, C]
+        _, T2, F2, _ = self._conv2_rows(T1, F1)
+        rows, rows3, T3, gap, segrow = self._batch_rows(B, T1, F1, T2)
+        y2 = ops.gemm(y1, w["c2_w"], bias=w["c2_b"], act="relu", a_rowidx=rows, segrow=segrow, seglen=C)
+        y = ops.gemm(y2.view(B * T2, F2 * C), w["out_w"], bias=w["out_b"])                      # [B*T2, C]
+        kl = [len(range(T)[:min(max(int(n), 0), T)][2::2][2::2]) for n in lens]                 # x_mask[:, :, 2::2][:, :, 2::2] per clip
+        klens = torch.tensor(kl, dtype=torch.int32).to(self._device, non_blocking=True)
+        kmax = max(kl)
+        y = ops.gemm(y, w["emb_w"], bias=w["emb_b"])
+        y = ops.layernorm(y, w["emb_nw"], w["emb_nb"], 1e-5, act="relu", post_scale=math.sqrt(C))
+        pos_proj = self._pos_projections(T2)
+        M = B * T2
+        h = ops.layernorm(y, w["layers"][0]["n1w"], w["layers"][0]["n1b"], a.layer_norm_eps) if w["layers"] else None
+        if not self.per_operator and w["layers"]:
+            sc = ops.encoder_scratch(M, C, w["layers"][0]["fc1_w"].shape[0], self._device)
+            for li, L in enumerate(w["layers"]):
+                nxt = w["layers"][li + 1] if li + 1 < len(w["layers"]) else None
+                nn_ = (nxt["n1w"], nxt["n1b"]) if nxt is not None else (w["an_w"], w["an_b"])
+                ops.encoder_layer(y, h, sc.h[li & 1], L, sc, heads=nh, B=B, act="relu", eps=a.layer_norm_eps,
+                                  next_norm=nn_, p=pos_proj[li], bias_u=L["u"], bias_v=L["v"], klen=kmax, klens=klens,
+                                  chunk=self.chunk, left=self.left)
+                h = sc.h[li & 1]
+        elif w["layers"]:
+            o = torch.empty((M, C), dtype=torch.float32, device=self._device)
+            for li, L in enumerate(w["layers"]):
+                qkv = ops.gemm(h, L["qkv_w"], bias=L["qkv_b"])
+                ops.attention(qkv, qkv[:, C:], qkv[:, 2 * C:], o, B=B, Hq=nh, Hkv=nh, Sq=T2, Sk=T2, d=dk, ldq=3 * C, hsq=dk,
+                              ldk=3 * C, hsk=dk, ldv=3 * C, hsv=dk, ldo=C, bsq=T2 * 3 * C, bsk=T2 * 3 * C, bso=T2 * C,
+                              scale=1.0 / math.sqrt(dk), klen=kmax, klens=klens, chunk=self.chunk, left=self.left,
+                              p=pos_proj[li], ldp=C, hsp=dk, bias_u=L["u"], bias_v=L["v"])
+                _, h = ops.gemm(o, L["out_w"], bias=L["out_b"], resid=y, out=y, ln=(L["n2w"], L["n2b"], a.layer_norm_eps))
+                f = ops.gemm(h, L["w1"], bias=L["b1"], act="relu")
+                nxt = w["layers"][li + 1] if li + 1 < len(w["layers"]) else None
+                nw, nb = (nxt["n1w"], nxt["n1b"]) if nxt is not None else (w["an_w"], w["an_b"])
+                _, h = ops.gemm(f, L["w2"], bias=L["b2"], resid=y, out=y, ln=(nw, nb, a.layer_norm_eps))
+        y = h if w["layers"] else ops.layernorm(y, w["an_w"], w["an_b"], a.layer_norm_eps)
+        yz = ops.audio_mask_rows(y, klens, B, gap)                                              # masked_fill_(~mask_pad, 0) + zero gap
+        z = ops.gemm(yz, w["ad_w"], bias=w["ad_b"], a_rowidx=rows3, segrow=list(range(a.adapter_kernel)), seglen=C)
+        z = ops.layernorm(z, w["ad_nw"], w["ad_nb"], a.adapter_norm_eps, act="gelu")
+        out = ops.gemm(z, w["pj_w"], bias=w["pj_b"])                                            # [B*T3, H]
+        mask = (torch.arange(T2, device=self._device)[None, :] < klens[:, None])[:, 0::2]
+        assert out.shape[0] == B * mask.shape[1]                                                # init_model.py:127
+        return out.view(B, T3, -1), mask

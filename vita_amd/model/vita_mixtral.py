@@ -160,10 +160,13 @@ class VITAMixtralForCausalLM(_HipModule):
     # ---- multimodal assembly -----------------------------------------------------------------
     @torch.no_grad()
     def prepare_inputs_labels_for_multimodal(self, input_ids, position_ids, attention_mask, past_key_values, labels,
-                                             images, audios):
+                                             images, audios, audio_valid_rows=False):
         """Inference subset of vita_arch.py:151-407 for batch size 1: encode, check the placeholder
         counts, splice image / audio embeddings at the -200 / -500 sentinels, truncate to
-        tokenizer_model_max_length.  Returns the reference's 6-tuple with inputs_embeds [1,S,H]."""
+        tokenizer_model_max_length.  Returns the reference's 6-tuple with inputs_embeds [1,S,H].
+        audio_valid_rows=False is the HF flavour: a clip contributes its whole padded row block (vita_arch.py:294-297).
+        True is the serving flavour: only the rows the encoder's mask marks valid (the plugin keeps each clip's valid tokens,
+        vllm_file/mixtral.py:1097-1116), i.e. serving.audio_feature_size(frames) tokens per clip."""
         if input_ids.shape[0] != 1:
             raise NotImplementedError("the HIP path serves one request per call (batch 1), like the demo")
         dev = self._device
@@ -199,14 +202,17 @@ class VITAMixtralForCausalLM(_HipModule):
         assert n_img + (0 if n_img else 1) == image_features.shape[0]       # vita_arch.py:227-231
         assert n_aud + (0 if n_aud else 1) == aud_emb.shape[0]             # vita_arch.py:232-236
         tiles_tok, aud_tok = image_features.shape[1], aud_emb.shape[1]
+        aud_valid = [aud_tok] * aud_emb.shape[0]
+        if audio_valid_rows:                                               # the mask is a prefix of every row (pad mask, strided)
+            aud_valid = [int(n) for n in audio_features["attention_mask"].sum(dim=1).tolist()]
         kind, idx, ii, ai = [], [], 0, 0
         for t in ids_np.tolist():
             if t == IMAGE_TOKEN_INDEX:
                 kind += [1] * tiles_tok
                 idx += list(range(ii * tiles_tok, (ii + 1) * tiles_tok)); ii += 1
             elif t == AUDIO_TOKEN_INDEX:
-                kind += [2] * aud_tok
-                idx += list(range(ai * aud_tok, (ai + 1) * aud_tok)); ai += 1
+                kind += [2] * aud_valid[ai]
+                idx += list(range(ai * aud_tok, ai * aud_tok + aud_valid[ai])); ai += 1
             else:
                 if t < 0 or t >= self.config.vocab_size:
                     raise ValueError(f"token id {t} outside the vocabulary")
@@ -239,7 +245,7 @@ class VITAMixtralForCausalLM(_HipModule):
     def generate(self, input_ids=None, images=None, audios=None, do_sample=False, temperature=None, top_p=None,
                  num_beams=1, output_scores=False, return_dict_in_generate=False, max_new_tokens=None,
                  use_cache=True, stopping_criteria=None, inputs_embeds=None, attention_mask=None,
-                 eos_token_id=None, streamer=None, top_k=None, seed=None, **kwargs):
+                 eos_token_id=None, streamer=None, top_k=None, seed=None, audio_valid_rows=False, **kwargs):
         """HF generate.  do_sample=True draws on the device (temperature -> top-k -> top-p, Gumbel-max over a Philox stream keyed
         by `seed`; include/vita_hip.h vh_sampling) and needs seed=: the ids are a function of the request.  Unset parameters take
         HF's defaults (temperature 1.0, top_k 50, top_p 1.0).  scores stay the raw logits."""
@@ -265,7 +271,7 @@ class VITAMixtralForCausalLM(_HipModule):
         ev[0].record()
         if inputs_embeds is None:
             _, _, _, _, inputs_embeds, _ = self.prepare_inputs_labels_for_multimodal(
-                input_ids, None, attention_mask, None, None, images, audios)
+                input_ids, None, attention_mask, None, None, images, audios, audio_valid_rows=audio_valid_rows)
         emb = inputs_embeds[0].to(torch.float32)
         if emb.shape[0] + max_new + 1 > self.engine.max_ctx:
             raise ValueError("prompt + max_new_tokens exceeds the KV-cache capacity")

@@ -114,8 +114,10 @@ def gemm(a, w, *, w_up=None, bias=None, act=None, scale=None, resid=None, out=No
 
 
 def attention(q, k, v, out, *, B, Hq, Hkv, Sq, Sk, d, ldq, hsq, ldk, hsk, ldv, hsv, ldo, bsq=0, bsk=0, bso=0, scale,
-              causal=False, q_off=0, klen=None, chunk=0, left=-1, p=None, ldp=0, hsp=0, bias_u=None, bias_v=None):
-    _dev(q, k, v, out)
+              causal=False, q_off=0, klen=None, chunk=0, left=-1, p=None, ldp=0, hsp=0, bias_u=None, bias_v=None, klens=None):
+    """klens: int32 device tensor [B], batch b masks keys >= klens[b] (the pad mask of a padded batch); klen must then be
+    their maximum (None: Sk, always a valid bound)."""
+    _dev(q, k, v, out, klens)
     for t, nm in ((q, "q"), (k, "k"), (v, "v"), (out, "out"), (p, "p")):
         _c(t, nm)
     lib = _lib.load()
@@ -133,8 +135,17 @@ def attention(q, k, v, out, *, B, Hq, Hkv, Sq, Sk, d, ldq, hsq, ldk, hsk, ldv, h
     a.klen = Sk if klen is None else int(klen)
     a.chunk, a.left = int(chunk), int(left)
     a.scale = float(scale)
+    a.klens = _klens(klens, B)
     check(lib.vh_attention(C.byref(a), _stream()), "vh_attention")
     return out
+
+
+def _klens(klens, B):
+    if klens is None:
+        return None
+    if klens.dtype != torch.int32 or klens.ndim != 1 or klens.shape[0] != B or not klens.is_contiguous():
+        raise ValueError(f"klens must be a contiguous int32 tensor of {B} entries")
+    return klens.data_ptr()
 
 
 class EncoderScratch:
@@ -175,12 +186,13 @@ def encoder_scratch(M, Cw, F, device):
 
 
 def encoder_layer(x, h_in, h_out, L, sc, *, heads, B, act, eps, next_norm=None, p=None, bias_u=None, bias_v=None, klen=-1, chunk=0,
-                  left=-1, planes=False):
+                  left=-1, planes=False, klens=None):
     """One pre-norm transformer block in ONE library call (vh_encoder_layer): x [M, C] updated in place, h_in = LN(x; norm1),
     h_out = LN(x_out; next_norm) when next_norm = (w, b) is given.  L: dict of this layer's weights (qkv_w, qkv_b, proj_w,
     proj_b, ls1?, n2w, n2b, fc1_w, fc1_b, fc2_w, fc2_b, ls2?).  planes=True: h_in / h_out hold bf16 hi/lo planes (split_planes_into) in
-    their M * C * 4 bytes and the Linears run on the weight-streaming GEMM (vita_hip.h: vh_encoder_layer_args.planes)."""
-    _dev(x, h_in)
+    their M * C * 4 bytes and the Linears run on the weight-streaming GEMM (vita_hip.h: vh_encoder_layer_args.planes).
+    klens: int32 device tensor [B] of per-sequence key lengths (klen = their maximum)."""
+    _dev(x, h_in, klens)
     a = _lib.EncoderLayerArgs()
     a.x, a.h_in, a.h_out = x.data_ptr(), h_in.data_ptr(), (h_out.data_ptr() if next_norm is not None else None)
     a.M, a.C, a.F, a.heads, a.B = sc.M, sc.C, sc.F, int(heads), int(B)
@@ -200,6 +212,7 @@ def encoder_layer(x, h_in, h_out, L, sc, *, heads, B, act, eps, next_norm=None, 
     a.qkv, a.attn, a.hmid, a.mid = sc.qkv.data_ptr(), sc.attn.data_ptr(), sc.hmid.data_ptr(), sc.mid.data_ptr()
     a.ws, a.ws_bytes = sc.ws.data_ptr(), sc.ws.numel() * sc.ws.element_size()
     a.planes = int(bool(planes))
+    a.klens = _klens(klens, int(B))
     check(_lib.load().vh_encoder_layer(C.byref(a), _stream()), "vh_encoder_layer")
 
 
@@ -281,6 +294,32 @@ def audio_conv1(feats, mean, istd, w, b):
     check(_lib.load().vh_audio_conv1(_p(feats), _p(mean), _p(istd), _p(w), _p(b), _p(out), T, F, Cc, _stream()),
           "vh_audio_conv1")
     return out, T1, F1
+
+
+def audio_conv1_batch(feats, mean, istd, w, b):
+    """vh_audio_conv1_batch: feats fp32 [B, T, F] (clips padded to a common T) -> ([B * T1 * F1, C], T1, F1), clip after clip."""
+    _dev(feats, w)
+    feats = _dense(_f32(feats, "feats"))
+    Bn, T, F = feats.shape
+    Cc = w.shape[0]
+    T1, F1 = (T - 3) // 2 + 1, (F - 3) // 2 + 1
+    out = torch.empty((Bn * T1 * F1, Cc), dtype=torch.float32, device=feats.device)
+    check(_lib.load().vh_audio_conv1_batch(_p(feats), _p(mean), _p(istd), _p(w), _p(b), _p(out), Bn, T, F, Cc, _stream()),
+          "vh_audio_conv1_batch")
+    return out, T1, F1
+
+
+def audio_mask_rows(x, klens, B, gap):
+    """vh_audio_mask_rows: x fp32 [B * S, cols] -> [B * (S + gap), cols] with rows >= klens[b] of clip b (and its gap rows) zero."""
+    _dev(x, klens)
+    _f32(_c(x, "x"), "x")
+    if x.shape[0] % B:
+        raise ValueError("audio_mask_rows: rows must be a multiple of B")
+    Sn, cols = x.shape[0] // B, x.shape[1]
+    out = torch.empty((B * (Sn + gap), cols), dtype=torch.float32, device=x.device)
+    check(_lib.load().vh_audio_mask_rows(_p(x), x.stride(0), _p(out), out.stride(0), _klens(klens, B), B, Sn, int(gap), cols,
+                                         _stream()), "vh_audio_mask_rows")
+    return out
 
 
 def embed_splice(kind, idx, embed, img, aud, H):

@@ -218,8 +218,6 @@ class LLM:
             else:
                 feats = audios[0].float()[None]
             lens = torch.tensor([int(a.shape[0]) for a in audios])
-            if len({int(a.shape[0]) for a in audios}) > 1:
-                raise NotImplementedError("clips of different lengths in one request are not batched yet")
             normalized = True                # WhaleFeatureExtractor already applied CMVN
         else:
             feats, lens = torch.zeros((1, 400, enc.acfg.input_dim)), torch.tensor([400])
@@ -236,7 +234,7 @@ class LLM:
             dev = self.model.device
             out = self.model.prepare_inputs_labels_for_multimodal(
                 torch.tensor([req["sent"]], dtype=torch.long, device=dev), None, None, None, None, req["pix"],
-                {"audios": req["feats"], "lengths": req["lens"]})
+                {"audios": req["feats"], "lengths": req["lens"]}, audio_valid_rows=True)
         finally:
             enc.normalized_input = False
         return out[4][0].to(torch.float32)
@@ -252,7 +250,8 @@ class LLM:
             out = self.model.generate(torch.tensor([sent], dtype=torch.long, device=dev), images=pix,
                                       audios={"audios": feats.to(dev), "lengths": lens.to(dev)}, num_beams=1,
                                       return_dict_in_generate=True, max_new_tokens=max_tokens,
-                                      eos_token_id=list(req["eos"]), streamer=streamer, **sample_kwargs(sp))
+                                      eos_token_id=list(req["eos"]), streamer=streamer, audio_valid_rows=True,
+                                      **sample_kwargs(sp))
         finally:
             enc.normalized_input = False
         gen = out.sequences[0, len(sent):].tolist()
