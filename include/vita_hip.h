@@ -99,7 +99,11 @@ int vh_gemm_ps(const vh_gemm_ps_args* args, void* stream);
 int vh_split_planes(const float* x, long ldx, uint16_t* hi, uint16_t* lo, long ldo, int rows, int cols, void* stream);
 /* vh_gemm_ps on int8 weights: args->W / W_up must be null; W (and W_up: GLU) int8 with args->ldw /
  * w_group_stride counted in int8 elements; column n of group e is scaled by s[e * s_group_stride + n] (s_up for the up half).
- * Always the 12-wave specialised kernel. */
+ * Always the 12-wave specialised kernel (vh_tune "ps_cfg" is ignored; "ps_xcd" and "ps_nt" apply).  Every int8 value is a legal
+ * weight: -128, which vh_quant_rows_i8 never emits, is converted like the others and contributes exactly -128 s.  The weight
+ * scale is applied to the K sum (each slab's under a K split) BEFORE bias, act, scale and resid.  Refused with VH_E_SHAPE, before
+ * anything is launched or written: K % 64 != 0, ksplit > K / 64 or < -8, a K split (ksplit > 1 or < 0) with W_up, bias, scale,
+ * resid, act or C_hi, ksplit < 0 without nslab_out, group_off with ngroups > 8, ldw * N >= 2^32. */
 int vh_gemm_ps_i8(const vh_gemm_ps_args* args, const int8_t* W, const float* s, const int8_t* W_up, const float* s_up,
                   long s_group_stride, void* stream);
 

@@ -45,6 +45,48 @@ CASES = {c.name: c for c in [
 # group) reach the specialised kernel's schedule only through the forced ps_cfg 2.
 TP_CASES = ("uniform", "skew")             # the TP shard widths and the overlap halves run on these two
 
+# ---- the int8 form's extra cases (tests/test_moe_gemm_i8_gpu.py; int8 ALWAYS runs the specialised kernel, at any row count) --------
+# an iteration of a few concurrent sequences at the released widths: rows per expert (tests/test_ops_gpu.py:
+# test_gemm_ps_device_chosen_ksplit_few_rows)
+DECODE_CNTS = ((2, 0, 1, 0, 0, 2, 0, 1), (1, 1, 1, 0, 1, 1, 0, 1), (3, 2, 4, 1, 2, 1, 2, 1), (6, 0, 0, 0, 0, 0, 0, 0))
+# short and odd K: 1 .. 5 stages of 64 pin the stagers' prologue (stage 0, half each), the clamped re-load past a tile's end and the
+# stage parity of the two stagers; N with a tail that is not a multiple of 4, one below the GLU / plain tile width and one above
+SMALL_K = (64, 128, 192, 256, 320)
+SMALL_N = (130, 390)
+SMALL_ROWS = {1: (0, 1, 0), 17: (1, 0, 16), 200: (7, 0, 193)}      # M -> rows per group of the grouped form (3 groups)
+
+
+def small_cases():
+    """(M, N, K, glu, grouped, ksplit) of the short-K section: ksplit 1 everywhere, and for plain also the largest legal fixed
+    split, K / 64 slabs of ONE stage each."""
+    out = []
+    for K in SMALL_K:
+        for M in SMALL_ROWS:
+            for N in SMALL_N:
+                for grouped in (True, False):
+                    out.append((M, N, K, True, grouped, 1))
+                    out.append((M, N, K, False, grouped, 1))
+                    if K > 64:
+                        out.append((M, N, K, False, grouped, K // 64))
+    return out
+
+
+def i8_rt_cap(M, N, glu, ksplit, cus=256):
+    """vhk_gemm_ps_i8's row-tile cap of an UNGROUPED call with a fixed split: the smallest cap 3 .. 11 whose tiles still fit one round
+    (more, shorter m-tiles while blocks would idle); 0 = none (12)."""
+    grid = max(cus & ~7, 8)
+    nrt, NT = (M + 15) >> 4, (N + (127 if glu else 255)) // (128 if glu else 256)
+    for c in range(3, 12):
+        if ((nrt + c - 1) // c) * NT * ksplit <= grid:
+            return c
+    return 0
+
+
+def k_slices(K, KS):
+    """(k0, nk) in stages of 64 of every K slice: TileCtx k0 / nk of for_each_tile."""
+    nk_total = K >> 6
+    return [((nk_total * ks) // KS, (nk_total * (ks + 1)) // KS - (nk_total * ks) // KS) for ks in range(KS)]
+
 
 # ---- the schedule, restated -------------------------------------------------------------------------------------------------------
 @dataclass(frozen=True)
@@ -83,14 +125,16 @@ def device_ksplit(MT, NT, nk_total, ksplit, nb):
     return KS
 
 
-def schedule(rows, N, K, glu, ksplit=1, cus=256):
-    """for_each_tile<GLU, 12> of k_gemm_sp for grouped rows (tuple of rows per group) or a plain GEMM (rows = (M,), no groups)."""
+def schedule(rows, N, K, glu, ksplit=1, cus=256, cap=0):
+    """for_each_tile<GLU, 12> of k_gemm_sp for grouped rows (tuple of rows per group) or a plain GEMM (rows = (M,), no groups).
+    cap: VhGemmPsArgs.rt_cap (0 < cap < 12 shortens the m-tiles)."""
     NOUT = 128 if glu else 256
     NT = (N + NOUT - 1) // NOUT
     nk_total = K >> 6
     nb = (cus & ~7) // 8
     rows = list(rows)
-    mtiles = lambda r: (((r + 15) >> 4) + RTMAX - 1) // RTMAX    # noqa: E731
+    cap = cap if 0 < cap < RTMAX else RTMAX
+    mtiles = lambda r: (((r + 15) >> 4) + cap - 1) // cap        # noqa: E731
     ordr = sorted(range(len(rows)), key=lambda e: -rows[e])        # stable, as the kernel's insertion sort
     MT = sum(mtiles(rows[e]) for e in ordr)
     KS = ksplit if ksplit > 1 else 1

@@ -112,6 +112,46 @@ def test_quant_rows_i8_null_pointers():
     assert lib.vh_quant_rows_i8(None, 1, 64, 64, 0, 64, None, 64, None, None) == -2
 
 
+def test_gemm_ps_i8_refusals():
+    """vh_gemm_ps_i8 refuses these before any device work (VH_E_SHAPE, the reason in vh_last_error).  M = 0 throughout: every check
+    runs before the launcher's no-rows return, so a check that stopped refusing would show as rc 0 here without a launch on the
+    fake pointers.  That a refused call with rows writes nothing is checked on the GPU:
+    tests/test_moe_gemm_i8_gpu.py::test_refusals_write_nothing."""
+    from vita_amd._lib import GemmPsArgs
+    lib = _lib()
+    fake = 0x1000
+
+    def refused(why, glu=False, **kw):
+        a = GemmPsArgs()
+        a.A_hi, a.A_lo, a.lda, a.ldw, a.C, a.ldc = fake, fake, 256, 256, fake, 256
+        a.M, a.N, a.K, a.ksplit, a.c_split_stride = 0, 256, 256, 1, 32 * 256
+        for k, v in kw.items():
+            setattr(a, k, v)
+        rc = lib.vh_gemm_ps_i8(C.byref(a), fake, fake, fake if glu else None, fake if glu else None, 256, None)
+        assert rc == -1, (kw, rc)
+        msg = lib.vh_last_error()
+        assert msg.startswith(b"vh_gemm_ps_i8: ") and why in msg, (kw, msg)
+
+    refused(b"multiple of 64", K=96)                                  # lda, ldw % 8 == 0: K is what is refused
+    refused(b"multiple of 64", K=32)
+    refused(b"above K / 64", ksplit=5)                                # more slabs than K stages (K / 64 = 4)
+    refused(b"below -8", ksplit=-9, nslab_out=fake)
+    refused(b"needs nslab_out", ksplit=-4)
+    for ks in (2, -2):                                                # a K split with GLU, an epilogue term or planes
+        split = b"a K split takes a plain GEMM"
+        refused(split, glu=True, ksplit=ks, nslab_out=fake)
+        for term in ("bias", "scale", "resid"):
+            refused(split, ksplit=ks, nslab_out=fake, **{term: fake})
+        refused(split, ksplit=ks, nslab_out=fake, act=3)
+        refused(split, ksplit=ks, nslab_out=fake, C_hi=fake, C_lo=fake, ldc_split=256)
+        refused(split, ksplit=ks, nslab_out=fake, C=None, C_hi=fake, C_lo=fake, ldc_split=256)
+    refused(b"more than 8 groups", group_off=fake, ngroups=9)         # the tile list holds 8 groups
+    refused(b"2^32", ldw=1 << 20, N=4096)                             # 32-bit per-lane byte offsets inside a group
+    a = GemmPsArgs()
+    a.A_hi, a.A_lo, a.lda, a.ldw, a.C, a.ldc, a.N, a.K, a.W = fake, fake, 256, 256, fake, 256, 256, 256, fake
+    assert lib.vh_gemm_ps_i8(C.byref(a), fake, fake, None, None, 256, None) == -2       # args->W next to the int8 weights
+
+
 def test_unknown_quantization_raises():
     from vita_amd.serving import LLM
     with pytest.raises(ValueError):

@@ -68,3 +68,50 @@ def test_restated_schedule_is_a_partition(name, proj, ksplit):
             assert b == pos, f"{key}: gap or overlap at row {pos}"
             pos = e
         assert pos == M
+
+
+# ---- the int8 form (tests/test_moe_gemm_i8_gpu.py): ALWAYS the specialised schedule, at any row count ------------------------------
+def _i8_runs():
+    """(projection, Schedule, K) of every launch shape of the int8 module's sections a - d on a 256-CU part."""
+    runs = []
+    for case in mc.CASES.values():                                                        # a. released widths
+        runs.append(("gateup", mc.gateup_schedule(case.rows), mc.H))
+        runs += [("down", mc.down_schedule(case.rows, ksplit=ks), mc.I) for ks in (mc.MOE_KSPLIT, 1, 2, 3)]
+    for name in mc.TP_CASES:                                                              # b. TP shards and the overlap halves
+        for it in mc.TP_WIDTHS:
+            runs.append(("gateup", mc.gateup_schedule(mc.CASES[name].rows, N=it), mc.H))
+            runs += [("down", mc.down_schedule(mc.CASES[name].rows, K=it, N=n), it) for n in (mc.H, mc.H // 2)]
+    for cnt in mc.DECODE_CNTS:                                                            # c. batched-decode shapes
+        runs += [("gateup", mc.gateup_schedule(cnt), mc.H), ("down", mc.down_schedule(cnt), mc.I)]
+    for (M, N, K, glu, grouped, ksplit) in mc.small_cases():                              # d. short and odd K
+        rows = mc.SMALL_ROWS[M] if grouped else (M,)
+        cap = 0 if grouped else mc.i8_rt_cap(M, N, glu, ksplit)
+        runs.append(("gateup" if glu else "down", mc.schedule(rows, N, K, glu, ksplit=ksplit, cap=cap), K))
+    return runs
+
+
+@pytest.mark.parametrize("proj", ["gateup", "down"])
+def test_i8_runs_reach_every_schedule_path(proj):
+    runs = [(s, K) for p, s, K in _i8_runs() if p == proj]
+    rts = {t.rt for s, _ in runs for t in s.tiles}
+    halves = {t.half for s, _ in runs for t in s.tiles if t.half >= 0}
+    assert rts == set(range(1, mc.RTMAX + 1)), f"{proj}: row-tile counts never run: {sorted(set(range(1, 13)) - rts)}"
+    assert halves == {0, 1}, f"{proj}: M-split tail halves reached: {sorted(halves)}"
+    assert any(s.empty_halves for s, _ in runs), f"{proj}: no run has an M-split tail whose second half is empty"
+    assert any(s.R == 0 for s, _ in runs), f"{proj}: no run has fewer tiles than blocks (R = 0)"
+    assert any(s.r > 0 and not s.split_tail for s, _ in runs), f"{proj}: no run has a partial last round that is not M-split"
+    # stage counts of the K slices some tile runs: the two stagers alternate stages, so an odd and an even count end on different
+    # stagers; a 1-stage slice is the prologue alone
+    nks = {mc.k_slices(K, s.KS)[t.ks][1] for s, K in runs for t in s.tiles}
+    assert any(n % 2 for n in nks) and any(n % 2 == 0 for n in nks), f"{proj}: stage counts reached: {sorted(nks)}"
+    assert 1 in nks, f"{proj}: no 1-stage K slice"
+    assert {1, 2, 3, 4, 5} <= nks, f"{proj}: short slices reached: {sorted(n for n in nks if n <= 5)}"
+
+
+def test_i8_small_cases_reach_the_rt_cap_selection():
+    """the ungrouped short-K calls take vhk_gemm_ps_i8's rt_cap branch: a cap below 12 that changes the m-tiling is reached, and
+    the largest fixed split has one stage per slab."""
+    caps = {(M, mc.i8_rt_cap(M, N, glu, ks)) for (M, N, K, glu, grouped, ks) in mc.small_cases() if not grouped}
+    assert (200, 3) in caps                                                               # 13 row tiles -> 5 m-tiles of <= 3
+    s = mc.schedule((200,), 390, 320, False, ksplit=5, cap=3)
+    assert s.KS == 5 and [nk for _, nk in mc.k_slices(320, 5)] == [1] * 5 and max(t.mi for t in s.tiles) == 4

@@ -119,7 +119,9 @@ int vh_gemm_ps_i8(const vh_gemm_ps_args* a, const int8_t* W, const float* s, con
     g.ksplit = a->ksplit; g.c_split_stride = a->c_split_stride; g.nslab_out = a->nslab_out;
     if ((size_t)a->lda * 2 * (size_t)(a->M > 0 ? a->M : 1) >= (1ull << 32))
         return fail(VH_E_SHAPE, "vh_gemm_ps_i8: activation plane above the 32-bit offset range");
-    return check_launch("vh_gemm_ps_i8", vhk_gemm_ps_i8(S(stream), g, VhPsI8{W, W_up, s, s_up, s_group_stride}));
+    const VhPsI8 q{W, W_up, s, s_up, s_group_stride};
+    if (const char* why = vhk_gemm_ps_i8_refusal(g, q)) return fail(VH_E_SHAPE, "vh_gemm_ps_i8: %s", why);
+    return check_launch("vh_gemm_ps_i8", vhk_gemm_ps_i8(S(stream), g, q));
 }
 int vh_quant_rows_i8(const uint16_t* w, long rows, int cols, long ld_src, int col0, int ncols, int8_t* q, long ld_dst, float* s,
                      void* stream) {

@@ -410,19 +410,30 @@ void k_gemm_sp_i8(const VhGemmPsArgs p, const VhPsI8 q8) {
 
 }  // namespace
 
+// why vhk_gemm_ps_i8 refuses these arguments (nullptr: it takes them).  Every check runs before anything is launched or written.
+const char* vhk_gemm_ps_i8_refusal(const VhGemmPsArgs& a, const VhPsI8& q) {
+    if (a.K <= 0 || a.K % 64 != 0) return "K must be a positive multiple of 64";
+    if (a.M < 0 || a.N <= 0) return "M < 0 or N <= 0";
+    if ((a.lda % 8) != 0 || (a.ldw % 8) != 0) return "lda % 8 / ldw % 8 alignment";
+    if (a.W || a.W_up || !q.W || !q.s || (q.W_up != nullptr) != (q.s_up != nullptr)) return "weight / scale pointers";
+    if (!a.A_hi || !a.A_lo || (!a.C && !a.C_hi) || (a.C_hi && !a.C_lo)) return "activation / output pointers";
+    const bool glu = q.W_up != nullptr;
+    const int ksplit = a.ksplit == 0 ? 1 : a.ksplit;
+    if (ksplit < -8) return "ksplit below -8";
+    if ((ksplit > 1 || ksplit < 0) && (glu || a.bias || a.scale || a.resid || a.act != VH_ACT_NONE || a.C_hi || !a.C))
+        return "a K split takes a plain GEMM into fp32 C (no W_up, bias, scale, resid, act or planes)";
+    if (ksplit < 0 && !a.nslab_out) return "a device-chosen K split needs nslab_out";
+    if (ksplit > (a.K >> 6)) return "ksplit above K / 64";
+    if (a.group_off && a.ngroups > 8) return "more than 8 groups";
+    if ((size_t)a.ldw * (size_t)a.N >= (1ull << 32)) return "ldw * N reaches 2^32";      // 32-bit per-lane byte offsets inside one group
+    return nullptr;
+}
+
 int vhk_gemm_ps_i8(hipStream_t st, const VhGemmPsArgs& a0, const VhPsI8& q) {
     VhGemmPsArgs a = a0;
-    if (a.K <= 0 || a.K % 64 != 0 || a.M < 0 || a.N <= 0 || (a.lda % 8) != 0 || (a.ldw % 8) != 0) return -1;
-    if (a.W || a.W_up || !q.W || !q.s || (q.W_up != nullptr) != (q.s_up != nullptr)) return -1;
-    if (!a.A_hi || !a.A_lo || (!a.C && !a.C_hi) || (a.C_hi && !a.C_lo)) return -1;
+    if (vhk_gemm_ps_i8_refusal(a, q)) return -1;
     const bool glu = q.W_up != nullptr;
     if (a.ksplit == 0) a.ksplit = 1;
-    if (a.ksplit < -8) return -1;
-    if ((a.ksplit > 1 || a.ksplit < 0) && (glu || a.bias || a.scale || a.resid || a.act != VH_ACT_NONE || a.C_hi || !a.C)) return -1;
-    if (a.ksplit < 0 && !a.nslab_out) return -1;
-    if (a.ksplit > (a.K >> 6)) return -1;
-    if (a.group_off && a.ngroups > 8) return -1;
-    if ((size_t)a.ldw * (size_t)a.N >= (1ull << 32)) return -1;      // 32-bit per-lane byte offsets inside one group
     if (a.M == 0) return 0;
     int grid = vh_num_cus() & ~7;
     if (grid < 8) grid = 8;

@@ -238,6 +238,7 @@ struct VhPsI8 {
     const float* s; const float* s_up; long s_group_stride;
 };
 int vhk_gemm_ps_i8(hipStream_t st, const VhGemmPsArgs& a, const VhPsI8& q);
+const char* vhk_gemm_ps_i8_refusal(const VhGemmPsArgs& a, const VhPsI8& q);   // nullptr, or why vhk_gemm_ps_i8 returns -1
 // w[rows][ld_src] bf16 -> q[rows][ld_dst] int8 (columns [col0, col0 + ncols)) + s[rows] fp32, the scale over all `cols`
 int vhk_quant_rows_i8(hipStream_t st, const uint16_t* w, long rows, int cols, long ld_src, int col0, int ncols, int8_t* q,
                       long ld_dst, float* s);

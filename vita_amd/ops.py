@@ -355,20 +355,14 @@ def split_planes_into(x, buf):
     return buf
 
 
-def gemm_ps(a_hi, a_lo, w, *, w_up=None, bias=None, act=None, scale=None, resid=None, out=None, out_split=False,
-            a_rowidx=None, m=None, c_rowidx=None, group_off=None, ngroups=0, w_group_stride=0, wide=False, ksplit=1,
-            nslab_out=None, out_planes=None):
-    """Weight-streaming GEMM on pre-split activations (vh_gemm_ps).  Returns fp32 out, or (hi, lo) planes when
-    out_split=True (out_planes: write them into these two bf16 [rows, N] views of equal row stride instead of new tensors).
-    ksplit > 1: `out` must be [ksplit, rows, N] (partial sums per K range; the caller adds them)."""
-    _dev(a_hi, a_lo, w)
-    _bf16(a_hi, "a_hi"); _bf16(a_lo, "a_lo"); _bf16(w, "w")
+def _gemm_ps_args(a_hi, a_lo, w, *, bias, act, scale, resid, out, out_split, a_rowidx, m, c_rowidx, group_off, ngroups,
+                  w_group_stride, ksplit, nslab_out, out_planes):
+    """vh_gemm_ps_args of gemm_ps / gemm_ps_i8 without the weight pointers -> (args, planes or None, out or None)."""
     g = _lib.GemmPsArgs()
     N, K = int(w.shape[-2]), int(w.shape[-1])
     g.A_hi, g.A_lo, g.lda = a_hi.data_ptr(), a_lo.data_ptr(), int(a_hi.stride(0))
     g.a_rowidx = a_rowidx.data_ptr() if a_rowidx is not None else None
-    g.W = w.data_ptr(); g.W_up = w_up.data_ptr() if w_up is not None else None
-    g.ldw, g.w_group_stride = K, int(w_group_stride)
+    g.ldw, g.w_group_stride = int(w.stride(-2)), int(w_group_stride)
     g.group_off = group_off.data_ptr() if group_off is not None else None
     g.ngroups = int(ngroups)
     M = int(m if m is not None else (a_rowidx.shape[0] if a_rowidx is not None else a_hi.shape[0]))
@@ -387,7 +381,7 @@ def gemm_ps(a_hi, a_lo, w, *, w_up=None, bias=None, act=None, scale=None, resid=
             planes = (torch.empty((M, N), dtype=torch.bfloat16, device=w.device),
                       torch.empty((M, N), dtype=torch.bfloat16, device=w.device))
         g.C_hi, g.C_lo, g.ldc_split = planes[0].data_ptr(), planes[1].data_ptr(), int(planes[0].stride(0))
-    else:
+    if not out_split or out is not None:
         if out is None:
             out = torch.empty((M, N), dtype=torch.float32, device=w.device)
         if ksplit > 1 or ksplit < 0:
@@ -403,8 +397,52 @@ def gemm_ps(a_hi, a_lo, w, *, w_up=None, bias=None, act=None, scale=None, resid=
     g.scale = scale.data_ptr() if scale is not None else None
     if resid is not None:
         g.resid, g.ldr = resid.data_ptr(), int(resid.stride(0))
-    g.M, g.N, g.K, g.act, g.wide = M, N, K, ACT[act], int(bool(wide))
+    g.M, g.N, g.K, g.act = M, N, K, ACT[act]
+    return g, planes, out
+
+
+def gemm_ps(a_hi, a_lo, w, *, w_up=None, bias=None, act=None, scale=None, resid=None, out=None, out_split=False,
+            a_rowidx=None, m=None, c_rowidx=None, group_off=None, ngroups=0, w_group_stride=0, wide=False, ksplit=1,
+            nslab_out=None, out_planes=None):
+    """Weight-streaming GEMM on pre-split activations (vh_gemm_ps).  Returns fp32 out, or (hi, lo) planes when
+    out_split=True (out_planes: write them into these two bf16 [rows, N] views of equal row stride instead of new tensors).
+    ksplit > 1: `out` must be [ksplit, rows, N] (partial sums per K range; the caller adds them)."""
+    _dev(a_hi, a_lo, w)
+    _bf16(a_hi, "a_hi"); _bf16(a_lo, "a_lo"); _bf16(w, "w")
+    g, planes, out = _gemm_ps_args(a_hi, a_lo, w, bias=bias, act=act, scale=scale, resid=resid, out=None if out_split else out,
+                                   out_split=out_split, a_rowidx=a_rowidx, m=m, c_rowidx=c_rowidx, group_off=group_off,
+                                   ngroups=ngroups, w_group_stride=w_group_stride, ksplit=ksplit, nslab_out=nslab_out,
+                                   out_planes=out_planes)
+    g.W = w.data_ptr(); g.W_up = w_up.data_ptr() if w_up is not None else None
+    g.ldw = int(w.shape[-1])
+    g.wide = int(bool(wide))
     check(_lib.load().vh_gemm_ps(C.byref(g), _stream()), "vh_gemm_ps")
+    return planes if out_split else out
+
+
+def gemm_ps_i8(a_hi, a_lo, w, s, *, w_up=None, s_up=None, s_group_stride=0, bias=None, act=None, scale=None, resid=None, out=None,
+               out_split=False, a_rowidx=None, m=None, c_rowidx=None, group_off=None, ngroups=0, w_group_stride=0, ksplit=1,
+               nslab_out=None, out_planes=None):
+    """gemm_ps on int8 weights (vh_gemm_ps_i8): w / w_up int8 [.., N, K] (rows contiguous; the row stride is taken from
+    the tensor, so a column range of a wider matrix is a legal operand), s / s_up fp32 scales, column n of group e scaled by
+    s[e * s_group_stride + n].  The keywords are gemm_ps's without `wide`; with out_split=True an fp32 `out` may be given as well
+    (the kernel then writes C and the planes) and the result is (hi, lo)."""
+    _dev(a_hi, a_lo, w, s, w_up, s_up)
+    _bf16(a_hi, "a_hi"); _bf16(a_lo, "a_lo")
+    for t, nm in ((w, "w"), (w_up, "w_up")):
+        if t is not None and (t.dtype != torch.int8 or t.stride(-1) != 1):
+            raise TypeError(f"{nm} must be int8 with contiguous rows, got {t.dtype} strides {t.stride()}")
+    for t, nm in ((s, "s"), (s_up, "s_up")):
+        if t is not None:
+            _f32(t, nm)
+    if (w_up is None) != (s_up is None):
+        raise ValueError("w_up and s_up go together")
+    if w_up is not None and (w_up.shape[-2:] != w.shape[-2:] or w_up.stride(-2) != w.stride(-2)):
+        raise ValueError("w_up must have w's [N, K] and row stride")
+    g, planes, out = _gemm_ps_args(a_hi, a_lo, w, bias=bias, act=act, scale=scale, resid=resid, out=out, out_split=out_split,
+                                   a_rowidx=a_rowidx, m=m, c_rowidx=c_rowidx, group_off=group_off, ngroups=ngroups,
+                                   w_group_stride=w_group_stride, ksplit=ksplit, nslab_out=nslab_out, out_planes=out_planes)
+    check(_lib.load().vh_gemm_ps_i8(C.byref(g), _p(w), _p(s), _p(w_up), _p(s_up), int(s_group_stride), _stream()), "vh_gemm_ps_i8")
     return planes if out_split else out
 
 
