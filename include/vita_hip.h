@@ -238,6 +238,9 @@ typedef struct {
                              through the all-reduce hook.  vocab_n == 0: the whole table on every rank. */
     int max_seqs;         /* > 0: slots for concurrent sequences over the paged KV cache (vh_mixtral_seq_*); max_ctx is then
                              the POOL size in tokens (a multiple of 64) shared by all sequences */
+    int penalty_tables;   /* != 0: a token table uint32[vocab] for the engine and for every sequence slot (vh_logit_rules penalties) */
+    int max_logprobs;     /* 1 .. 20: log-probability buffers for the engine and every slot ([max_new], [max_new][max_logprobs] x 2);
+                             both 0: the workspace is what it was, the vh_logit_rules setters answer VH_E_ARG */
 } vh_mixtral_cfg;
 
 typedef struct {
@@ -450,6 +453,62 @@ int vh_mixtral_seq_set_sampling(vh_mixtral_t* m, int seq, const vh_sampling* s /
 /* per-operator entry: tokens_out[r] = the draw of row r = logits + r * ld (ld = 0: the same row for every draw) at draw index
  *   draw0 + r, by the engine's device code.  logits fp32, V entries per row; tokens_out int[rows].                             */
 int vh_sample_rows(const float* logits, long ld, int rows, int V, const vh_sampling* s /* host */, int* tokens_out, void* stream);
+
+/* ---- logit rules: repetition / presence / frequency penalties and log-probabilities on the device (replaces HF
+ * RepetitionPenaltyLogitsProcessor — transformers generation/logits_process.py — and vLLM's apply_penalties + Sampler logprobs behind
+ * SamplingParams(repetition_penalty, presence_penalty, frequency_penalty, logprobs)) ----------------------------------------------
+ * History of a request: P = the SET of its prompt ids, c[v] = how often id v occurs in its output so far (the prefill's token is
+ * output 0).  The engine keeps both per request in a token table uint32 seen[vocab] (bit 31 = in P, low bits = c[v]) and counts every
+ * token it writes on the device, so multi-step decode stays host-free.
+ * Penalties: the fp32 logit x of id v becomes, each step a single IEEE fp32 operation without contraction, in this order
+ *   1. v in P or c[v] > 0:  x = x > 0 ? x / r : x * r          (r = repetition_penalty)
+ *   2.                      x = x - f * (float)c[v]            (f = frequency_penalty; a product, then a difference)
+ *   3. c[v] > 0:            x = x - p                          (p = presence_penalty)
+ * NaN stays NaN, +-inf follows IEEE.  The penalised value is what SELECTION sees (greedy argmax, the temperature-only Gumbel
+ * compare, the top-k / top-p filter); the kept logits rows stay RAW, as under sampling.  r = 1, f = p = 0 is "off": a request with
+ * neutral penalties and no logprobs launches exactly the kernels of an engine without rules.
+ * Logprobs: logprobs = K, 0 <= K <= max_logprobs <= 20, gives every generated token the log-probability of the chosen id and the K
+ * most probable ids with theirs, under log_softmax of the RAW fp32 logits row of that step (vLLM's default raw_logprobs, HF's
+ * output_logits view): x_v - (M + log sum_j exp(x_j - M)) in double, M the row maximum, the sum taken as one partial per wave added
+ * in wave order, rounded to fp32 once.  The top K are ordered by (logit descending, id ascending); entries past the vocabulary are
+ * id -1 and -inf; NaN logits rank as -inf and a row with nothing finite gives -inf everywhere.  logprobs = -1 is off.
+ * Accepted: finite r > 0, finite f and p, -1 <= logprobs <= cfg.max_logprobs; non-neutral penalties need cfg.penalty_tables,
+ * logprobs >= 0 needs cfg.max_logprobs > 0.  Under a vocab-sharded LM head (vocab_n > 0) non-neutral penalties and logprobs are refused
+ * (VH_E_ARG), as filters are; an unsharded head under tensor parallelism works unchanged (every rank holds the same row and table). */
+typedef struct {
+    float repetition_penalty, presence_penalty, frequency_penalty;
+    int logprobs;
+} vh_logit_rules;
+/* Rules of the single-sequence engine (vh_mixtral_prefill / decode) from the next prefill on.  The table is cleared, ids[0, n_prompt)
+ * are marked as prompt and ids[n_prompt, n_prompt + n_output) counted as outputs (how a recomputed sequence or a later turn gets its
+ * history back); a call without penalties (rules == NULL: off, or logprobs only) leaves it all zero.  The whole call is validated
+ * before anything changes: an id outside [0, vocab) or a bad value is VH_E_ARG and leaves the previous setting AND table in force.
+ * A call that has to write the table — one with penalties, or the first one without after a request that had them — waits for the
+ * device the workspace lives on (whichever device is current) and writes with a blocking copy; other calls touch nothing on the
+ * device.  vh_mixtral_reset restores "off"; seq_alloc / seq_free / reset do not touch a table, the next setter call on that
+ * engine / slot does. */
+int vh_mixtral_set_logit_rules(vh_mixtral_t* m, const vh_logit_rules* rules /* host, nullable */, const int* ids /* host */,
+                               int n_prompt, int n_output);
+/* the same for one sequence of the paged engine; seq_alloc, seq_free and vh_mixtral_reset restore "off" */
+int vh_mixtral_seq_set_logit_rules(vh_mixtral_t* m, int seq, const vh_logit_rules* rules /* host, nullable */,
+                                   const int* ids /* host */, int n_prompt, int n_output);
+/* Device pointers of the logprob buffers (null without cfg.max_logprobs): entry i belongs to generated token i of the current
+ * (re)prefill, as vh_mixtral_tokens.  token: fp32 [max_new]; top_ids: int [max_new][max_logprobs]; top: fp32 [max_new][max_logprobs]
+ * (the first K of a row are written). */
+const float* vh_mixtral_logprobs_token(const vh_mixtral_t* m);
+const int* vh_mixtral_logprobs_top_ids(const vh_mixtral_t* m);
+const float* vh_mixtral_logprobs_top(const vh_mixtral_t* m);
+const float* vh_mixtral_seq_logprobs_token(const vh_mixtral_t* m, int seq);
+const int* vh_mixtral_seq_logprobs_top_ids(const vh_mixtral_t* m, int seq);
+const float* vh_mixtral_seq_logprobs_top(const vh_mixtral_t* m, int seq);
+const uint32_t* vh_mixtral_seen(const vh_mixtral_t* m);                 /* the token tables (null without cfg.penalty_tables) */
+const uint32_t* vh_mixtral_seq_seen(const vh_mixtral_t* m, int seq);
+/* per-operator entry: the engine's device code on caller-provided rows (row r = logits + r * ld, V entries).  seen (nullable, device
+ * uint32[V]): one table for all rows; penalised_out (nullable, device fp32 [rows][V]) receives the penalised rows (rules->logprobs is
+ * not read).  lp_tok (nullable; then tokens, and for K > 0 lp_top_id and lp_top, must be set): tokens[r] is the chosen id of row r,
+ * lp_tok fp32 [rows], lp_top_id int [rows][K], lp_top fp32 [rows][K], 0 <= K <= 20, of the RAW rows. */
+int vh_logit_rules_rows(const float* logits, long ld, int rows, int V, const vh_logit_rules* rules /* host */, const uint32_t* seen,
+                        float* penalised_out, const int* tokens, float* lp_tok, int* lp_top_id, float* lp_top, int K, void* stream);
 
 /* Live HIP-event timing of the dominant kernel of a phase, on the stream the engine launches it on: stride > 0 samples the
  * DECODE gate|up expert GEMV of every stride-th layer, stride < 0 the PREFILL gate|up grouped GEMM of every |stride|-th layer

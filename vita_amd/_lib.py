@@ -97,6 +97,16 @@ def sampling(temperature=0.0, top_k=0, top_p=1.0, seed=0, draw0=0):
     return Sampling(float(temperature), int(top_k), float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, int(draw0))
 
 
+class LogitRules(C.Structure):
+    """vh_logit_rules: penalties and log-probabilities of one request (1, 0, 0, -1 = off)."""
+    _fields_ = [("repetition_penalty", c_float), ("presence_penalty", c_float), ("frequency_penalty", c_float), ("logprobs", c_int)]
+
+
+def logit_rules(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logprobs=-1):
+    return LogitRules(float(repetition_penalty), float(presence_penalty), float(frequency_penalty),
+                      -1 if logprobs is None else int(logprobs))
+
+
 class MixtralCfg(C.Structure):
     _fields_ = [
         ("hidden", c_int), ("n_layers", c_int), ("n_q_heads", c_int), ("n_kv_heads", c_int),
@@ -104,6 +114,7 @@ class MixtralCfg(C.Structure):
         ("rms_eps", c_float), ("max_ctx", c_int), ("max_prefill", c_int), ("max_new", c_int),
         ("tp_rank", c_int), ("tp_world", c_int), ("nsplit", c_int), ("logit_rows", c_int),
         ("vocab_lo", c_int), ("vocab_n", c_int), ("max_seqs", c_int),
+        ("penalty_tables", c_int), ("max_logprobs", c_int),
     ]
 
 
@@ -202,6 +213,18 @@ SIGNATURES = {
     "vh_mixtral_set_sampling": (c_int, [c_void_p, C.POINTER(Sampling)]),
     "vh_mixtral_seq_set_sampling": (c_int, [c_void_p, c_int, C.POINTER(Sampling)]),
     "vh_sample_rows": (c_int, [c_void_p, c_long, c_int, c_int, C.POINTER(Sampling), c_void_p, c_void_p]),
+    "vh_mixtral_set_logit_rules": (c_int, [c_void_p, C.POINTER(LogitRules), C.POINTER(c_int), c_int, c_int]),
+    "vh_mixtral_seq_set_logit_rules": (c_int, [c_void_p, c_int, C.POINTER(LogitRules), C.POINTER(c_int), c_int, c_int]),
+    "vh_mixtral_logprobs_token": (c_void_p, [c_void_p]),
+    "vh_mixtral_logprobs_top_ids": (c_void_p, [c_void_p]),
+    "vh_mixtral_logprobs_top": (c_void_p, [c_void_p]),
+    "vh_mixtral_seq_logprobs_token": (c_void_p, [c_void_p, c_int]),
+    "vh_mixtral_seq_logprobs_top_ids": (c_void_p, [c_void_p, c_int]),
+    "vh_mixtral_seq_logprobs_top": (c_void_p, [c_void_p, c_int]),
+    "vh_mixtral_seen": (c_void_p, [c_void_p]),
+    "vh_mixtral_seq_seen": (c_void_p, [c_void_p, c_int]),
+    "vh_logit_rules_rows": (c_int, [c_void_p, c_long, c_int, c_int, C.POINTER(LogitRules), c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_int, c_void_p]),
     "vh_mixtral_profile": (c_int, [c_void_p, c_int, c_int]),
     "vh_mixtral_profile_read": (c_int, [c_void_p, C.POINTER(C.c_double), C.POINTER(c_int)]),
 }

@@ -367,10 +367,16 @@ struct vh_mixtral {
     // and its generated ids.  The kernels see ONE sequence at a time: bind() points the engine's "current sequence"
     // members (xa .. out_tokens, table, host mirrors) at a sequence's slots, unbind() restores the default single-sequence
     // state, so prefill and decode are the same code for both.
+    // logit rules of one request (vh_logit_rules): penalties read the request's token table, K >= 0 runs k_dec_logprobs after the select
+    struct Rules {
+        float r = 1.f, f = 0.f, p = 0.f; int K = -1;
+        bool pen() const { return r != 1.f || f != 0.f || p != 0.f; }
+    };
     struct Seq {
         bool live = false;
         int host_pos = 0, poisoned = 0, npages = 0;
         VhSampleParams samp{};         // vh_mixtral_seq_set_sampling (T = 0: greedy)
+        Rules rules{};                 // vh_mixtral_seq_set_logit_rules (off)
         std::vector<int> pages;        // host mirror of the device table (sized once: uploads read from it)
     };
     std::vector<Seq> seqs;
@@ -386,19 +392,36 @@ struct vh_mixtral {
     int *l_attn_cnt[VH_BMAX] = {}, *l_route[VH_BMAX] = {}, *l_blk_idx[VH_BMAX] = {};
     const int* table = nullptr;        // device page table of the bound sequence; null = contiguous rows (default state)
     int bound = -1;
-    struct { float *xa, *xb, *da, *dm; int *counters, *out_tokens; int host_pos, poisoned; VhSampleParams samp; } dflt{};
+    struct { float *xa, *xb, *da, *dm; int *counters, *out_tokens; int host_pos, poisoned; VhSampleParams samp; Rules rules; } dflt{};
     VhSampleParams samp{};             // sampling of the bound sequence / of the single-sequence engine (T = 0: greedy)
+    Rules rules{};                     // logit rules of the bound sequence / of the single-sequence engine (off)
+    // state of the logit rules, one unit per owner: unit 0 = the single-sequence engine, unit 1 + s = sequence slot s
+    unsigned* seen_tab = nullptr;      // [1 + max_seqs][V] token tables (cfg.penalty_tables)
+    float *lp_tok = nullptr, *lp_top = nullptr; int* lp_top_id = nullptr;   // [1 + max_seqs][max_new] / [..][max_new][max_logprobs]
+    std::vector<char> seen_dirty;      // per unit: the table holds a history (a setter call without penalties clears it)
+    int device = -1;                   // the device the workspace lives on (the setters synchronise THAT device)
+    int lp_rows() const { return c.max_new > 0 ? c.max_new : 1; }
+    int unit() const { return bound + 1; }
+    unsigned* seen_of(int u) const { return seen_tab ? seen_tab + (size_t)u * V : nullptr; }
+    VhPenalty pen_of(const Rules& r, int u) const { return r.pen() ? VhPenalty{seen_of(u), r.r, r.f, r.p, 0} : VhPenalty{}; }
+    void logprob_slot(VhDecLogprobJob& j, int u, const Rules& r, const float* row, const int* ngen, const int* toks) const {
+        const int q = j.n++;
+        j.logits[q] = row; j.ngen[q] = ngen; j.tokens[q] = toks; j.K[q] = r.K;
+        j.lp_tok[q] = lp_tok + (size_t)u * lp_rows();
+        j.lp_top_id[q] = lp_top_id + (size_t)u * lp_rows() * c.max_logprobs;
+        j.lp_top[q] = lp_top + (size_t)u * lp_rows() * c.max_logprobs;
+    }
     float* samp_rows = nullptr;        // [VH_BMAX][V] logits rows of the batched head for sequences with a top-k / top-p filter
     int n_pages() const { return c.max_ctx / 64; }
     int live_seqs() const { int n = 0; for (const Seq& q : seqs) n += q.live; return n; }
     void bind(int s) {
-        dflt = {xa, xb, delta_attn, delta_moe, counters, out_tokens, host_pos, poisoned, samp};
+        dflt = {xa, xb, delta_attn, delta_moe, counters, out_tokens, host_pos, poisoned, samp, rules};
         float* x = seq_x + (size_t)s * 4 * H;
         xa = x; xb = x + H; delta_attn = x + 2 * H; delta_moe = x + 3 * H;
         counters = seq_counters + 4 * s;
         out_tokens = seq_tokens + (size_t)s * (c.max_new > 0 ? c.max_new : 1);
         table = seq_table + (size_t)s * max_splits;
-        host_pos = seqs[s].host_pos; poisoned = seqs[s].poisoned; samp = seqs[s].samp;
+        host_pos = seqs[s].host_pos; poisoned = seqs[s].poisoned; samp = seqs[s].samp; rules = seqs[s].rules;
         bound = s;
     }
     void unbind() {
@@ -406,7 +429,7 @@ struct vh_mixtral {
         q.host_pos = host_pos; q.poisoned = poisoned;
         xa = dflt.xa; xb = dflt.xb; delta_attn = dflt.da; delta_moe = dflt.dm;
         counters = dflt.counters; out_tokens = dflt.out_tokens;
-        host_pos = dflt.host_pos; poisoned = dflt.poisoned; samp = dflt.samp;
+        host_pos = dflt.host_pos; poisoned = dflt.poisoned; samp = dflt.samp; rules = dflt.rules;
         table = nullptr; bound = -1;
     }
     // pages covering positions [0, n_tokens) of sequence s; new table entries are uploaded on st.  -1: pool exhausted.
@@ -424,7 +447,7 @@ struct vh_mixtral {
     void release(int s) {
         Seq& q = seqs[s];
         for (int j = q.npages - 1; j >= 0; --j) free_pages.push_back(q.pages[j]);
-        q.npages = 0; q.live = false; q.host_pos = 0; q.poisoned = 0; q.samp = VhSampleParams{};
+        q.npages = 0; q.live = false; q.host_pos = 0; q.poisoned = 0; q.samp = VhSampleParams{}; q.rules = Rules{};
     }
     void init_seqs() {
         seqs.assign(c.max_seqs > 0 ? c.max_seqs : 0, Seq{});
@@ -513,6 +536,14 @@ struct vh_mixtral {
         }
         kcache = cv.take<float>((size_t)c.n_layers * nkv * c.max_ctx * hd);
         vcache = cv.take<float>((size_t)c.n_layers * nkv * c.max_ctx * hd);
+        // ---- logit rules (behind everything else: an engine without them is laid out as before) -----------------------------
+        const size_t units = 1 + (size_t)(c.max_seqs > 0 ? c.max_seqs : 0);
+        if (c.penalty_tables) seen_tab = cv.take<unsigned>(units * V);
+        if (c.max_logprobs > 0) {
+            lp_tok = cv.take<float>(units * lp_rows());
+            lp_top_id = cv.take<int>(units * lp_rows() * c.max_logprobs);
+            lp_top = cv.take<float>(units * lp_rows() * c.max_logprobs);
+        }
         return al(cv.off, 256);
     }
     // py layout: a K-split slab of a projection output (QKV, O) `ncols` wide holds max_prefill rows, one of the MoE down
@@ -579,6 +610,7 @@ int cfg_ok(const vh_mixtral_cfg* c) {
     if (c->vocab_n > 0 && c->vocab >= (1 << 24)) return fail(VH_E_SHAPE, "vocab-sharded head needs vocab < 2^24");
     if (c->max_seqs < 0 || c->max_seqs > 4096) return fail(VH_E_SHAPE, "max_seqs outside [0,4096]");
     if (c->max_seqs > 0 && (c->max_ctx % 64) != 0) return fail(VH_E_SHAPE, "paged KV cache: max_ctx must be a multiple of the 64-token page");
+    if (c->max_logprobs < 0 || c->max_logprobs > 20) return fail(VH_E_SHAPE, "max_logprobs outside [0,20]");
     return VH_OK;
 }
 int rccl_allreduce_cb(void* user, float* buf, long count, void* stream) {
@@ -621,6 +653,10 @@ vh_mixtral_t* vh_mixtral_create(const vh_mixtral_cfg* cfg, const vh_mixtral_laye
         return nullptr;
     }
     m->init_seqs();
+    m->seen_dirty.assign(1 + m->seqs.size(), 0);
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, workspace) == hipSuccess) m->device = at.device;
+    else (void)hipGetLastError();      // a host pointer (argument tests without a GPU): the current device is used
     return m;
 }
 
@@ -746,6 +782,7 @@ int vh_mixtral_reset(vh_mixtral_t* m, void* stream) {
         return fail(VH_E_HIP, "reset memset failed");
     m->host_pos = 0; m->poisoned = 0;
     m->samp = VhSampleParams{};                  // greedy again (released sequences too)
+    m->rules = vh_mixtral::Rules{};              // and no logit rules
     for (int s = 0; s < (int)m->seqs.size(); ++s)
         if (m->seqs[s].live) m->release(s);      // the pool is one: a reset returns every page
     return VH_OK;
@@ -792,6 +829,86 @@ int vh_sample_rows(const float* logits, long ld, int rows, int V, const vh_sampl
     const int rc = sampling_params(s, &p, "vh_sample_rows");
     if (rc != VH_OK) return rc;
     return check_launch("vh_sample_rows", vhk_sample_rows(S(stream), logits, ld, rows, V, p, tokens_out));
+}
+
+// ---- logit rules ------------------------------------------------------------------------------------------------------
+static int rules_values(const vh_logit_rules* r, int kmax, vh_mixtral::Rules* out, const char* what) {
+    *out = vh_mixtral::Rules{};
+    if (!r) return VH_OK;
+    if (!std::isfinite(r->repetition_penalty) || !(r->repetition_penalty > 0.f))
+        return fail(VH_E_ARG, "%s: repetition_penalty must be finite and > 0 (got %g)", what, (double)r->repetition_penalty);
+    if (!std::isfinite(r->presence_penalty) || !std::isfinite(r->frequency_penalty))
+        return fail(VH_E_ARG, "%s: presence_penalty and frequency_penalty must be finite", what);
+    if (r->logprobs < -1 || r->logprobs > kmax) return fail(VH_E_ARG, "%s: logprobs %d outside [-1, %d]", what, r->logprobs, kmax);
+    out->r = r->repetition_penalty; out->p = r->presence_penalty; out->f = r->frequency_penalty; out->K = r->logprobs;
+    return VH_OK;
+}
+// validate the whole call, then write unit u's table (penalties only) and hand the rules back; nothing changes on a refusal
+static int engine_rules(vh_mixtral* m, int u, const vh_logit_rules* r, const int* ids, int n_prompt, int n_output, vh_mixtral::Rules* out,
+                        const char* what) {
+    if (!m->c.penalty_tables && m->c.max_logprobs <= 0)
+        return fail(VH_E_ARG, "%s: the engine was created without penalty_tables and max_logprobs", what);
+    if (r && r->logprobs >= 0 && m->c.max_logprobs <= 0) return fail(VH_E_ARG, "%s: logprobs need cfg.max_logprobs > 0", what);
+    vh_mixtral::Rules v;
+    const int rc = rules_values(r, m->c.max_logprobs > 0 ? m->c.max_logprobs : 0, &v, what);
+    if (rc != VH_OK) return rc;
+    if (v.pen() && !m->c.penalty_tables) return fail(VH_E_ARG, "%s: penalties need cfg.penalty_tables", what);
+    if ((v.pen() || v.K >= 0) && m->c.vocab_n > 0)
+        return fail(VH_E_ARG, "%s: penalties and logprobs need an unsharded LM head (vocab_n = %d of %d)", what, m->c.vocab_n, m->V);
+    if (n_prompt < 0 || n_output < 0 || (!ids && n_prompt + (long)n_output > 0))
+        return fail(VH_E_ARG, "%s: bad history (n_prompt %d, n_output %d)", what, n_prompt, n_output);
+    const long n = (long)n_prompt + n_output;
+    for (long i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= m->V) return fail(VH_E_ARG, "%s: id %d at %ld is outside [0, %d)", what, ids[i], i, m->V);
+    // The table is rewritten (penalties) or cleared (it held a history and this request has no penalties).  It may still be read by
+    // steps in flight on any stream of the engine's device: wait for that device, then write with blocking calls.
+    if (v.pen() || (m->seen_tab && m->seen_dirty[u])) {
+        std::vector<unsigned> tab;
+        if (v.pen()) {
+            tab.assign((size_t)m->V, 0u);
+            for (long i = 0; i < n_prompt; ++i) tab[ids[i]] |= 0x80000000u;
+            for (long i = n_prompt; i < n; ++i) tab[ids[i]] += 1u;
+        }
+        int cur = -1;
+        const bool hop = m->device >= 0 && hipGetDevice(&cur) == hipSuccess && cur != m->device;
+        if (hop && hipSetDevice(m->device) != hipSuccess) return fail(VH_E_HIP, "%s: cannot select device %d", what, m->device);
+        const size_t bytes = (size_t)m->V * sizeof(unsigned);
+        bool ok = hipDeviceSynchronize() == hipSuccess;
+        ok = ok && (v.pen() ? hipMemcpy(m->seen_of(u), tab.data(), bytes, hipMemcpyHostToDevice) : hipMemset(m->seen_of(u), 0, bytes)) == hipSuccess;
+        ok = ok && hipDeviceSynchronize() == hipSuccess;
+        if (hop) (void)hipSetDevice(cur);
+        if (!ok) return fail(VH_E_HIP, "%s: token table upload failed", what);
+        m->seen_dirty[u] = v.pen() ? 1 : 0;
+    }
+    *out = v;
+    return VH_OK;
+}
+
+int vh_mixtral_set_logit_rules(vh_mixtral_t* m, const vh_logit_rules* r, const int* ids, int n_prompt, int n_output) {
+    if (!m) return fail(VH_E_ARG, "null engine");
+    vh_mixtral::Rules v;
+    const int rc = engine_rules(m, 0, r, ids, n_prompt, n_output, &v, "vh_mixtral_set_logit_rules");
+    if (rc != VH_OK) return rc;
+    m->rules = v;
+    return VH_OK;
+}
+
+int vh_logit_rules_rows(const float* logits, long ld, int rows, int V, const vh_logit_rules* r, const uint32_t* seen, float* penalised_out,
+                        const int* tokens, float* lp_tok, int* lp_top_id, float* lp_top, int K, void* stream) {
+    const char* what = "vh_logit_rules_rows";
+    if (!logits) return fail(VH_E_ARG, "%s: null pointer", what);
+    if (rows < 1 || V < 1 || ld < 0) return fail(VH_E_SHAPE, "%s: rows %d, V %d, ld %ld", what, rows, V, ld);
+    if (K < 0 || K > 20) return fail(VH_E_ARG, "%s: K %d outside [0, 20]", what, K);
+    if (lp_tok && (!tokens || (K > 0 && (!lp_top_id || !lp_top)))) return fail(VH_E_ARG, "%s: logprobs need tokens and the top-K buffers", what);
+    if (penalised_out && !r) return fail(VH_E_ARG, "%s: penalised_out needs rules", what);
+    vh_mixtral::Rules v;
+    vh_logit_rules rr = r ? *r : vh_logit_rules{1.f, 0.f, 0.f, -1};
+    rr.logprobs = -1;
+    const int rc = rules_values(&rr, 20, &v, what);
+    if (rc != VH_OK) return rc;
+    if (!penalised_out && !lp_tok) return VH_OK;
+    const VhPenalty pen = seen ? VhPenalty{seen, v.r, v.f, v.p, 0} : VhPenalty{};
+    return check_launch(what, vhk_logit_rules_rows(S(stream), logits, ld, rows, V, pen, penalised_out, tokens, lp_tok, lp_top_id, lp_top, K));
 }
 
 // a launcher returns non-zero when it REJECTS its arguments before launching (VH_E_SHAPE); a launch the runtime
@@ -1255,13 +1372,18 @@ static int head_and_select(vh_mixtral* m, hipStream_t st, const float* x_in, con
     const bool sharded = m->c.vocab_n > 0 && (m->c.tp_world > 1 || (m->comm && vh_comm_is_loopback(m->comm)));
     const bool filt = sampling_filters(m->samp, m->V);   // top-k / top-p: greedy head, then the filter kernel on the kept row
     const int keyed = m->samp.T > 0.0 ? 1 : 0;           // sampled candidates travel as exact keys of their double scores
+    // penalties (off: a null table, the kernels and launches of an engine without rules): folded into the head's per-block compare,
+    // or applied on load by the filter kernel; the select counts the token into the table
+    const VhPenalty pen = m->pen_of(m->rules, m->unit());
     VH_TRY(vhk_dec_lmhead(st, x_in, delta, m->final_norm, m->c.rms_eps, m->lm_head, m->Vn, m->H, m->logits, m->blk_val,
-                          m->blk_idx, m->lm_grid, m->counters + 1, m->hist_rows(), m->v0, m->V, cx, filt ? nullptr : &m->samp), "lm_head");
+                          m->blk_idx, m->lm_grid, m->counters + 1, m->hist_rows(), m->v0, m->V, cx, filt ? nullptr : &m->samp,
+                          filt ? nullptr : &pen), "lm_head");
     int nblk = m->lm_grid;
     if (filt) {
         VhDecSampleJob j{};
         j.n = 1; j.V = m->V; j.hist_rows = m->hist_rows();
         j.logits[0] = m->logits; j.ngen[0] = m->counters + 1; j.blk_val[0] = m->blk_val; j.blk_idx[0] = m->blk_idx; j.sample[0] = m->samp;
+        j.pen[0] = pen;
         VH_TRY(vhk_dec_sample(st, j), "sample");
         nblk = 1;
     } else if (sharded) {
@@ -1270,7 +1392,13 @@ static int head_and_select(vh_mixtral* m, hipStream_t st, const float* x_in, con
         if (rc != VH_OK) return rc;
     }
     VH_TRY(vhk_dec_select(st, m->blk_val, m->blk_idx, nblk, m->embed, m->H, m->V, m->xa, m->counters, m->counters + 1,
-                          m->out_tokens, m->c.max_new, mode, set_pos, keyed), "select");
+                          m->out_tokens, m->c.max_new, mode, set_pos, keyed, const_cast<unsigned*>(pen.seen)), "select");
+    if (m->rules.K >= 0) {
+        VhDecLogprobJob lj{};
+        lj.V = m->V; lj.hist_rows = m->hist_rows(); lj.kmax = m->c.max_logprobs; lj.max_new = m->lp_rows();
+        m->logprob_slot(lj, m->unit(), m->rules, m->logits, m->counters + 1, m->out_tokens);
+        VH_TRY(vhk_dec_logprobs(st, lj), "logprobs");
+    }
     return VH_OK;
 }
 
@@ -1405,7 +1533,7 @@ static int seq_ok(vh_mixtral* m, int s, const char* what) {
 int vh_mixtral_seq_alloc(vh_mixtral_t* m) {
     if (!m) return fail(VH_E_ARG, "null engine");
     for (int s = 0; s < (int)m->seqs.size(); ++s)
-        if (!m->seqs[s].live) { m->seqs[s].live = true; m->seqs[s].samp = VhSampleParams{}; return s; }
+        if (!m->seqs[s].live) { m->seqs[s].live = true; m->seqs[s].samp = VhSampleParams{}; m->seqs[s].rules = vh_mixtral::Rules{}; return s; }
     return fail(VH_E_FULL, "vh_mixtral_seq_alloc: all %d sequence slots are in use", (int)m->seqs.size());
 }
 
@@ -1425,6 +1553,31 @@ int vh_mixtral_seq_set_sampling(vh_mixtral_t* m, int s, const vh_sampling* smp) 
     m->seqs[s].samp = p;
     return VH_OK;
 }
+
+int vh_mixtral_seq_set_logit_rules(vh_mixtral_t* m, int s, const vh_logit_rules* r, const int* ids, int n_prompt, int n_output) {
+    const int rc0 = seq_ok(m, s, "vh_mixtral_seq_set_logit_rules");
+    if (rc0 != VH_OK) return rc0;
+    vh_mixtral::Rules v;
+    const int rc = engine_rules(m, 1 + s, r, ids, n_prompt, n_output, &v, "vh_mixtral_seq_set_logit_rules");
+    if (rc != VH_OK) return rc;
+    m->seqs[s].rules = v;
+    return VH_OK;
+}
+static bool slot_ok(const vh_mixtral_t* m, int s) { return m && s >= 0 && s < (int)m->seqs.size(); }
+const float* vh_mixtral_logprobs_token(const vh_mixtral_t* m) { return m ? m->lp_tok : nullptr; }
+const int* vh_mixtral_logprobs_top_ids(const vh_mixtral_t* m) { return m ? m->lp_top_id : nullptr; }
+const float* vh_mixtral_logprobs_top(const vh_mixtral_t* m) { return m ? m->lp_top : nullptr; }
+const float* vh_mixtral_seq_logprobs_token(const vh_mixtral_t* m, int s) {
+    return (slot_ok(m, s) && m->lp_tok) ? m->lp_tok + (size_t)(1 + s) * m->lp_rows() : nullptr;
+}
+const int* vh_mixtral_seq_logprobs_top_ids(const vh_mixtral_t* m, int s) {
+    return (slot_ok(m, s) && m->lp_top_id) ? m->lp_top_id + (size_t)(1 + s) * m->lp_rows() * m->c.max_logprobs : nullptr;
+}
+const float* vh_mixtral_seq_logprobs_top(const vh_mixtral_t* m, int s) {
+    return (slot_ok(m, s) && m->lp_top) ? m->lp_top + (size_t)(1 + s) * m->lp_rows() * m->c.max_logprobs : nullptr;
+}
+const uint32_t* vh_mixtral_seen(const vh_mixtral_t* m) { return m ? m->seen_of(0) : nullptr; }
+const uint32_t* vh_mixtral_seq_seen(const vh_mixtral_t* m, int s) { return slot_ok(m, s) ? m->seen_of(1 + s) : nullptr; }
 
 int vh_mixtral_pages_free(const vh_mixtral_t* m) { return m ? (int)m->free_pages.size() : 0; }
 int vh_mixtral_seq_pos(const vh_mixtral_t* m, int s) {
@@ -1530,29 +1683,38 @@ static int batched_head(vh_mixtral* m, hipStream_t st, const int* ids, int n, co
         VhDecBatchVec hv{};
         VhDecBatchHead hdp{};
         VhDecSampleJob sj{};
+        VhDecLogprobJob lj{};
+        VhPenalty pen[VH_BMAX] = {};
         bool filt[VH_BMAX] = {};
         hv.n = gn;
         sj.V = m->V; sj.hist_rows = 1;
+        lj.V = m->V; lj.hist_rows = 1; lj.kmax = m->c.max_logprobs; lj.max_new = m->lp_rows();
         for (int b = 0; b < gn; ++b) {
             const VhSampleParams& sp = m->seqs[ids[g0 + b]].samp;
             int* cnt = m->seq_counters + 4 * ids[g0 + b];
             hv.x_in[b] = x_in[g0 + b]; hv.delta[b] = delta[g0 + b];
             hdp.blk_val[b] = m->l_blk_val[b]; hdp.blk_idx[b] = m->l_blk_idx[b];
             hdp.ngen[b] = cnt + 1;
+            const vh_mixtral::Rules& rl = m->seqs[ids[g0 + b]].rules;
+            pen[b] = m->pen_of(rl, 1 + ids[g0 + b]);
             filt[b] = sampling_filters(sp, m->V);
-            if (!filt[b]) hdp.sample[b] = sp;
-            if (filt[b] || logits_out) hdp.logits[b] = m->samp_rows + (size_t)b * m->V;
+            if (!filt[b]) { hdp.sample[b] = sp; hdp.pen[b] = pen[b]; }
+            if (filt[b] || logits_out || rl.K >= 0) hdp.logits[b] = m->samp_rows + (size_t)b * m->V;
+            if (rl.K >= 0)
+                m->logprob_slot(lj, 1 + ids[g0 + b], rl, gn >= 2 ? hdp.logits[b] : m->logits, cnt + 1,
+                                m->seq_tokens + (size_t)ids[g0 + b] * m->lp_rows());
             if (filt[b]) {
                 const int j = sj.n++;
                 sj.logits[j] = gn >= 2 ? hdp.logits[b] : m->logits; sj.ngen[j] = cnt + 1;
                 sj.blk_val[j] = m->l_blk_val[b]; sj.blk_idx[j] = m->l_blk_idx[b]; sj.sample[j] = sp;
+                sj.pen[j] = pen[b];
             }
         }
         if (gn >= 2) {   // one pass over the table for the group: 97 us (four activation rows, always) against n x 70
             VH_TRY(vhk_decb_lmhead(st, hv, m->final_norm, eps, m->lm_head, m->Vn, H, hdp, m->lm_grid, m->v0), "batched lm_head");
         } else {
             VH_TRY(vhk_dec_lmhead(st, x_in[g0], delta[g0], m->final_norm, eps, m->lm_head, m->Vn, H, m->logits, m->l_blk_val[0],
-                                  m->l_blk_idx[0], m->lm_grid, hdp.ngen[0], 1, m->v0, m->V, nullptr, &hdp.sample[0]), "lm_head");
+                                  m->l_blk_idx[0], m->lm_grid, hdp.ngen[0], 1, m->v0, m->V, nullptr, &hdp.sample[0], &hdp.pen[0]), "lm_head");
         }
         if (logits_out)   // before the filter kernel's turn: it reads the rows, it does not change them
             for (int b = 0; b < gn; ++b)
@@ -1571,8 +1733,9 @@ static int batched_head(vh_mixtral* m, hipStream_t st, const int* ids, int n, co
             }
             VH_TRY(vhk_dec_select(st, m->l_blk_val[b], m->l_blk_idx[b], nblk, m->embed, H, m->V, m->seq_x + (size_t)ids[sb] * 4 * H, cnt, cnt + 1,
                                   m->seq_tokens + (size_t)ids[sb] * (m->c.max_new > 0 ? m->c.max_new : 1), m->c.max_new, mode,
-                                  set_pos ? set_pos[sb] : 0, keyed), "select");
+                                  set_pos ? set_pos[sb] : 0, keyed, const_cast<unsigned*>(pen[b].seen)), "select");
         }
+        if (lj.n > 0) VH_TRY(vhk_dec_logprobs(st, lj), "logprobs");   // one workgroup per sequence of the group that asked for them
     }
     return VH_OK;
 }

@@ -14,6 +14,7 @@
 //   k_dec_down         down GEMV of the two experts, routing-weighted sum -> delta_moe (K26)
 //   k_dec_lmhead       final RMSNorm ; LM-head GEMV ; per-block argmax          (K27)
 //   k_dec_select       global argmax ; append token ; pos++ ; next embedding    (K28,K18)
+//   k_dec_logprobs     log-probabilities of the token and the top K of its raw row (requests that ask for them)
 //
 // GEMV shape: a 256-thread block owns R output rows; thread t owns 16-byte chunks
 // c = t + 256*j of every row (a wave reads 1 KiB contiguous per load instruction),
@@ -934,14 +935,17 @@ __global__ __launch_bounds__(256) void k_dec_down_i8(const float* __restrict__ h
 // ---- K_F: final RMSNorm + LM head GEMV + per-block argmax ---------------------------
 // SAMP: temperature-only sampling (vh_sample.h) — the per-block argmax compares z + G in double instead of the logit (the kept
 // logits stay raw); the draw index is sp.draw0 + n_generated.  The greedy instantiation is the kernel as it was.
+// PEN: the request has penalties (vh_logit_rules) — the thread that owns logit v reads seen[v], stores the RAW value to the row and
+// compares the penalised one (or its z + G under SAMP).
 #define LM_R 8
-template <int NJ, bool SAMP>
+template <int NJ, bool SAMP, bool PEN>
 __global__ __launch_bounds__(256) void k_dec_lmhead(const float* __restrict__ x_in, const float* __restrict__ delta,
                                                     const float* __restrict__ norm_w, float eps,
                                                     const uint16_t* __restrict__ W, int V, int K,
                                                     float* __restrict__ logits, float* __restrict__ blk_val,
                                                     int* __restrict__ blk_idx, const int* __restrict__ ngen_ptr,
-                                                    int hist_rows, int v0, int Vfull, const VhXchg cx, const VhSampleParams sp) {
+                                                    int hist_rows, int v0, int Vfull, const VhXchg cx, const VhSampleParams sp,
+                                                    const VhPenalty pen) {
     typedef typename std::conditional<SAMP, double, float>::type BT;
     __shared__ float red[4 * (LM_R + 1)];
     xchg_reduce(cx);
@@ -986,6 +990,7 @@ __global__ __launch_bounds__(256) void k_dec_lmhead(const float* __restrict__ x_
             for (int r = 0; r < LM_R; ++r) if (threadIdx.x == r) v = vals[r];
             v *= inv;
             logits[n0 + threadIdx.x] = v;
+            if (PEN) v = vhs_penalise(v, pen.seen[v0 + n0 + threadIdx.x], pen.r, pen.f, pen.p);
             if (SAMP) {
                 const double s = vhs_perturbed(v, v0 + n0 + threadIdx.x, sp, draw);
                 if (s > best) { best = s; besti = v0 + n0 + threadIdx.x; }
@@ -1013,7 +1018,7 @@ __global__ __launch_bounds__(256) void k_dec_select(const float* __restrict__ bl
                                                     int nblk, const uint16_t* __restrict__ embed, int H, int vocab,
                                                     float* __restrict__ x_next, int* __restrict__ pos_ptr,
                                                     int* __restrict__ ngen_ptr, int* __restrict__ out_tokens,
-                                                    int max_out, int mode, int set_pos) {
+                                                    int max_out, int mode, int set_pos, unsigned* __restrict__ seen) {
     typedef typename std::conditional<KEYED, double, float>::type VT;
     __shared__ VT v_s[256];
     __shared__ int i_s[256];
@@ -1039,6 +1044,7 @@ __global__ __launch_bounds__(256) void k_dec_select(const float* __restrict__ bl
         // mode 1: decode step (append, pos++); mode 0: end of prefill (first token, pos = set_pos)
         const int n = mode ? *ngen_ptr : 0;
         if (n < max_out) out_tokens[n] = tok;
+        if (seen) seen[tok] += 1;           // the request's token table (vh_logit_rules): one more occurrence in its output
         *ngen_ptr = n + 1;
         *pos_ptr = mode ? (*pos_ptr + 1) : set_pos;
     }
@@ -1185,8 +1191,9 @@ __global__ __launch_bounds__(256) void k_decb_attn(const VhDecBatchAttn bt, floa
 }
 
 // final RMSNorm + LM head + per-block argmax for every sequence of the batch (the 424 MB table is read once); SAMP: sequences with
-// hd.sample[b].T > 0 compare z + G (as k_dec_lmhead<SAMP>), the others their logits (in double: the same order and winner)
-template <int NJ, bool SAMP>
+// hd.sample[b].T > 0 compare z + G (as k_dec_lmhead<SAMP>), the others their logits (in double: the same order and winner); PEN: sequences
+// with a token table (hd.pen[b].seen) compare penalised values, the kept rows stay raw
+template <int NJ, bool SAMP, bool PEN>
 __global__ __launch_bounds__(256) void k_decb_lmhead(const VhDecBatchVec bt, const float* __restrict__ norm_w, float eps,
                                                      const uint16_t* __restrict__ W, int V, int K, const VhDecBatchHead hd,
                                                      int v0) {
@@ -1239,6 +1246,7 @@ __global__ __launch_bounds__(256) void k_decb_lmhead(const VhDecBatchVec bt, con
                 float v = tot[b * (LM_R + 1) + threadIdx.x];
                 v *= inv[b];
                 if (hd.logits[b]) hd.logits[b][v0 + n0 + threadIdx.x] = v;
+                if (PEN && hd.pen[b].seen) v = vhs_penalise(v, hd.pen[b].seen[v0 + n0 + threadIdx.x], hd.pen[b].r, hd.pen[b].f, hd.pen[b].p);
                 if (SAMP) {
                     const double s = hd.sample[b].T > 0.0 ? vhs_perturbed(v, v0 + n0 + threadIdx.x, hd.sample[b], draw[b]) : (double)v;
                     if (s > best[b]) { best[b] = s; besti[b] = v0 + n0 + threadIdx.x; }
@@ -1265,14 +1273,42 @@ __global__ __launch_bounds__(256) void k_decb_lmhead(const VhDecBatchVec bt, con
 
 // ---- filtered draws (top-k / top-p) after the LM head: one workgroup per request row (vh_sample.h) ----------------------------
 #define SAMPLE_NT 1024
+template <bool PEN>
 __global__ __launch_bounds__(SAMPLE_NT) void k_dec_sample(const VhDecSampleJob job) {
     __shared__ VhsShared<SAMPLE_NT / 64> sh;
     const int b = blockIdx.x;
     const int n = *job.ngen[b];
     const float* row = job.logits[b] + (size_t)min(n, job.hist_rows - 1) * job.V;
     double best; int bi;
-    vhs_row<SAMPLE_NT>(row, job.V, job.sample[b], (unsigned long long)(job.sample[b].draw0 + n), sh, best, bi);
+    vhs_row<SAMPLE_NT, PEN>(row, job.V, job.sample[b], (unsigned long long)(job.sample[b].draw0 + n), sh, best, bi, job.pen[b]);
     if (threadIdx.x == 0) { vhs_key3(best, job.blk_val[b], 1); job.blk_idx[b][0] = bi; }
+}
+// ---- log-probabilities of the token just selected and the top K of its RAW row (vh_sample.h vhs_logprobs_row): one workgroup per
+// request row, after the select; the row index comes from the sequence's counters on the device
+#define LOGPROB_NT 1024
+#define LOGPROB_EL 52     // rows of up to LOGPROB_NT * LOGPROB_EL entries keep a thread's elements in registers for the top-K rounds
+template <int EL>
+__global__ __launch_bounds__(LOGPROB_NT) void k_dec_logprobs(const VhDecLogprobJob job) {
+    __shared__ VhsLpShared<LOGPROB_NT / 64> sh;
+    const int b = blockIdx.x;
+    const int i = *job.ngen[b] - 1;
+    if (i < 0 || i >= job.max_new) return;
+    const float* row = job.logits[b] + (size_t)min(i, job.hist_rows - 1) * job.V;
+    vhs_logprobs_row<LOGPROB_NT, EL>(row, job.V, job.tokens[b][i], job.K[b], job.lp_tok[b] + i, job.lp_top_id[b] + (size_t)i * job.kmax,
+                                 job.lp_top[b] + (size_t)i * job.kmax, sh);
+}
+// per-operator entry vh_logit_rules_rows: the penalised row (nullable) and the log-probabilities (nullable) of caller-provided rows
+template <int EL>
+__global__ __launch_bounds__(LOGPROB_NT) void k_logit_rules_rows(const float* __restrict__ logits, long ld, int V, const VhPenalty pen,
+                                                                 float* __restrict__ penalised_out, const int* __restrict__ tokens,
+                                                                 float* __restrict__ lp_tok, int* __restrict__ lp_top_id,
+                                                                 float* __restrict__ lp_top, int K) {
+    __shared__ VhsLpShared<LOGPROB_NT / 64> sh;
+    const size_t r = blockIdx.x;
+    const float* row = logits + r * ld;
+    if (penalised_out)
+        for (int i = threadIdx.x; i < V; i += LOGPROB_NT) penalised_out[r * V + i] = vhs_ld<true>(row, i, pen);
+    if (lp_tok) vhs_logprobs_row<LOGPROB_NT, EL>(row, V, tokens[r], K, lp_tok + r, lp_top_id + r * K, lp_top + r * K, sh);
 }
 // per-operator entry vh_sample_rows: row r = logits + r * ld (ld = 0: one row for every draw), draw = draw0 + r
 template <int NT>
@@ -1456,23 +1492,49 @@ int vhk_dec_down_i8(hipStream_t st, const float* hbuf, const int* route, const i
 
 int vhk_dec_lmhead(hipStream_t st, const float* x_in, const float* delta, const float* norm_w, float eps,
                    const uint16_t* W, int V, int K, float* logits, float* blk_val, int* blk_idx, int grid,
-                   const int* ngen_ptr, int hist_rows, int v0, int Vfull, const VhXchg* cx, const VhSampleParams* sample) {
+                   const int* ngen_ptr, int hist_rows, int v0, int Vfull, const VhXchg* cx, const VhSampleParams* sample,
+                   const VhPenalty* pen) {
     const bool samp = sample && sample->T > 0.0;
     if (samp && !ngen_ptr) return -1;
     const VhSampleParams sp = samp ? *sample : VhSampleParams{};
+    const VhPenalty pn = (pen && pen->seen) ? *pen : VhPenalty{};
     return pick_nj(K, [&](auto nj) {
-        if (samp)
-            hipLaunchKernelGGL((k_dec_lmhead<decltype(nj)::value, true>), dim3(grid), dim3(256), 0, st, x_in, delta, norm_w, eps,
-                               W, V, K, logits, blk_val, blk_idx, ngen_ptr, hist_rows, v0, Vfull, xchg_or_none(cx), sp);
-        else
-            hipLaunchKernelGGL((k_dec_lmhead<decltype(nj)::value, false>), dim3(grid), dim3(256), 0, st, x_in, delta, norm_w, eps,
-                               W, V, K, logits, blk_val, blk_idx, ngen_ptr, hist_rows, v0, Vfull, xchg_or_none(cx), sp);
+        constexpr int NJ = decltype(nj)::value;
+        auto go = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, x_in, delta, norm_w, eps, W, V, K, logits, blk_val, blk_idx, ngen_ptr,
+                               hist_rows, v0, Vfull, xchg_or_none(cx), sp, pn);
+        };
+        if (pn.seen) { if (samp) go(k_dec_lmhead<NJ, true, true>); else go(k_dec_lmhead<NJ, false, true>); }
+        else if (samp) go(k_dec_lmhead<NJ, true, false>);
+        else go(k_dec_lmhead<NJ, false, false>);
         return 0;
     });
 }
 int vhk_dec_sample(hipStream_t st, const VhDecSampleJob& job) {
     if (job.n < 1 || job.n > VH_BMAX || job.V < 1 || job.hist_rows < 1) return -1;
-    hipLaunchKernelGGL(k_dec_sample, dim3(job.n), dim3(SAMPLE_NT), 0, st, job);
+    bool pen = false;
+    for (int b = 0; b < job.n; ++b) pen = pen || job.pen[b].seen != nullptr;
+    if (pen) hipLaunchKernelGGL(k_dec_sample<true>, dim3(job.n), dim3(SAMPLE_NT), 0, st, job);
+    else hipLaunchKernelGGL(k_dec_sample<false>, dim3(job.n), dim3(SAMPLE_NT), 0, st, job);
+    return 0;
+}
+int vhk_dec_logprobs(hipStream_t st, const VhDecLogprobJob& job) {
+    if (job.n < 1 || job.n > VH_BMAX || job.V < 1 || job.hist_rows < 1 || job.kmax < 1 || job.max_new < 1) return -1;
+    for (int b = 0; b < job.n; ++b)
+        if (job.K[b] < 0 || job.K[b] > job.kmax) return -1;
+    if (job.V <= LOGPROB_NT * LOGPROB_EL) hipLaunchKernelGGL(k_dec_logprobs<LOGPROB_EL>, dim3(job.n), dim3(LOGPROB_NT), 0, st, job);
+    else hipLaunchKernelGGL(k_dec_logprobs<0>, dim3(job.n), dim3(LOGPROB_NT), 0, st, job);
+    return 0;
+}
+int vhk_logit_rules_rows(hipStream_t st, const float* logits, long ld, int rows, int V, const VhPenalty& pen, float* penalised_out,
+                         const int* tokens, float* lp_tok, int* lp_top_id, float* lp_top, int K) {
+    if (rows < 1 || V < 1 || ld < 0 || K < 0) return -1;
+    if (V <= LOGPROB_NT * LOGPROB_EL)
+        hipLaunchKernelGGL(k_logit_rules_rows<LOGPROB_EL>, dim3(rows), dim3(LOGPROB_NT), 0, st, logits, ld, V, pen, penalised_out, tokens,
+                           lp_tok, lp_top_id, lp_top, K);
+    else
+        hipLaunchKernelGGL(k_logit_rules_rows<0>, dim3(rows), dim3(LOGPROB_NT), 0, st, logits, ld, V, pen, penalised_out, tokens, lp_tok,
+                           lp_top_id, lp_top, K);
     return 0;
 }
 int vhk_sample_rows(hipStream_t st, const float* logits, long ld, int rows, int V, const VhSampleParams& sp, int* tokens_out) {
@@ -1501,11 +1563,11 @@ int vhk_dec_pick(hipStream_t st, const float* blk_val, const int* blk_idx, int n
 
 int vhk_dec_select(hipStream_t st, const float* blk_val, const int* blk_idx, int nblk, const uint16_t* embed, int H,
                    int vocab, float* x_next, int* pos_ptr, int* ngen_ptr, int* out_tokens, int max_out, int mode, int set_pos,
-                   int keyed) {
+                   int keyed, unsigned* seen) {
     if (keyed) hipLaunchKernelGGL(k_dec_select<true>, dim3(1), dim3(256), 0, st, blk_val, blk_idx, nblk, embed, H, vocab, x_next, pos_ptr,
-                                  ngen_ptr, out_tokens, max_out, mode, set_pos);
+                                  ngen_ptr, out_tokens, max_out, mode, set_pos, seen);
     else hipLaunchKernelGGL(k_dec_select<false>, dim3(1), dim3(256), 0, st, blk_val, blk_idx, nblk, embed, H, vocab, x_next, pos_ptr,
-                            ngen_ptr, out_tokens, max_out, mode, set_pos);
+                            ngen_ptr, out_tokens, max_out, mode, set_pos, seen);
     return 0;
 }
 
@@ -1541,10 +1603,13 @@ int vhk_decb_lmhead(hipStream_t st, const VhDecBatchVec& bt, const float* norm_w
     return pick_nj(K, [&](auto nj) {
         constexpr int NJ = decltype(nj)::value;
         if (NJ > 2) return -1;
-        bool samp = false;
-        for (int b = 0; b < bt.n; ++b) samp = samp || hd.sample[b].T > 0.0;
-        if (samp) hipLaunchKernelGGL((k_decb_lmhead<(NJ > 2 ? 2 : NJ), true>), dim3(grid), dim3(256), 0, st, bt, norm_w, eps, W, V, K, hd, v0);
-        else hipLaunchKernelGGL((k_decb_lmhead<(NJ > 2 ? 2 : NJ), false>), dim3(grid), dim3(256), 0, st, bt, norm_w, eps, W, V, K, hd, v0);
+        constexpr int NB = NJ > 2 ? 2 : NJ;
+        bool samp = false, pen = false;
+        for (int b = 0; b < bt.n; ++b) { samp = samp || hd.sample[b].T > 0.0; pen = pen || hd.pen[b].seen != nullptr; }
+        auto go = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, st, bt, norm_w, eps, W, V, K, hd, v0); };
+        if (pen) { if (samp) go(k_decb_lmhead<NB, true, true>); else go(k_decb_lmhead<NB, false, true>); }
+        else if (samp) go(k_decb_lmhead<NB, true, false>);
+        else go(k_decb_lmhead<NB, false, false>);
         return 0;
     });
 }

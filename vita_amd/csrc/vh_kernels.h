@@ -138,18 +138,34 @@ struct VhDecBatchAttn {
 // seeded sampling of one request (vh_sample.h; the vh_sampling of the C ABI in double): T = 0 greedy, top_k 0 / top_p >= 1 off;
 // the draw of a token is draw0 + its index in the request's output (counters[1] on the device)
 struct VhSampleParams { double T, top_p; int top_k, pad_; unsigned long long seed; long long draw0; };
+// penalties of one request (vh_logit_rules; vh_sample.h vhs_penalise): seen = its token table (bit 31 = in the prompt, low bits = count in
+// the output), null = no penalties
+struct VhPenalty { const unsigned* seen; float r, f, p; int pad_; };
 // logits[b]: nullable full-vocab row; sample[b]: T > 0 folds the Gumbel-max draw into the per-block argmax (the SAMP instantiation),
 // ngen[b] = the sequence's counters + 1
 struct VhDecBatchHead {
     float* logits[VH_BMAX]; float* blk_val[VH_BMAX]; int* blk_idx[VH_BMAX];
     VhSampleParams sample[VH_BMAX]; const int* ngen[VH_BMAX];
+    VhPenalty pen[VH_BMAX];      // pen[b].seen != null: the per-block argmax of sequence b compares penalised values (the PEN instantiation)
 };
 // filtered draws (top-k / top-p) after the LM head: block b reads row logits[b] + min(*ngen[b], hist_rows - 1) * V and leaves its
 // draw in blk_val[b][0] / blk_idx[b][0] (k_dec_select then runs with nblk = 1)
 struct VhDecSampleJob {
     const float* logits[VH_BMAX]; const int* ngen[VH_BMAX]; float* blk_val[VH_BMAX]; int* blk_idx[VH_BMAX];
     VhSampleParams sample[VH_BMAX]; int hist_rows, V, n;
+    VhPenalty pen[VH_BMAX];      // the filter and the draw see penalised values (applied on load)
 };
+// log-probabilities after the select: block b reads row logits[b] + min(i, hist_rows - 1) * V, i = *ngen[b] - 1 (the token just
+// written, tokens[b][i]) and writes lp_tok[b][i], lp_top_id[b][i * kmax + j], lp_top[b][i * kmax + j] for j < K[b]
+struct VhDecLogprobJob {
+    const float* logits[VH_BMAX]; const int* ngen[VH_BMAX]; const int* tokens[VH_BMAX];
+    float* lp_tok[VH_BMAX]; int* lp_top_id[VH_BMAX]; float* lp_top[VH_BMAX]; int K[VH_BMAX];
+    int hist_rows, V, kmax, max_new, n;
+};
+int vhk_dec_logprobs(hipStream_t st, const VhDecLogprobJob& job);
+// per-operator entry vh_logit_rules_rows: row r = logits + r * ld; penalised_out (nullable) [rows][V]; logprobs when lp_tok != null
+int vhk_logit_rules_rows(hipStream_t st, const float* logits, long ld, int rows, int V, const VhPenalty& pen, float* penalised_out,
+                         const int* tokens, float* lp_tok, int* lp_top_id, float* lp_top, int K);
 int vhk_dec_sample(hipStream_t st, const VhDecSampleJob& job);
 int vhk_sample_rows(hipStream_t st, const float* logits, long ld, int rows, int V, const VhSampleParams& sp, int* tokens_out);
 int vhk_decb_gemv(hipStream_t st, const VhDecBatchVec& bt, const float* norm_w, float eps, const uint16_t* W, int N, int K, int norm);
@@ -172,14 +188,15 @@ int vhk_dec_down_i8(hipStream_t st, const float* hbuf, const int* route, const i
 int vhk_dec_lmhead(hipStream_t st, const float* x_in, const float* delta, const float* norm_w, float eps,
                    const uint16_t* W, int V, int K, float* logits, float* blk_val, int* blk_idx, int grid,
                    const int* ngen_ptr, int hist_rows, int v0, int Vfull, const VhXchg* cx = nullptr,
-                   const VhSampleParams* sample = nullptr);   // sample: temperature-only draw (T > 0; ngen_ptr required)
+                   const VhSampleParams* sample = nullptr,    // sample: temperature-only draw (T > 0; ngen_ptr required)
+                   const VhPenalty* pen = nullptr);           // pen->seen != null: selection sees penalised values (the kept row stays raw)
 // keyed: sampled candidates (the 3-float keys of vh_sample.h vhs_key3 at stride nblk in blk_val; cand holds [world][4])
 int vhk_dec_cand(hipStream_t st, const float* blk_val, const int* blk_idx, int nblk, float* cand, int rank, int world, int keyed = 0);
 int vhk_dec_cand_unpack(hipStream_t st, const float* cand, int world, float* val, int* idx, int keyed = 0);
 int vhk_dec_pick(hipStream_t st, const float* blk_val, const int* blk_idx, int nblk, int vocab, int* token_out, float* value_out);
 int vhk_dec_select(hipStream_t st, const float* blk_val, const int* blk_idx, int nblk, const uint16_t* embed, int H,
                    int vocab, float* x_next, int* pos_ptr, int* ngen_ptr, int* out_tokens, int max_out, int mode, int set_pos,
-                   int keyed = 0);
+                   int keyed = 0, unsigned* seen = nullptr);   // seen (nullable): the request's token table, seen[token] += 1
 
 // ---- GEMM (vh_gemm.hip) -------------------------------------------------------------
 // C[orow(m), n] = epilogue( sum_k A[arow(m,k), k] * W[n, k] )

@@ -51,6 +51,28 @@ __device__ __forceinline__ unsigned vhs_key(float v) {
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 __device__ __forceinline__ float vhs_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+// ---- logit rules (include/vita_hip.h vh_logit_rules; restated in numpy by tests/logit_rules_ref.py) -----------------------------
+// seen word of an id: bit 31 = in the prompt, low bits = times it occurs in the output so far.  Every step is ONE IEEE fp32
+// operation (no contraction): repetition (HF RepetitionPenaltyLogitsProcessor), then frequency, then presence (vLLM apply_penalties).
+__device__ __forceinline__ float vhs_penalise(float x, unsigned s, float r, float f, float p) {
+    // plain operators under contract(off): the product and the difference below must stay two roundings.  (__fmul_rn / __fsub_rn are
+    // inline functions of the HIP headers built under the translation unit's default contraction, and the compiler fused their
+    // product and difference into one fma; the division is the correctly rounded one, hipcc's default.)
+#pragma clang fp contract(off)
+    const unsigned c = s & 0x7fffffffu;
+    if (s) x = x > 0.f ? x / r : x * r;
+    const float fc = f * (float)c;
+    x = x - fc;
+    if (c) x = x - p;
+    return x;
+}
+// row[i] as selection sees it: penalised when the request has a table (PEN instantiations only; the others are the plain load)
+template <bool PEN>
+__device__ __forceinline__ float vhs_ld(const float* __restrict__ row, int i, const VhPenalty& pen) {
+    const float v = row[i];
+    if (PEN) return pen.seen ? vhs_penalise(v, pen.seen[i], pen.r, pen.f, pen.p) : v;
+    return v;
+}
 // z_i + G_i of vocab index i (temperature-only path of the LM head kernels)
 __device__ __forceinline__ double vhs_perturbed(float v, int i, const VhSampleParams& p, unsigned long long draw) {
     unsigned long long x[4];
@@ -99,8 +121,8 @@ __device__ __forceinline__ T vhs_wave_incl_scan(T v) {
 }
 
 // key of the k-th largest value of row[0, V) (1 <= k <= V)
-template <int NT>
-__device__ unsigned vhs_select_count(const float* __restrict__ row, int V, int k, VhsShared<NT / 64>& sh) {
+template <int NT, bool PEN = false>
+__device__ unsigned vhs_select_count(const float* __restrict__ row, int V, int k, VhsShared<NT / 64>& sh, const VhPenalty& pen = VhPenalty{}) {
     const int tid = threadIdx.x, lane = tid & 63;
     unsigned prefix = 0;
     int need = k;
@@ -110,7 +132,7 @@ __device__ unsigned vhs_select_count(const float* __restrict__ row, int V, int k
         for (int b = tid; b < 256; b += NT) sh.cnt[b] = 0;
         __syncthreads();
         for (int i = tid; i < V; i += NT) {
-            const unsigned key = vhs_key(row[i]);
+            const unsigned key = vhs_key(vhs_ld<PEN>(row, i, pen));
             if ((key & hmask) == prefix) atomicAdd(&sh.cnt[(key >> shift) & 255u], 1u);
         }
         __syncthreads();
@@ -138,14 +160,15 @@ __device__ unsigned vhs_select_count(const float* __restrict__ row, int V, int k
 }
 
 // smallest kept key of the top-p cut among keys >= lo (lo: the top-k threshold, 0 = none)
-template <int NT>
-__device__ unsigned vhs_select_mass(const float* __restrict__ row, int V, const VhSampleParams& p, unsigned lo, VhsShared<NT / 64>& sh) {
+template <int NT, bool PEN = false>
+__device__ unsigned vhs_select_mass(const float* __restrict__ row, int V, const VhSampleParams& p, unsigned lo, VhsShared<NT / 64>& sh,
+                                    const VhPenalty& pen = VhPenalty{}) {
     constexpr int NW = NT / 64;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     if (tid == 0) sh.kmax = 0;
     __syncthreads();
     unsigned km = 0;
-    for (int i = tid; i < V; i += NT) km = max(km, vhs_key(row[i]));
+    for (int i = tid; i < V; i += NT) km = max(km, vhs_key(vhs_ld<PEN>(row, i, pen)));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) km = max(km, (unsigned)__shfl_xor((int)km, o, 64));
     if (lane == 0) atomicMax(&sh.kmax, km);
@@ -163,7 +186,7 @@ __device__ unsigned vhs_select_mass(const float* __restrict__ row, int V, const 
         for (int b = tid; b < NW * 256; b += NT) sh.mass[b >> 8][b & 255] = 0.0;
         __syncthreads();
         for (int i = tid; i < V; i += NT) {
-            const unsigned key = vhs_key(row[i]);
+            const unsigned key = vhs_key(vhs_ld<PEN>(row, i, pen));
             if (key >= lo && (key & hmask) == prefix) {
                 const unsigned b = (key >> shift) & 255u;
                 atomicAdd(&sh.cnt[b], 1u);
@@ -214,14 +237,14 @@ __device__ unsigned vhs_select_mass(const float* __restrict__ row, int V, const 
 
 // One row: filter (top-k, top-p) and Gumbel-max draw `draw` (T = 0: plain argmax).  Block-collective; every thread returns the
 // winner (value = z + G of it, index; index 0x7fffffff when nothing finite was kept).
-template <int NT>
+template <int NT, bool PEN = false>
 __device__ void vhs_row(const float* __restrict__ row, int V, const VhSampleParams& p, unsigned long long draw, VhsShared<NT / 64>& sh,
-                        double& best_out, int& idx_out) {
+                        double& best_out, int& idx_out, const VhPenalty& pen = VhPenalty{}) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const bool greedy = !(p.T > 0.0);
     unsigned thr = 0;
-    if (!greedy && p.top_k > 0 && p.top_k < V) thr = vhs_select_count<NT>(row, V, p.top_k, sh);
-    if (!greedy && p.top_p < 1.0) thr = max(thr, vhs_select_mass<NT>(row, V, p, thr, sh));
+    if (!greedy && p.top_k > 0 && p.top_k < V) thr = vhs_select_count<NT, PEN>(row, V, p.top_k, sh, pen);
+    if (!greedy && p.top_p < 1.0) thr = max(thr, vhs_select_mass<NT, PEN>(row, V, p, thr, sh, pen));
     double best = -INFINITY;
     int bi = 0x7fffffff;
     for (int g = tid; 4 * g < V; g += NT) {        // ascending indices per thread: the first maximum wins
@@ -229,7 +252,7 @@ __device__ void vhs_row(const float* __restrict__ row, int V, const VhSamplePara
         bool any = false;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            v[j] = 4 * g + j < V ? vhs_canon(row[4 * g + j]) : -INFINITY;
+            v[j] = 4 * g + j < V ? vhs_canon(vhs_ld<PEN>(row, 4 * g + j, pen)) : -INFINITY;
             any = any || (4 * g + j < V && vhs_key(v[j]) >= thr);
         }
         if (!any) continue;
@@ -256,4 +279,100 @@ __device__ void vhs_row(const float* __restrict__ row, int V, const VhSamplePara
         if (sh.bv[q] > best || (sh.bv[q] == best && sh.bi[q] < bi)) { best = sh.bv[q]; bi = sh.bi[q]; }
     __syncthreads();          // sh is reused by the caller's next row
     best_out = best; idx_out = bi;
+}
+
+// ---- log-probabilities of one RAW row (vLLM's raw_logprobs / HF output_logits view): lp(x) = x - (M + log sum_j exp(x_j - M)) in
+// double, M the row maximum, rounded to fp32 once.  The sum is one partial per wave (each thread adds its strided elements in
+// ascending order, the wave folds them in a fixed butterfly) added in wave order, so it does not depend on timing.  NaN ranks as
+// -inf; a row with nothing finite gives -inf everywhere.  The top K in (logit descending, id ascending) order come from K rounds
+// of a block-wide maximum over 64-bit (value key, ~id) keys: every thread keeps its best candidate below the previous winner and
+// only the winner's owner looks through its elements again.  EL > 0 (V <= NT * EL): a thread's elements stay in EL registers for
+// those rounds, so a round costs a wave reduction, two barriers and one wave's pass over its registers; EL = 0: the owner re-reads
+// its elements from the row.  Entries past V: id -1, -inf.
+template <int NW>
+struct VhsLpShared {
+    double part[NW];
+    unsigned long long top[NW];
+    unsigned kmax;
+};
+__device__ __forceinline__ unsigned long long vhs_lp_key(float v, int i) {
+    return ((unsigned long long)vhs_key(v) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
+}
+template <int NT, int EL>
+__device__ void vhs_logprobs_row(const float* __restrict__ row, int V, int tok, int K, float* __restrict__ lp_tok,
+                                 int* __restrict__ top_id, float* __restrict__ top_lp, VhsLpShared<NT / 64>& sh) {
+    constexpr int NW = NT / 64;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (tid == 0) sh.kmax = 0;
+    __syncthreads();
+    unsigned km = 0;
+    for (int i = tid; i < V; i += NT) km = max(km, vhs_key(row[i]));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) km = max(km, (unsigned)__shfl_xor((int)km, o, 64));
+    if (lane == 0) atomicMax(&sh.kmax, km);
+    __syncthreads();
+    const double M = (double)vhs_unkey(sh.kmax);
+    double lse = INFINITY;                  // nothing finite: every log-probability is -inf
+    if (M > -INFINITY) {
+        double s = 0.0;
+        for (int i = tid; i < V; i += NT) s += exp((double)vhs_canon(row[i]) - M);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) sh.part[w] = s;
+        __syncthreads();
+        double tot = 0.0;
+#pragma unroll
+        for (int q = 0; q < NW; ++q) tot += sh.part[q];
+        lse = M + log(tot);
+    }
+    auto lp_of = [&](float v) -> float { return M > -INFINITY ? (float)((double)vhs_canon(v) - lse) : -INFINITY; };
+    if (tid == 0 && lp_tok) lp_tok[0] = (tok >= 0 && tok < V) ? lp_of(row[tok]) : -INFINITY;
+    if (K <= 0) return;
+    unsigned keys[EL > 0 ? EL : 1];          // order keys of this thread's elements (0, below every real key, past V)
+    if (EL > 0) {
+#pragma unroll
+        for (int j = 0; j < EL; ++j) keys[j] = tid + j * NT < V ? vhs_key(row[tid + j * NT]) : 0u;
+    }
+    unsigned long long prev = ~0ull, mine = 0ull;
+    bool rescan = true;
+    for (int j = 0; j < K; ++j) {
+        if (rescan) {
+            mine = 0ull;
+            if (EL > 0) {
+                // ids ascend with q, so among equal values the first one met is the one to keep: a strict compare of the value keys
+                // (and "below the previous winner" among equal values is "a larger id": q * NT > its id - tid, an immediate compare)
+                const unsigned ph = (unsigned)(prev >> 32);
+                const long long d = (long long)(0xFFFFFFFFu - (unsigned)prev) - tid;
+                unsigned mh = 0u;
+                int mq = 0;
+#pragma unroll
+                for (int q = 0; q < EL; ++q) {
+                    const unsigned kh = keys[q];
+                    if ((kh < ph || (kh == ph && (long long)(q * NT) > d)) && kh > mh) { mh = kh; mq = q; }
+                }
+                const unsigned ml = 0xFFFFFFFFu - (unsigned)(tid + mq * NT);
+                mine = mh ? (((unsigned long long)mh << 32) | ml) : 0ull;
+            } else {
+                for (int i = tid; i < V; i += NT) {
+                    const unsigned long long k = vhs_lp_key(row[i], i);
+                    if (k < prev && k > mine) mine = k;
+                }
+            }
+        }
+        unsigned long long b = mine;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(b, o, 64); b = t > b ? t : b; }
+        __syncthreads();                    // the previous round's sh.top has been read by everyone
+        if (lane == 0) sh.top[w] = b;
+        __syncthreads();
+        b = sh.top[0];
+#pragma unroll
+        for (int q = 1; q < NW; ++q) b = sh.top[q] > b ? sh.top[q] : b;
+        rescan = b != 0ull && mine == b;    // keys are distinct (they carry the id): exactly one owner
+        if (tid == 0) {
+            if (b == 0ull) { top_id[j] = -1; top_lp[j] = -INFINITY; }
+            else { top_id[j] = (int)(0xFFFFFFFFu - (unsigned)(b & 0xFFFFFFFFull)); top_lp[j] = lp_of(vhs_unkey((unsigned)(b >> 32))); }
+        }
+        prev = b;
+    }
 }

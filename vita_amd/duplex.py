@@ -271,7 +271,9 @@ class DuplexServer:
         self.mgr.shutdown()
 
 
-def make_serving_llm(model_path, max_new_tokens=128):
-    """Default engine factory of a worker process: one vita_amd.serving.LLM replica on the visible GPU."""
+def make_serving_llm(model_path, max_new_tokens=128, max_logprobs=0):
+    """Default engine factory of a worker process: one vita_amd.serving.LLM replica on the visible GPU.  max_logprobs > 0 (e.g.
+    factory_args=(path, 128, 20)) creates the token tables and logprob buffers that SamplingParams' penalties and logprobs need;
+    without it a turn that asks for them raises ValueError."""
     from .serving import LLM
-    return LLM(model=model_path, tensor_parallel_size=1, max_new_tokens=max_new_tokens)
+    return LLM(model=model_path, tensor_parallel_size=1, max_new_tokens=max_new_tokens, max_logprobs=max_logprobs)

@@ -23,7 +23,7 @@ def rope_tables(max_pos, head_dim, theta):
 
 class MixtralEngine:
     def __init__(self, cfg: VitaConfig, packed, device, max_ctx=None, max_prefill=None, max_new=1024, rank=0,
-                 world=1, nsplit=0, logit_rows=0, max_seqs=0):
+                 world=1, nsplit=0, logit_rows=0, max_seqs=0, penalty_tables=False, max_logprobs=0):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise _lib.VitaHipError("MixtralEngine needs a GPU (no CPU fallback)")
@@ -46,6 +46,9 @@ class MixtralEngine:
         c.tp_rank, c.tp_world, c.nsplit, c.logit_rows = rank, world, nsplit, logit_rows
         c.vocab_lo, c.vocab_n = int(packed.get("vocab_lo", 0)), int(packed.get("vocab_n", 0))   # vocab-sharded LM head
         c.max_seqs = int(max_seqs)
+        # logit rules (vh_logit_rules): a token table / logprob buffers for the engine and every sequence slot; both off = the
+        # workspace and the launches of an engine without them
+        c.penalty_tables, c.max_logprobs = int(bool(penalty_tables)), int(max_logprobs)
         if c.vocab_n and packed["lm_head"].shape[0] != c.vocab_n:
             raise ValueError("packed lm_head does not match its vocab shard")
         self.c = c
@@ -92,6 +95,7 @@ class MixtralEngine:
                                          4 * t.vocab_size * self.logit_rows].view(torch.float32).view(
             self.logit_rows, t.vocab_size)  # row i = the scores that produced generated token i
         self.n_gen = 0
+        self.has_logit_rules = bool(c.penalty_tables or c.max_logprobs)
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -247,6 +251,60 @@ class MixtralEngine:
         """seeded sampling of sequence s (vh_mixtral_seq_set_sampling); seq_alloc / seq_free / reset restore greedy."""
         p = _lib.sampling(temperature, top_k, top_p, seed, draw0)
         check(self.lib.vh_mixtral_seq_set_sampling(self.h, int(s), C.byref(p)), "vh_mixtral_seq_set_sampling")
+
+    # ---- logit rules: penalties and log-probabilities (vh_logit_rules) ------------------------------------------------
+    @staticmethod
+    def _rules_args(repetition_penalty, presence_penalty, frequency_penalty, logprobs, prompt_ids, output_ids):
+        r = _lib.logit_rules(repetition_penalty, presence_penalty, frequency_penalty, logprobs)
+        pi, oi = [int(x) for x in (prompt_ids or ())], [int(x) for x in (output_ids or ())]
+        n = len(pi) + len(oi)
+        ids = (C.c_int * max(n, 1))(*(pi + oi))
+        return r, ids, len(pi), len(oi)
+
+    def set_logit_rules(self, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logprobs=-1, prompt_ids=None,
+                        output_ids=None):
+        """penalties and log-probabilities of the following prefill / decode calls (vh_mixtral_set_logit_rules; the defaults
+        are "off").  prompt_ids: the request's prompt set; output_ids: tokens it has already generated (a recomputed sequence, a
+        later turn) — the device counts the tokens it writes from there on.  Needs an engine created with penalty_tables /
+        max_logprobs; reset() restores "off"."""
+        r, ids, n_p, n_o = self._rules_args(repetition_penalty, presence_penalty, frequency_penalty, logprobs, prompt_ids, output_ids)
+        check(self.lib.vh_mixtral_set_logit_rules(self.h, C.byref(r), ids, n_p, n_o), "vh_mixtral_set_logit_rules")
+
+    def seq_set_logit_rules(self, s, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logprobs=-1,
+                            prompt_ids=None, output_ids=None):
+        """the same for sequence s (vh_mixtral_seq_set_logit_rules); seq_alloc / seq_free / reset restore "off"."""
+        r, ids, n_p, n_o = self._rules_args(repetition_penalty, presence_penalty, frequency_penalty, logprobs, prompt_ids, output_ids)
+        check(self.lib.vh_mixtral_seq_set_logit_rules(self.h, int(s), C.byref(r), ids, n_p, n_o), "vh_mixtral_seq_set_logit_rules")
+
+    def _view(self, ptr, n, dtype):
+        if not ptr:
+            raise _lib.VitaHipError("no such buffer: the sequence slot does not exist")
+        base = self.workspace.data_ptr()
+        return self.workspace[ptr - base: ptr - base + 4 * n].view(dtype)
+
+    def logprobs(self, s=None):
+        """zero-copy views (token fp32 [max_new], top_ids int32 [max_new, max_logprobs], top fp32 [max_new, max_logprobs]) of the
+        logprob buffers of the engine (s None) or of sequence s: entry i belongs to generated token i of the current (re)prefill,
+        the first K of a row are written.  Raises on an engine created without max_logprobs."""
+        K, n = int(self.c.max_logprobs), max(self.max_new, 1)
+        if K <= 0:
+            raise _lib.VitaHipError("the engine was created without logprob buffers (max_logprobs = 0)")
+        if s is None:
+            p = (self.lib.vh_mixtral_logprobs_token(self.h), self.lib.vh_mixtral_logprobs_top_ids(self.h),
+                 self.lib.vh_mixtral_logprobs_top(self.h))
+        else:
+            p = (self.lib.vh_mixtral_seq_logprobs_token(self.h, int(s)), self.lib.vh_mixtral_seq_logprobs_top_ids(self.h, int(s)),
+                 self.lib.vh_mixtral_seq_logprobs_top(self.h, int(s)))
+        return (self._view(p[0], n, torch.float32), self._view(p[1], n * K, torch.int32).view(n, K),
+                self._view(p[2], n * K, torch.float32).view(n, K))
+
+    def seen_table(self, s=None):
+        """zero-copy int32 view [vocab] of the token table of the engine (s None) or of sequence s: bit 31 = in the prompt, low
+        bits = occurrences in the output so far."""
+        if not self.c.penalty_tables:
+            raise _lib.VitaHipError("the engine was created without token tables (penalty_tables = False)")
+        p = self.lib.vh_mixtral_seen(self.h) if s is None else self.lib.vh_mixtral_seq_seen(self.h, int(s))
+        return self._view(p, int(self.c.vocab), torch.int32)
 
     def seq_alloc(self):
         """-> sequence slot id (raises VitaHipError, code VH_E_FULL, when every slot is taken)."""

@@ -22,7 +22,7 @@ from .encoders import InternViTVisionTower, VisionProjector, WhaleAudioEncoder, 
 
 
 class GenerateOutput(SimpleNamespace):
-    """Minimal stand-in for HF GenerateDecoderOnlyOutput: .sequences, .scores."""
+    """Minimal stand-in for HF GenerateDecoderOnlyOutput: .sequences, .scores (+ .logprobs with output_logprobs=K)."""
 
     def __getitem__(self, k):
         return getattr(self, k)
@@ -51,7 +51,7 @@ class _Backbone(_HipModule):
 class VITAMixtralForCausalLM(_HipModule):
     def __init__(self, cfg: VitaConfig, state_dict, device="cuda:0", packed_llm=None, max_new_tokens=1024,
                  max_prefill=None, rank=0, world=1, keep_scores=True, max_seqs=0, kv_pool_tokens=None,
-                 gpu_memory_utilization=None, experts_int8=False):
+                 gpu_memory_utilization=None, experts_int8=False, penalty_tables=False, max_logprobs=0):
         super().__init__()
         from ..checkpoint import pack_mixtral
         self.vcfg_all = cfg
@@ -85,7 +85,8 @@ class VITAMixtralForCausalLM(_HipModule):
         self.engine = MixtralEngine(cfg, self.packed, self._device, max_prefill=self.max_prefill,
                                     max_new=max_new_tokens, rank=rank, world=world,
                                     logit_rows=max_new_tokens if keep_scores else 0,
-                                    max_seqs=max_seqs, max_ctx=kv_pool_tokens)   # max_seqs > 0: paged KV pool (serving)
+                                    max_seqs=max_seqs, max_ctx=kv_pool_tokens,   # max_seqs > 0: paged KV pool (serving)
+                                    penalty_tables=penalty_tables, max_logprobs=max_logprobs)
         self.lookahead = 8          # decode steps enqueued per host synchronisation in generate()
         self.last_timing = {}
         self.overlap_encoders = True      # audio tower on a side stream under the vision tower (prepare_inputs_labels_for_multimodal)
@@ -245,10 +246,16 @@ class VITAMixtralForCausalLM(_HipModule):
     def generate(self, input_ids=None, images=None, audios=None, do_sample=False, temperature=None, top_p=None,
                  num_beams=1, output_scores=False, return_dict_in_generate=False, max_new_tokens=None,
                  use_cache=True, stopping_criteria=None, inputs_embeds=None, attention_mask=None,
-                 eos_token_id=None, streamer=None, top_k=None, seed=None, audio_valid_rows=False, **kwargs):
+                 eos_token_id=None, streamer=None, top_k=None, seed=None, audio_valid_rows=False, repetition_penalty=None,
+                 output_logprobs=None, presence_penalty=0.0, frequency_penalty=0.0, penalty_prompt_ids=None, **kwargs):
         """HF generate.  do_sample=True draws on the device (temperature -> top-k -> top-p, Gumbel-max over a Philox stream keyed
         by `seed`; include/vita_hip.h vh_sampling) and needs seed=: the ids are a function of the request.  Unset parameters take
-        HF's defaults (temperature 1.0, top_k 50, top_p 1.0).  scores stay the raw logits."""
+        HF's defaults (temperature 1.0, top_k 50, top_p 1.0).  scores stay the raw logits.
+        repetition_penalty: HF's RepetitionPenaltyLogitsProcessor on the device (include/vita_hip.h vh_logit_rules); on this
+        inputs_embeds path HF penalises the generated ids only, so the prompt set is empty unless penalty_prompt_ids names one (the
+        serving surface passes the request's expanded ids, as vLLM does; presence_penalty / frequency_penalty are vLLM's).
+        output_logprobs=K (0..max_logprobs): the dict output gains .logprobs, per generated token {id: logprob} of the top K and the
+        chosen id under log_softmax of the RAW scores.  Both need a model built with penalty_tables=True / max_logprobs=K."""
         if num_beams != 1:
             raise NotImplementedError("vita_amd implements num_beams=1 (greedy or seeded sampling)")
         if do_sample and seed is None:
@@ -262,6 +269,15 @@ class VITAMixtralForCausalLM(_HipModule):
             if self.engine.vocab_sharded and (top_k > 0 or top_p < 1.0):
                 raise ValueError("top-k / top-p need an unsharded LM head (this model's head is vocab-sharded over the TP ranks); "
                                  "pass top_k=0 and top_p=1.0 for temperature-only sampling (HF's default top_k is 50)")
+        rp = 1.0 if repetition_penalty is None else float(repetition_penalty)
+        pen_on = rp != 1.0 or float(presence_penalty) != 0.0 or float(frequency_penalty) != 0.0
+        n_lp = -1 if output_logprobs is None or output_logprobs is False else int(output_logprobs)
+        if pen_on and not self.engine.c.penalty_tables:
+            raise ValueError("penalties need a model built with penalty_tables=True (LLM: max_logprobs > 0 or penalty_tables=True)")
+        if n_lp >= 0 and n_lp > self.engine.c.max_logprobs:
+            raise ValueError(f"output_logprobs={n_lp} exceeds the model's max_logprobs={self.engine.c.max_logprobs}")
+        if n_lp >= 0 and self.engine.c.max_logprobs <= 0:
+            raise ValueError("output_logprobs needs a model built with max_logprobs > 0")
         max_new = int(max_new_tokens or self.generation_config.max_new_tokens or 20)
         if max_new > self.max_new_tokens:
             raise ValueError(f"max_new_tokens={max_new} exceeds the engine capacity {self.max_new_tokens}")
@@ -281,6 +297,10 @@ class VITAMixtralForCausalLM(_HipModule):
             eng.set_sampling(temperature, top_k, top_p, int(seed))
         else:
             eng.set_sampling()
+        if pen_on or n_lp >= 0:
+            eng.set_logit_rules(rp, presence_penalty, frequency_penalty, n_lp, prompt_ids=penalty_prompt_ids)
+        elif eng.has_logit_rules:
+            eng.set_logit_rules()          # off: the kernels and launches of an engine without rules
         eng.prefill(emb)
         prompt = input_ids if input_ids is not None else torch.zeros((1, 0), dtype=torch.long, device=self._device)
         prompt = prompt.to(self._device)
@@ -332,4 +352,22 @@ class VITAMixtralForCausalLM(_HipModule):
             # vocab-sharded head: a kept row holds this rank's slice and zeros elsewhere; the sum is the full row
             rows = eng.gather_vocab(eng.logits_all[:len(generated)]) if eng.vocab_sharded else eng.logits_all[:len(generated)].clone()
             scores = tuple(rows[i][None] for i in range(len(generated)))
-        return GenerateOutput(sequences=sequences, scores=scores, past_key_values=None)
+        out = GenerateOutput(sequences=sequences, scores=scores, past_key_values=None)
+        if n_lp >= 0:
+            out.logprobs = logprob_dicts(eng.logprobs(), generated, n_lp)
+        return out
+
+
+def logprob_dicts(views, token_ids, K):
+    """(token, top_ids, top) logprob buffers -> per generated token {id: logprob}: the top K ids (entries past the vocabulary,
+    id -1, dropped) plus the chosen id."""
+    n = len(token_ids)
+    tok = views[0][:n].tolist()
+    ids = views[1][:n, :K].tolist()
+    top = views[2][:n, :K].tolist()
+    out = []
+    for i in range(n):
+        d = {int(v): float(x) for v, x in zip(ids[i], top[i]) if v >= 0}
+        d.setdefault(int(token_ids[i]), float(tok[i]))
+        out.append(d)
+    return out

@@ -533,3 +533,35 @@ def sample_rows(logits, rows=None, temperature=1.0, top_k=0, top_p=1.0, seed=0, 
     s = _lib.sampling(temperature, top_k, top_p, seed, draw0)
     check(_lib.load().vh_sample_rows(_p(logits), ld, n, V, C.byref(s), _p(tok), _stream()), "vh_sample_rows")
     return tok
+
+
+def logit_rules_rows(logits, seen=None, repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, tokens=None, logprobs=-1,
+                     want_penalised=True):
+    """The engine's logit rules (vh_logit_rules_rows) on rows of logits fp32 [R, V]: -> (penalised [R, V] or None, lp_tok [R] or
+    None, lp_top_id [R, K] or None, lp_top [R, K] or None).  seen: int32 / uint32 [V] token table shared by the rows (bit 31 = in
+    the prompt, low bits = output count; None = no history); tokens int32 [R] + logprobs = K >= 0: the log-probability of tokens[r]
+    and the top K of the RAW row r."""
+    _dev(logits)
+    if logits.dtype != torch.float32 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise TypeError("logits must be float32 [R, V] with contiguous rows")
+    R, V = logits.shape
+    K = -1 if logprobs is None else int(logprobs)
+    if seen is not None and (seen.numel() != V or seen.element_size() != 4 or not seen.is_contiguous()):
+        raise ValueError("seen must be a contiguous 32-bit table of V entries")
+    pen = torch.empty((R, V), dtype=torch.float32, device=logits.device) if want_penalised else None
+    lp_tok = lp_id = lp_top = None
+    if K >= 0:
+        if tokens is None or tokens.dtype != torch.int32 or tokens.numel() != R:
+            raise ValueError("logprobs need tokens int32 [R]")
+        lp_tok = torch.empty(R, dtype=torch.float32, device=logits.device)
+        lp_id = torch.empty((R, max(K, 1)), dtype=torch.int32, device=logits.device)
+        lp_top = torch.empty((R, max(K, 1)), dtype=torch.float32, device=logits.device)
+    r = _lib.logit_rules(repetition_penalty, presence_penalty, frequency_penalty, -1)
+    check(_lib.load().vh_logit_rules_rows(_p(logits), logits.stride(0), R, V, C.byref(r), _p(seen) if seen is not None else None,
+                                          _p(pen) if pen is not None else None, _p(tokens) if K >= 0 else None,
+                                          _p(lp_tok) if K >= 0 else None, _p(lp_id) if K >= 0 else None,
+                                          _p(lp_top) if K >= 0 else None, max(K, 0), _stream()), "vh_logit_rules_rows")
+    if K >= 0:
+        lp_id, lp_top = lp_id[:, :K], lp_top[:, :K]
+    return pen, lp_tok, lp_id, lp_top
+

@@ -48,6 +48,33 @@ class SamplingParams:
     top_p: float = 1.0
     top_k: int = -1
     seed: Optional[int] = None
+    # logit rules on the device (include/vita_hip.h vh_logit_rules), vLLM's names and ranges: the penalties see the request's
+    # expanded prompt ids and its output so far; logprobs = K returns, per generated token, the top K and the chosen id under
+    # log_softmax of the RAW logits (vLLM's default)
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logprobs: Optional[int] = None
+
+    def __post_init__(self):
+        if not 0.0 < float(self.repetition_penalty) <= 2.0:
+            raise ValueError(f"repetition_penalty must be in (0, 2], got {self.repetition_penalty}")
+        for name in ("presence_penalty", "frequency_penalty"):
+            if not -2.0 <= float(getattr(self, name)) <= 2.0:
+                raise ValueError(f"{name} must be in [-2, 2], got {getattr(self, name)}")
+        if self.logprobs is not None and not 0 <= int(self.logprobs) <= 20:
+            raise ValueError(f"logprobs must be in [0, 20], got {self.logprobs}")
+
+
+def rules_of(sp):
+    """the logit rules of a request (keywords of MixtralEngine.set_logit_rules / seq_set_logit_rules without the ids), or None when
+    it has neither penalties nor logprobs."""
+    if sp is None:
+        return None
+    r, p, f = float(sp.repetition_penalty), float(sp.presence_penalty), float(sp.frequency_penalty)
+    if r == 1.0 and p == 0.0 and f == 0.0 and sp.logprobs is None:
+        return None
+    return dict(repetition_penalty=r, presence_penalty=p, frequency_penalty=f, logprobs=-1 if sp.logprobs is None else int(sp.logprobs))
 
 
 def sampling_of(sp):
@@ -71,6 +98,8 @@ class CompletionOutput:
     text: str
     token_ids: List[int]
     finish_reason: str = "length"
+    logprobs: Optional[List[dict]] = None           # SamplingParams(logprobs=K): per token {id: logprob}, the top K + the chosen id
+    cumulative_logprob: Optional[float] = None      # sum of the chosen ids' log-probabilities
 
 
 @dataclass
@@ -132,10 +161,19 @@ def expanded_token_ids(sentinel_ids, audio_frames, *, image_token_index, audio_t
     return out
 
 
+def completion(index, text, token_ids, reason, logprobs=None):
+    """CompletionOutput with .logprobs / .cumulative_logprob filled from the per-token {id: logprob} dicts (None: not asked for)."""
+    out = CompletionOutput(index, text, token_ids, reason)
+    if logprobs is not None:
+        out.logprobs = logprobs[:len(token_ids)]
+        out.cumulative_logprob = float(sum(d[t] for d, t in zip(out.logprobs, token_ids)))
+    return out
+
+
 class LLM:
     def __init__(self, model, dtype=None, tensor_parallel_size=1, trust_remote_code=True, gpu_memory_utilization=None,
                  disable_custom_all_reduce=True, limit_mm_per_prompt=None, max_new_tokens=1024, device="cuda",
-                 max_num_seqs=0, kv_pool_tokens=None, quantization=None, **_):
+                 max_num_seqs=0, kv_pool_tokens=None, quantization=None, max_logprobs=0, penalty_tables=None, **_):
         from .model.builder import load_pretrained_model
         # vLLM's quantization="experts_int8": the MoE experts as int8 with per-output-row scales (DESIGN 5.5)
         if quantization not in (None, "experts_int8"):
@@ -155,7 +193,10 @@ class LLM:
         self.tokenizer, self.model, self.image_processor, _ = load_pretrained_model(
             model, None, os.path.basename(str(model).rstrip("/")), "mixtral-8x7b", device=device,
             max_new_tokens=max_new_tokens, max_seqs=int(max_num_seqs), kv_pool_tokens=kv_pool_tokens,
-            gpu_memory_utilization=gpu_memory_utilization, load_8bit=quantization == "experts_int8", **kw)
+            gpu_memory_utilization=gpu_memory_utilization, load_8bit=quantization == "experts_int8",
+            # max_logprobs > 0 (vLLM's name): logprob buffers AND token tables for the engine and every sequence slot, so that
+            # SamplingParams' penalties and logprobs run on the device; penalty_tables=True alone: the tables only
+            max_logprobs=int(max_logprobs), penalty_tables=bool(max_logprobs) if penalty_tables is None else bool(penalty_tables), **kw)
         self.collective = "none"
         if world > 1:
             from .parallel import setup_tensor_parallel
@@ -222,8 +263,21 @@ class LLM:
         else:
             feats, lens = torch.zeros((1, 400, enc.acfg.input_dim)), torch.tensor([400])
         eos = {self.model.generation_config.eos_token_id, *(sp.stop_token_ids or [])} - {None}
+        rules, prompt_set = rules_of(sp), None
+        if rules is not None:
+            eng = self.model.engine
+            pen = (rules["repetition_penalty"], rules["presence_penalty"], rules["frequency_penalty"]) != (1.0, 0.0, 0.0)
+            if (pen and not eng.c.penalty_tables) or rules["logprobs"] > eng.c.max_logprobs:
+                raise ValueError(f"penalties / logprobs={sp.logprobs} need LLM(max_logprobs=K) with K >= logprobs "
+                                 f"(this engine: max_logprobs={eng.c.max_logprobs}, penalty_tables={bool(eng.c.penalty_tables)})")
+            # the prompt set of the penalties: the ids vLLM sees as prompt_token_ids (placeholders widened); ids that are not rows
+            # of the LM head can never be generated and are left out
+            frames = [int(a.shape[0]) for a in audios]
+            exp = expanded_token_ids(sent, frames, image_token_index=self.image_token_index, audio_token_index=self.audio_token_index)
+            V = int(self.model.config.vocab_size)
+            prompt_set = sorted({t for t in exp if 0 <= t < V})
         return dict(ids=ids, sent=sent, pix=pix, feats=feats.to(dev), lens=lens.to(dev), normalized=normalized,
-                    max_tokens=max_tokens, eos=eos)
+                    max_tokens=max_tokens, eos=eos, rules=rules, prompt_set=prompt_set)
 
     @torch.no_grad()
     def _embed(self, req):
@@ -246,12 +300,16 @@ class LLM:
         dev = self.model.device
         enc = self.model.get_audio_encoder()
         enc.normalized_input = req["normalized"]
+        rules = req.get("rules")
+        rkw = {} if rules is None else dict(repetition_penalty=rules["repetition_penalty"], presence_penalty=rules["presence_penalty"],
+                                             frequency_penalty=rules["frequency_penalty"], penalty_prompt_ids=req["prompt_set"],
+                                             output_logprobs=rules["logprobs"] if rules["logprobs"] >= 0 else None)
         try:
             out = self.model.generate(torch.tensor([sent], dtype=torch.long, device=dev), images=pix,
                                       audios={"audios": feats.to(dev), "lengths": lens.to(dev)}, num_beams=1,
                                       return_dict_in_generate=True, max_new_tokens=max_tokens,
                                       eos_token_id=list(req["eos"]), streamer=streamer, audio_valid_rows=True,
-                                      **sample_kwargs(sp))
+                                      **sample_kwargs(sp), **rkw)
         finally:
             enc.normalized_input = False
         gen = out.sequences[0, len(sent):].tolist()
@@ -259,8 +317,9 @@ class LLM:
         reason = "stop" if gen and gen[-1] in eos else "length"
         text = self.tokenizer.decode(gen, skip_special_tokens=sp.skip_special_tokens)
         self._n += 1
+        lps = getattr(out, "logprobs", None)
         return RequestOutput(request_id=str(self._n - 1), prompt_token_ids=ids,
-                             outputs=[CompletionOutput(0, text, gen, reason)], metrics=dict(self.model.last_timing))
+                             outputs=[completion(0, text, gen, reason, lps)], metrics=dict(self.model.last_timing))
 
     def generate_stream(self, inputs, sampling_params: SamplingParams = None, request_id=None, should_stop=None):
         """Generator of RequestOutput with the CUMULATIVE text after every decode window — the shape of
@@ -344,17 +403,26 @@ class ContinuousBatcher:
         self.running = []                 # admission order
         self.errors = {}                  # request id -> exception of a request that failed alone (event reason "error")
         self.stats = {"iterations": 0, "prefills": 0, "prefill_calls": 0, "preemptions": 0, "decode_steps": 0, "failed": 0}
+        self.logprobs = {}                # request id -> per-token {id: logprob} of requests with rules["logprobs"] >= 0; the entry of a
+                                          # finished request stays until the caller pops it (a failed or aborted one is dropped here)
 
-    def add(self, request_id, embeds, max_tokens, eos=(), sampling=None):
-        """sampling: None (greedy) or the keywords of MixtralEngine.seq_set_sampling without draw0 (see sampling_of)."""
+    def add(self, request_id, embeds, max_tokens, eos=(), sampling=None, rules=None, prompt_ids=None):
+        """sampling: None (greedy) or the keywords of MixtralEngine.seq_set_sampling without draw0 (see sampling_of).
+        rules: None or the keywords of MixtralEngine.seq_set_logit_rules without the ids (see rules_of); prompt_ids: the prompt set
+        of the penalties.  The rules are re-armed with prompt and output ids after a recompute preemption, and the logprobs of a
+        request (self.logprobs[request_id]) run on across it."""
         S = int(embeds.shape[0])
         if S + 2 > self.eng.max_ctx or S > self.eng.max_prefill:
             raise ValueError(f"prompt of {S} tokens exceeds the engine (max_prefill {self.eng.max_prefill}, pool "
                              f"{self.eng.max_ctx} tokens)")
         self.waiting.append(dict(id=request_id, emb=embeds, max_tokens=min(int(max_tokens), self.eng.max_new),
-                                 eos=set(eos), out=[], seq=None, base=0, sampling=sampling))
+                                 eos=set(eos), out=[], seq=None, base=0, sampling=sampling, rules=rules,
+                                 prompt_ids=list(prompt_ids or ())))
+        if rules is not None and rules.get("logprobs", -1) >= 0:
+            self.logprobs[request_id] = []
 
     def abort(self, request_id):
+        self.logprobs.pop(request_id, None)
         for r in list(self.running):
             if r["id"] == request_id:
                 self.eng.seq_free(r["seq"])
@@ -377,13 +445,21 @@ class ContinuousBatcher:
         takes — in chunks of max_prefill (seq_prefill appends at the sequence's position)."""
         emb, mp = r["emb"], int(self.eng.max_prefill)
         for s0 in range(0, int(emb.shape[0]), mp):
+            if s0 > 0 and s0 + mp >= int(emb.shape[0]):
+                self._arm(r)                 # a chunked re-prompt: only the LAST chunk's token is an output (the table counts it)
             self.eng.seq_prefill(r["seq"], emb[s0:s0 + mp])
             self.stats["prefill_calls"] += 1
+
+    def _arm(self, r):
+        """the logit rules of r's slot with its history: the prompt set, and every token generated so far as outputs."""
+        if r.get("rules") is not None:
+            self.eng.seq_set_logit_rules(r["seq"], prompt_ids=r["prompt_ids"], output_ids=r["out"], **r["rules"])
 
     def _fail(self, r, exc, events):
         """ONE request failed (its prompt does not fit, its prefill was rejected): it ends with an "error" event, nobody else
         is touched.  Device-level failures (spin time-outs, launch errors seen at the synchronisation) still propagate."""
         self.errors[r["id"]] = exc
+        self.logprobs.pop(r["id"], None)
         self.stats["failed"] += 1
         events.append((r["id"], [], True, "error"))
 
@@ -452,6 +528,14 @@ class ContinuousBatcher:
                     self._fail(r, e, events)
                     continue
             S = int(r["emb"].shape[0])
+            if S <= mp:                          # (a chunked re-prompt arms its rules in front of its last chunk: _prefill)
+                try:
+                    self._arm(r)
+                except Exception as e:
+                    self.eng.seq_free(r["seq"])
+                    r["seq"] = None
+                    self._fail(r, e, events)
+                    continue
             if not can_batch or S > mp:          # no batched entry point / a re-prompt that goes in chunks: alone, in order
                 self._prefill_group(group, events)
                 rows = 0
@@ -514,6 +598,11 @@ class ContinuousBatcher:
             n_dev = min(cnt[1], self.eng.max_new)                 # tokens of this (re)prefill + its decode steps
             have = len(r["out"]) - r["base"]
             new = self.eng.seq_tokens(r["seq"])[have:n_dev].tolist()
+            new_lp = None
+            if r["id"] in self.logprobs and n_dev > have:
+                from .model.vita_mixtral import logprob_dicts
+                views = self.eng.logprobs(r["seq"])
+                new_lp = logprob_dicts(tuple(v[have:n_dev] for v in views), new, r["rules"]["logprobs"])
             r["fresh"] = False
             accepted, reason = [], None
             for tok in new:
@@ -525,6 +614,8 @@ class ContinuousBatcher:
                 if reason:
                     break
             r["out"] += accepted
+            if new_lp is not None:
+                self.logprobs[r["id"]] += new_lp[:len(accepted)]
             if reason is None and (r is starved or self.eng.seq_pos(r["seq"]) + 2 >= self.eng.max_ctx):
                 reason = "length"                                 # the pool cannot hold another token of this sequence
             if reason:
@@ -551,6 +642,7 @@ class AsyncEngineArgs:
                                              # bounded by gpu_memory_utilization of the free memory (VITAMixtralForCausalLM.default_kv_pool_tokens)
     device: str = "cuda"
     quantization: Optional[str] = None       # None or "experts_int8" (LLM)
+    max_logprobs: int = 0                    # > 0 (<= 20): SamplingParams' penalties and logprobs on the device (LLM)
 
 
 class AsyncLLMEngine:
@@ -582,7 +674,8 @@ class AsyncLLMEngine:
         llm = LLM(args.model, dtype=args.dtype, tensor_parallel_size=args.tensor_parallel_size,
                   gpu_memory_utilization=args.gpu_memory_utilization,
                   limit_mm_per_prompt=args.limit_mm_per_prompt, max_new_tokens=args.max_new_tokens, device=args.device,
-                  max_num_seqs=args.max_num_seqs, kv_pool_tokens=pool, quantization=args.quantization)
+                  max_num_seqs=args.max_num_seqs, kv_pool_tokens=pool, quantization=args.quantization,
+                  max_logprobs=args.max_logprobs)
         return cls(llm, max_num_seqs=args.max_num_seqs, **kw)
 
     async def get_tokenizer(self):
@@ -614,7 +707,8 @@ class AsyncLLMEngine:
                 try:
                     req = self.llm._prepare(inputs, sp)
                     emb = self.llm._embed(req)
-                    self.batcher.add(rid, emb, req["max_tokens"], req["eos"], sampling=sampling_of(sp))
+                    self.batcher.add(rid, emb, req["max_tokens"], req["eos"], sampling=sampling_of(sp), rules=req.get("rules"),
+                                     prompt_ids=req.get("prompt_set"))
                     state[rid] = (req["ids"], sp, [])
                 except BaseException as e:          # surfaced to the caller's iterator
                     self._post(rid, e)
@@ -625,6 +719,7 @@ class AsyncLLMEngine:
                     self._post(rid, e)
                 state.clear()
                 self.batcher.waiting.clear()
+                self.batcher.logprobs.clear()
                 for r in list(self.batcher.running):
                     self.batcher.abort(r["id"])
                 continue
@@ -638,8 +733,9 @@ class AsyncLLMEngine:
                 ids, sp, toks = state[rid]
                 toks += new
                 text = self.llm.tokenizer.decode(toks, skip_special_tokens=sp.skip_special_tokens)
+                lps = self.batcher.logprobs.pop(rid, None) if finished else self.batcher.logprobs.get(rid)
                 self._post(rid, RequestOutput(request_id=str(rid), prompt_token_ids=ids, finished=finished,
-                                              outputs=[CompletionOutput(0, text, list(toks), reason)]))
+                                              outputs=[completion(0, text, list(toks), reason, lps)]))
                 if finished:
                     state.pop(rid)
 
