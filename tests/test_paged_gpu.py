@@ -123,6 +123,75 @@ def test_pages_are_reused_and_legacy_api_is_fenced(dev):
     eng.close()
 
 
+def test_slot_traffic_leaves_the_single_sequence_state_alone(dev):
+    """The engine-level sampling, logit rules, token table, logprob rows and buffers belong to the single-sequence engine alone: two
+    slots with OTHER sampling and rules are prefilled, stepped one at a time and in batched iterations, and freed; a single-sequence
+    request on the same engine afterwards is, bit for bit, the request of an engine that never saw a slot, and each slot's ids are
+    those of its request alone.  70 tokens cross a 64-token page."""
+    from vita_amd.engine import MixtralEngine
+    n_new = 6
+    cfg = VitaConfig.tiny()
+    sd = synth_state_dict(cfg, seed=5, parts=("text",))
+    rng = np.random.default_rng(12)
+    prompts = [rng.integers(3, cfg.text.vocab_size, size=S).tolist() for S in (70, 33)]
+    embs = [torch.from_numpy(sd["model.embed_tokens.weight"][p]).to(dev) for p in prompts]
+    packed = pack_mixtral(sd, cfg, dev)
+    samp_e = dict(temperature=0.8, top_k=12, top_p=0.9, seed=1234)
+    rules_e = dict(repetition_penalty=1.3, logprobs=5, prompt_ids=prompts[0])
+    samp_b = dict(temperature=0.8, top_k=12, top_p=0.9, seed=99)
+    rules_b = dict(presence_penalty=0.5, logprobs=2, prompt_ids=prompts[1])
+
+    def engine():
+        return MixtralEngine(cfg, packed, dev, max_ctx=1024, max_prefill=70 + n_new + 8, max_new=n_new + 4, max_seqs=2,
+                             penalty_tables=True, max_logprobs=5)
+
+    def single(eng, emb):
+        """prefill + decode through the single-sequence entry points -> ids, logprob rows, token table"""
+        eng.prefill(emb)
+        eng.decode(n_new - 1)
+        torch.cuda.synchronize()
+        tok, top_id, top = eng.logprobs()
+        return (eng.generated(),) + tuple(t.cpu().numpy().copy() for t in (tok[:n_new], top_id[:n_new], top[:n_new], eng.seen_table()))
+
+    eng = engine()
+    ptrs = (eng.lib.vh_mixtral_counters(eng.h), eng.lib.vh_mixtral_tokens(eng.h))
+    eng.set_sampling(**samp_e)
+    eng.set_logit_rules(**rules_e)
+    a, b = eng.seq_alloc(), eng.seq_alloc()                 # a: greedy, no rules (what seq_alloc leaves)
+    eng.seq_set_sampling(b, **samp_b)
+    eng.seq_set_logit_rules(b, **rules_b)
+    eng.seq_prefill(a, embs[0])
+    eng.seq_prefill(b, embs[1])
+    eng.seq_decode([a])                                     # the one-at-a-time branch
+    for _ in range(n_new - 2):
+        eng.seq_decode([a, b])                              # batched iterations
+    eng.seq_decode([b])
+    ids_a, ids_b = _ids(eng, a, n_new), _ids(eng, b, n_new)
+    eng.seq_free(a)
+    eng.seq_free(b)
+    assert (eng.lib.vh_mixtral_counters(eng.h), eng.lib.vh_mixtral_tokens(eng.h)) == ptrs == (eng._cnt_ptr, eng._tok_ptr)
+    got = single(eng, embs[0])
+    eng.close()
+
+    ref = engine()                                          # the same setters, prefill and decode; never a slot
+    ref.set_sampling(**samp_e)
+    ref.set_logit_rules(**rules_e)
+    want = single(ref, embs[0])
+    assert got[0] == want[0], (got[0], want[0])
+    for name, g, w in zip(("token logprobs", "top ids", "top logprobs", "token table"), got[1:], want[1:]):
+        assert np.array_equal(g, w), name
+    assert int((want[4] & 0x7FFFFFFF).sum()) == n_new      # the request did run under its rules: every token it wrote was counted
+    # each slot's request alone (single-sequence entry points of the untouched engine)
+    ref.reset()
+    assert single(ref, embs[0])[0] == ids_a, "the greedy slot differs from its solo run"
+    ref.reset()
+    ref.set_sampling(**samp_b)
+    ref.set_logit_rules(**rules_b)
+    assert single(ref, embs[1])[0] == ids_b, "the sampled slot differs from its solo run"
+    assert ids_a != got[0]                                  # the engine-level sampling and rules did not leak into slot a
+    ref.close()
+
+
 def test_pool_and_slot_exhaustion(dev):
     from vita_amd._lib import VitaHipError
     _, _, eng, (A, B) = _setup(dev, [100, 100], 4, pool=192, max_seqs=2)      # 3 pages: A takes 2

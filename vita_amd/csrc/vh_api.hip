@@ -352,8 +352,7 @@ struct vh_mixtral {
     int nq, nkv, hd, H, I, E, V, nqkv, max_splits, lm_grid;
     int v0 = 0, Vn = 0;         // this rank's rows of the LM head ([v0, v0 + Vn); the whole table when unsharded)
     float* cand = nullptr;      // [tp_world][2] (value, index) candidates of the vocab-sharded head
-    int host_pos = 0;  // host mirror of counters[0] (sizes the split-KV grid without a device read)
-    // state
+    // state (xa .. delta_moe, counters, out_tokens: where carve() puts the single-sequence engine's; read through units[0])
     float *kcache, *vcache;  // [layer][nkv][max_ctx][hd]
     float *xa, *xb, *delta_attn, *delta_moe, *qkv, *part_o, *part_ml, *attn_out, *hbuf, *logits, *blk_val;
     int *blk_idx, *route, *counters, *out_tokens, *attn_cnt;
@@ -364,20 +363,39 @@ struct vh_mixtral {
     int *pids, *pgoff, *pstok, *psslot, *pnslab;
     // ---- concurrent sequences over a paged KV cache (vLLM's block tables).  The KV pool above is cut into
     // 64-token pages (= one decode-attention tile); a sequence owns a page table, a residual-stream state, its counters
-    // and its generated ids.  The kernels see ONE sequence at a time: bind() points the engine's "current sequence"
-    // members (xa .. out_tokens, table, host mirrors) at a sequence's slots, unbind() restores the default single-sequence
-    // state, so prefill and decode are the same code for both.
+    // and its generated ids.  All of it is reached through ONE record per state owner (Unit): units[0] is the single-sequence
+    // engine, units[1 + s] sequence slot s.  Prefill, a decode step and the head take the unit they work on, so they are the
+    // same code for both; the batched iteration and the batched prefill take a list of units.
     // logit rules of one request (vh_logit_rules): penalties read the request's token table, K >= 0 runs k_dec_logprobs after the select
     struct Rules {
         float r = 1.f, f = 0.f, p = 0.f; int K = -1;
         bool pen() const { return r != 1.f || f != 0.f || p != 0.f; }
     };
-    struct Seq {
+    struct Unit {
+        // device buffers, fixed once init_units() has run
+        float *xa = nullptr, *xb = nullptr, *da = nullptr, *dm = nullptr;   // residual stream in / out, attention delta, MoE delta ([H] each)
+        int *counters = nullptr;           // {pos, n_generated, attn_done (monotonic), device error flag}
+        int *tokens = nullptr;             // [lp_rows()] generated ids
+        int *table = nullptr;              // [max_splits] page table; null = contiguous rows (unit 0)
+        unsigned* seen = nullptr;          // [V] token table of the penalties (cfg.penalty_tables, else null)
+        float *lp_tok = nullptr, *lp_top = nullptr; int* lp_top_id = nullptr;   // [lp_rows()] / [lp_rows()][max_logprobs] (cfg.max_logprobs, else null)
+        // host mirrors
+        int host_pos = 0;                  // mirror of counters[0] (sizes the split-KV grid without a device read)
+        int poisoned = 0;                  // a step was enqueued in part: unit 0 needs a prefill / reset, a slot is lost until freed
+        bool seen_dirty = false;           // the token table holds a history (a setter call without penalties clears it)
+        VhSampleParams samp{};             // vh_mixtral_[seq_]set_sampling (T = 0: greedy)
+        Rules rules{};                     // vh_mixtral_[seq_]set_logit_rules (off)
+        VhPenalty pen() const { return rules.pen() ? VhPenalty{seen, rules.r, rules.f, rules.p, 0} : VhPenalty{}; }
+        // what reset / seq_alloc / seq_free leave: position 0, greedy, no logit rules
+        void fresh() { host_pos = 0; poisoned = 0; samp = VhSampleParams{}; rules = Rules{}; }
+    };
+    std::vector<Unit> units;               // [1 + max_seqs]
+    Unit& slot(int s) { return units[1 + s]; }
+    const Unit& slot(int s) const { return units[1 + s]; }
+    struct Seq {                           // paging state of slot s (the rest of the slot is units[1 + s])
         bool live = false;
-        int host_pos = 0, poisoned = 0, npages = 0;
-        VhSampleParams samp{};         // vh_mixtral_seq_set_sampling (T = 0: greedy)
-        Rules rules{};                 // vh_mixtral_seq_set_logit_rules (off)
-        std::vector<int> pages;        // host mirror of the device table (sized once: uploads read from it)
+        int npages = 0;
+        std::vector<int> pages;            // host mirror of the device table (sized once: uploads read from it)
     };
     std::vector<Seq> seqs;
     std::vector<int> free_pages;
@@ -386,52 +404,24 @@ struct vh_mixtral {
     VhSeg* seq_segs = nullptr;         // [max_seqs] the same on the device
     float* seq_x = nullptr;            // [max_seqs][4][H]: xa, xb, delta_attn, delta_moe
     int *seq_counters = nullptr, *seq_tokens = nullptr, *seq_table = nullptr, *seq_batch = nullptr;
-    // scratch "lanes" 1..VH_BMAX-1 of the per-step buffers (lane 0 = the single-sequence ones) for batched decode iterations
+    // scratch "lanes" of the per-step buffers for batched decode iterations: lane 0 = the single-sequence ones, lanes 1..VH_BMAX-1
+    // exist only with sequence slots
     float *l_qkv[VH_BMAX] = {}, *l_part_o[VH_BMAX] = {}, *l_part_ml[VH_BMAX] = {}, *l_attn_out[VH_BMAX] = {}, *l_hbuf[VH_BMAX] = {},
           *l_blk_val[VH_BMAX] = {}, *l_cand[VH_BMAX] = {};
     int *l_attn_cnt[VH_BMAX] = {}, *l_route[VH_BMAX] = {}, *l_blk_idx[VH_BMAX] = {};
-    const int* table = nullptr;        // device page table of the bound sequence; null = contiguous rows (default state)
-    int bound = -1;
-    struct { float *xa, *xb, *da, *dm; int *counters, *out_tokens; int host_pos, poisoned; VhSampleParams samp; Rules rules; } dflt{};
-    VhSampleParams samp{};             // sampling of the bound sequence / of the single-sequence engine (T = 0: greedy)
-    Rules rules{};                     // logit rules of the bound sequence / of the single-sequence engine (off)
-    // state of the logit rules, one unit per owner: unit 0 = the single-sequence engine, unit 1 + s = sequence slot s
+    // state of the logit rules, one row per unit
     unsigned* seen_tab = nullptr;      // [1 + max_seqs][V] token tables (cfg.penalty_tables)
     float *lp_tok = nullptr, *lp_top = nullptr; int* lp_top_id = nullptr;   // [1 + max_seqs][max_new] / [..][max_new][max_logprobs]
-    std::vector<char> seen_dirty;      // per unit: the table holds a history (a setter call without penalties clears it)
     int device = -1;                   // the device the workspace lives on (the setters synchronise THAT device)
-    int lp_rows() const { return c.max_new > 0 ? c.max_new : 1; }
-    int unit() const { return bound + 1; }
-    unsigned* seen_of(int u) const { return seen_tab ? seen_tab + (size_t)u * V : nullptr; }
-    VhPenalty pen_of(const Rules& r, int u) const { return r.pen() ? VhPenalty{seen_of(u), r.r, r.f, r.p, 0} : VhPenalty{}; }
-    void logprob_slot(VhDecLogprobJob& j, int u, const Rules& r, const float* row, const int* ngen, const int* toks) const {
+    int lp_rows() const { return c.max_new > 0 ? c.max_new : 1; }   // rows of a unit's token / logprob buffers
+    void logprob_slot(VhDecLogprobJob& j, const Unit& u, const float* row) const {
         const int q = j.n++;
-        j.logits[q] = row; j.ngen[q] = ngen; j.tokens[q] = toks; j.K[q] = r.K;
-        j.lp_tok[q] = lp_tok + (size_t)u * lp_rows();
-        j.lp_top_id[q] = lp_top_id + (size_t)u * lp_rows() * c.max_logprobs;
-        j.lp_top[q] = lp_top + (size_t)u * lp_rows() * c.max_logprobs;
+        j.logits[q] = row; j.ngen[q] = u.counters + 1; j.tokens[q] = u.tokens; j.K[q] = u.rules.K;
+        j.lp_tok[q] = u.lp_tok; j.lp_top_id[q] = u.lp_top_id; j.lp_top[q] = u.lp_top;
     }
     float* samp_rows = nullptr;        // [VH_BMAX][V] logits rows of the batched head for sequences with a top-k / top-p filter
     int n_pages() const { return c.max_ctx / 64; }
     int live_seqs() const { int n = 0; for (const Seq& q : seqs) n += q.live; return n; }
-    void bind(int s) {
-        dflt = {xa, xb, delta_attn, delta_moe, counters, out_tokens, host_pos, poisoned, samp, rules};
-        float* x = seq_x + (size_t)s * 4 * H;
-        xa = x; xb = x + H; delta_attn = x + 2 * H; delta_moe = x + 3 * H;
-        counters = seq_counters + 4 * s;
-        out_tokens = seq_tokens + (size_t)s * (c.max_new > 0 ? c.max_new : 1);
-        table = seq_table + (size_t)s * max_splits;
-        host_pos = seqs[s].host_pos; poisoned = seqs[s].poisoned; samp = seqs[s].samp; rules = seqs[s].rules;
-        bound = s;
-    }
-    void unbind() {
-        Seq& q = seqs[bound];
-        q.host_pos = host_pos; q.poisoned = poisoned;
-        xa = dflt.xa; xb = dflt.xb; delta_attn = dflt.da; delta_moe = dflt.dm;
-        counters = dflt.counters; out_tokens = dflt.out_tokens;
-        host_pos = dflt.host_pos; poisoned = dflt.poisoned; samp = dflt.samp; rules = dflt.rules;
-        table = nullptr; bound = -1;
-    }
     // pages covering positions [0, n_tokens) of sequence s; new table entries are uploaded on st.  -1: pool exhausted.
     int ensure_pages(int s, int n_tokens, hipStream_t st) {
         Seq& q = seqs[s];
@@ -440,14 +430,15 @@ struct vh_mixtral {
         if (need > max_splits || (int)free_pages.size() < need - had) return -1;
         for (int j = had; j < need; ++j) { q.pages[j] = free_pages.back(); free_pages.pop_back(); }
         q.npages = need;
-        if (hipMemcpyAsync(seq_table + (size_t)s * max_splits + had, q.pages.data() + had, (size_t)(need - had) * sizeof(int),
+        if (hipMemcpyAsync(slot(s).table + had, q.pages.data() + had, (size_t)(need - had) * sizeof(int),
                            hipMemcpyHostToDevice, st) != hipSuccess) return -2;
         return 0;
     }
     void release(int s) {
         Seq& q = seqs[s];
         for (int j = q.npages - 1; j >= 0; --j) free_pages.push_back(q.pages[j]);
-        q.npages = 0; q.live = false; q.host_pos = 0; q.poisoned = 0; q.samp = VhSampleParams{}; q.rules = Rules{};
+        q.npages = 0; q.live = false;
+        slot(s).fresh();
     }
     void init_seqs() {
         seqs.assign(c.max_seqs > 0 ? c.max_seqs : 0, Seq{});
@@ -459,8 +450,29 @@ struct vh_mixtral {
         segs_host.clear();
         segs_host.reserve(seqs.size() + 1);
     }
+    // the records, from the buffers carve() handed out: the one place that knows how the slots lie in seq_x .. seq_table and the
+    // rules buffers
+    void init_units() {
+        const size_t rows = (size_t)lp_rows(), top = rows * (size_t)c.max_logprobs;
+        units.assign(1 + seqs.size(), Unit{});
+        for (size_t i = 0; i < units.size(); ++i) {
+            Unit& u = units[i];
+            if (i == 0) {
+                u.xa = xa; u.xb = xb; u.da = delta_attn; u.dm = delta_moe;
+                u.counters = counters; u.tokens = out_tokens;
+            } else {
+                const size_t s = i - 1;
+                float* x = seq_x + s * 4 * H;
+                u.xa = x; u.xb = x + H; u.da = x + 2 * H; u.dm = x + 3 * H;
+                u.counters = seq_counters + 4 * s;
+                u.tokens = seq_tokens + s * rows;
+                u.table = seq_table + s * max_splits;
+            }
+            if (seen_tab) u.seen = seen_tab + i * V;
+            if (lp_tok) { u.lp_tok = lp_tok + i * rows; u.lp_top_id = lp_top_id + i * top; u.lp_top = lp_top + i * top; }
+        }
+    }
     int rccl_gen = 0;           // bumped by vh_mixtral_cancel_rccl: a pending vh_mixtral_init_rccl then discards its communicator
-    int poisoned = 0;           // a decode step failed half-way: only prefill / reset may follow
     int* route_dbg = nullptr;   // optional: per-layer top-2 expert ids of the next prefill, [layer][token][2]
     // tensor parallel
     vh_allreduce_fn ar_fn; void* ar_user; void* rccl_comm;
@@ -506,20 +518,20 @@ struct vh_mixtral {
         g_qkv = cv.take<unsigned long long>(nqkv);
         g_attn = cv.take<unsigned long long>(vh_gran_gemv_len(nq * hd));
         // ---- everything whose size follows max_ctx / max_new / logit_rows: behind the fixed part ---------------------------
-        out_tokens = cv.take<int>(c.max_new > 0 ? c.max_new : 1);
+        out_tokens = cv.take<int>(lp_rows());
         part_o = cv.take<float>((size_t)nq * max_splits * hd);
         part_ml = cv.take<float>((size_t)nq * max_splits * 2);
         logits = cv.take<float>((size_t)hist_rows() * V);
+        l_qkv[0] = qkv; l_part_o[0] = part_o; l_part_ml[0] = part_ml; l_attn_out[0] = attn_out; l_attn_cnt[0] = attn_cnt;
+        l_hbuf[0] = hbuf; l_route[0] = route; l_blk_val[0] = blk_val; l_blk_idx[0] = blk_idx; l_cand[0] = cand;
         if (c.max_seqs > 0) {
             const size_t n = (size_t)c.max_seqs;
             seq_x = cv.take<float>(n * 4 * H);
             seq_counters = cv.take<int>(n * 4);
-            seq_tokens = cv.take<int>(n * (c.max_new > 0 ? c.max_new : 1));
+            seq_tokens = cv.take<int>(n * lp_rows());
             seq_table = cv.take<int>(n * max_splits);
             seq_batch = cv.take<int>(n);
             seq_segs = cv.take<VhSeg>(n);   // 24 bytes per slot: the segments of a batched prefill pass
-            l_qkv[0] = qkv; l_part_o[0] = part_o; l_part_ml[0] = part_ml; l_attn_out[0] = attn_out; l_attn_cnt[0] = attn_cnt;
-            l_hbuf[0] = hbuf; l_route[0] = route; l_blk_val[0] = blk_val; l_blk_idx[0] = blk_idx; l_cand[0] = cand;
             for (int b = 1; b < VH_BMAX; ++b) {
                 l_qkv[b] = cv.take<float>(nqkv);
                 l_part_o[b] = cv.take<float>((size_t)nq * max_splits * hd);
@@ -554,6 +566,11 @@ struct vh_mixtral {
     float* py_half(int h) const { return py + (size_t)h * 8 * c.max_prefill * (H / 2); }
     int hist_rows() const { return c.logit_rows > 1 ? c.logit_rows : 1; }
     int cand_world() const { return c.tp_world > 1 ? c.tp_world : 1; }   // slots of the vocab-sharded head's candidate vector (loop-back: this rank's only)
+    // The head's candidates are exchanged: the LM head is a vocab shard of a tensor-parallel rank.  The single-sequence form also
+    // counts a loop-back communicator (one rank playing them all); the batched callers never did.
+    bool head_sharded(bool loopback_counts) const {
+        return c.vocab_n > 0 && (c.tp_world > 1 || (loopback_counts && comm && vh_comm_is_loopback(comm)));
+    }
     void derive() {
         nq = c.n_q_heads; nkv = c.n_kv_heads; hd = c.head_dim; H = c.hidden; I = c.inter; E = c.n_experts;
         V = c.vocab; nqkv = (nq + 2 * nkv) * hd;
@@ -653,7 +670,7 @@ vh_mixtral_t* vh_mixtral_create(const vh_mixtral_cfg* cfg, const vh_mixtral_laye
         return nullptr;
     }
     m->init_seqs();
-    m->seen_dirty.assign(1 + m->seqs.size(), 0);
+    m->init_units();
     hipPointerAttribute_t at{};
     if (hipPointerGetAttributes(&at, workspace) == hipSuccess) m->device = at.device;
     else (void)hipGetLastError();      // a host pointer (argument tests without a GPU): the current device is used
@@ -772,17 +789,15 @@ int vh_mixtral_profile_read(vh_mixtral_t* m, double* total_ms, int* count) {
     return VH_OK;
 }
 
-const int* vh_mixtral_tokens(const vh_mixtral_t* m) { return m ? m->out_tokens : nullptr; }
-const int* vh_mixtral_counters(const vh_mixtral_t* m) { return m ? m->counters : nullptr; }
+const int* vh_mixtral_tokens(const vh_mixtral_t* m) { return m ? m->units[0].tokens : nullptr; }
+const int* vh_mixtral_counters(const vh_mixtral_t* m) { return m ? m->units[0].counters : nullptr; }
 const float* vh_mixtral_logits(const vh_mixtral_t* m) { return m ? m->logits : nullptr; }
 
 int vh_mixtral_reset(vh_mixtral_t* m, void* stream) {
     if (!m) return fail(VH_E_ARG, "null engine");
-    if (hipMemsetAsync(m->counters, 0, 4 * sizeof(int), S(stream)) != hipSuccess)
+    if (hipMemsetAsync(m->units[0].counters, 0, 4 * sizeof(int), S(stream)) != hipSuccess)
         return fail(VH_E_HIP, "reset memset failed");
-    m->host_pos = 0; m->poisoned = 0;
-    m->samp = VhSampleParams{};                  // greedy again (released sequences too)
-    m->rules = vh_mixtral::Rules{};              // and no logit rules
+    m->units[0].fresh();                         // greedy again, no logit rules (released sequences too)
     for (int s = 0; s < (int)m->seqs.size(); ++s)
         if (m->seqs[s].live) m->release(s);      // the pool is one: a reset returns every page
     return VH_OK;
@@ -818,7 +833,7 @@ int vh_mixtral_set_sampling(vh_mixtral_t* m, const vh_sampling* s) {
     VhSampleParams p;
     const int rc = engine_sampling(m, s, &p, "vh_mixtral_set_sampling");
     if (rc != VH_OK) return rc;
-    m->samp = p;
+    m->units[0].samp = p;
     return VH_OK;
 }
 
@@ -843,8 +858,8 @@ static int rules_values(const vh_logit_rules* r, int kmax, vh_mixtral::Rules* ou
     out->r = r->repetition_penalty; out->p = r->presence_penalty; out->f = r->frequency_penalty; out->K = r->logprobs;
     return VH_OK;
 }
-// validate the whole call, then write unit u's table (penalties only) and hand the rules back; nothing changes on a refusal
-static int engine_rules(vh_mixtral* m, int u, const vh_logit_rules* r, const int* ids, int n_prompt, int n_output, vh_mixtral::Rules* out,
+// validate the whole call, then write unit u's table (penalties only) and set its rules; nothing changes on a refusal
+static int engine_rules(vh_mixtral* m, vh_mixtral::Unit& u, const vh_logit_rules* r, const int* ids, int n_prompt, int n_output,
                         const char* what) {
     if (!m->c.penalty_tables && m->c.max_logprobs <= 0)
         return fail(VH_E_ARG, "%s: the engine was created without penalty_tables and max_logprobs", what);
@@ -862,7 +877,7 @@ static int engine_rules(vh_mixtral* m, int u, const vh_logit_rules* r, const int
         if (ids[i] < 0 || ids[i] >= m->V) return fail(VH_E_ARG, "%s: id %d at %ld is outside [0, %d)", what, ids[i], i, m->V);
     // The table is rewritten (penalties) or cleared (it held a history and this request has no penalties).  It may still be read by
     // steps in flight on any stream of the engine's device: wait for that device, then write with blocking calls.
-    if (v.pen() || (m->seen_tab && m->seen_dirty[u])) {
+    if (v.pen() || (u.seen && u.seen_dirty)) {
         std::vector<unsigned> tab;
         if (v.pen()) {
             tab.assign((size_t)m->V, 0u);
@@ -874,23 +889,19 @@ static int engine_rules(vh_mixtral* m, int u, const vh_logit_rules* r, const int
         if (hop && hipSetDevice(m->device) != hipSuccess) return fail(VH_E_HIP, "%s: cannot select device %d", what, m->device);
         const size_t bytes = (size_t)m->V * sizeof(unsigned);
         bool ok = hipDeviceSynchronize() == hipSuccess;
-        ok = ok && (v.pen() ? hipMemcpy(m->seen_of(u), tab.data(), bytes, hipMemcpyHostToDevice) : hipMemset(m->seen_of(u), 0, bytes)) == hipSuccess;
+        ok = ok && (v.pen() ? hipMemcpy(u.seen, tab.data(), bytes, hipMemcpyHostToDevice) : hipMemset(u.seen, 0, bytes)) == hipSuccess;
         ok = ok && hipDeviceSynchronize() == hipSuccess;
         if (hop) (void)hipSetDevice(cur);
         if (!ok) return fail(VH_E_HIP, "%s: token table upload failed", what);
-        m->seen_dirty[u] = v.pen() ? 1 : 0;
+        u.seen_dirty = v.pen();
     }
-    *out = v;
+    u.rules = v;
     return VH_OK;
 }
 
 int vh_mixtral_set_logit_rules(vh_mixtral_t* m, const vh_logit_rules* r, const int* ids, int n_prompt, int n_output) {
     if (!m) return fail(VH_E_ARG, "null engine");
-    vh_mixtral::Rules v;
-    const int rc = engine_rules(m, 0, r, ids, n_prompt, n_output, &v, "vh_mixtral_set_logit_rules");
-    if (rc != VH_OK) return rc;
-    m->rules = v;
-    return VH_OK;
+    return engine_rules(m, m->units[0], r, ids, n_prompt, n_output, "vh_mixtral_set_logit_rules");
 }
 
 int vh_logit_rules_rows(const float* logits, long ld, int rows, int V, const vh_logit_rules* r, const uint32_t* seen, float* penalised_out,
@@ -918,8 +929,6 @@ static int launch_failed(const char* what) {
     if (e != hipSuccess) return fail(VH_E_HIP, "%s: %s", what, hipGetErrorString(e));
     return fail(VH_E_SHAPE, "%s: launch rejected (shape / arguments)", what);
 }
-static int head_and_select(vh_mixtral* m, hipStream_t st, const float* x_in, const float* delta, int mode, int set_pos,
-                           const VhXchg* cx = nullptr);
 #define VH_TRY(expr, what)                             \
     do {                                               \
         if ((expr) != 0) return launch_failed(what);   \
@@ -1014,14 +1023,127 @@ static int moe_down(vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, co
     return VH_OK;
 }
 
-// One pass over the weights for the rows of nseg segments, back to back in embeds.  One segment: the engine's CURRENT sequence (the
-// default state, or the slot the caller bound).  Several: distinct slots (seq), addressed in place — everything row-wise runs on all
-// Sn rows at once; RoPE + KV write and attention take the segment descriptors, the head runs per slot through batched_head.
-struct PfSeg { int seq, len, pos0; };
-static int batched_head(vh_mixtral* m, hipStream_t st, const int* ids, int n, const float* const* x_in, const float* const* delta,
-                        int mode, const int* set_pos, float* logits_out);
+// Vocab-sharded head: this rank's best per-block candidate (value, index; a 4-float key when sampled) goes into its slot of
+// cand, the all-reduce fills the other world - 1 slots, and the world candidates replace the per-block ones for the select
+static int exchange_candidates(vh_mixtral* m, hipStream_t st, float* blk_val, int* blk_idx, float* cand, int world, int keyed) {
+    VH_TRY(vhk_dec_cand(st, blk_val, blk_idx, m->lm_grid, cand, m->c.tp_rank, world, keyed), "candidates");
+    if (m->allreduce(cand, (keyed ? 4L : 2L) * world, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
+    VH_TRY(vhk_dec_cand_unpack(st, cand, world, blk_val, blk_idx, keyed), "candidates");
+    return VH_OK;
+}
+
+// Final norm + LM head + token select for n units, in groups of up to VH_BMAX per pass over the table (a group of two or more: the
+// batched LM-head kernel, one score row per member in samp_rows; a group of one: the single-row kernel on m->logits and lane 0).  Row b
+// is x_in[b] (+ delta[b]; all null or all set), drawn with units[b]'s sampling parameters at its own draw index under its logit rules
+// (penalties off: a null table, the kernels and launches of an engine without rules; on: folded into the head's per-block compare, or
+// applied on load by the filter kernel; the select counts the token into the table); the token, the counters and the next embedding land
+// in the unit.  Vocab-sharded head: every rank scores its rows, the (max, index) candidates travel through the all-reduce hook, every
+// rank takes the same global argmax; kept scores are this rank's slice, zeros elsewhere.
+struct HeadArgs {
+    int mode = 1;                  // 1: a decode step (append, pos++); 0: the end of a prefill (first token, pos = set_pos[b])
+    const int* set_pos = nullptr;  // mode 0: [n]
+    int hist_rows = 1;             // rows of the score history a group of ONE keeps in m->logits (a larger group keeps one row per member)
+    const VhXchg* cx = nullptr;    // fused MoE exchange the single-row LM head sums first (n = 1 only: the batched iteration has none)
+    bool sharded = false;          // the per-block candidates are exchanged (vh_mixtral::head_sharded: the callers differ on loop-back)
+    float* logits_out = nullptr;   // device fp32 [n][vocab], row b = the scores of x_in[b] (copied before the filter kernel's turn)
+};
+static int head(vh_mixtral* m, hipStream_t st, vh_mixtral::Unit* const* units, int n, const float* const* x_in, const float* const* delta,
+                const HeadArgs& a) {
+    const int H = m->H, V = m->V;
+    const float eps = m->c.rms_eps;
+    if (a.logits_out && a.sharded &&
+        (hipMemsetAsync(m->samp_rows, 0, (size_t)VH_BMAX * V * sizeof(float), st) != hipSuccess ||
+         hipMemsetAsync(m->logits, 0, (size_t)V * sizeof(float), st) != hipSuccess))
+        return fail(VH_E_HIP, "memset failed");
+    for (int g0 = 0; g0 < n; g0 += VH_BMAX) {
+        const int gn = n - g0 < VH_BMAX ? n - g0 : VH_BMAX;
+        const bool batched = gn >= 2;
+        const int hist = batched ? 1 : a.hist_rows;
+        VhDecBatchVec hv{};
+        VhDecBatchHead hdp{};
+        VhDecSampleJob sj{};
+        VhDecLogprobJob lj{};
+        VhPenalty pen[VH_BMAX] = {};
+        bool filt[VH_BMAX] = {};
+        float* row[VH_BMAX] = {};     // where member b's scores are kept
+        hv.n = gn;
+        sj.V = V; sj.hist_rows = hist;
+        lj.V = V; lj.hist_rows = hist; lj.kmax = m->c.max_logprobs; lj.max_new = m->lp_rows();
+        for (int b = 0; b < gn; ++b) {
+            const vh_mixtral::Unit& u = *units[g0 + b];
+            row[b] = batched ? m->samp_rows + (size_t)b * V : m->logits;
+            hv.x_in[b] = x_in[g0 + b]; hv.delta[b] = delta[g0 + b];
+            hdp.blk_val[b] = m->l_blk_val[b]; hdp.blk_idx[b] = m->l_blk_idx[b];
+            hdp.ngen[b] = u.counters + 1;
+            pen[b] = u.pen();
+            filt[b] = sampling_filters(u.samp, V);   // top-k / top-p: greedy head, then the filter kernel on the kept row
+            if (!filt[b]) { hdp.sample[b] = u.samp; hdp.pen[b] = pen[b]; }
+            if (batched && (filt[b] || a.logits_out || u.rules.K >= 0)) hdp.logits[b] = row[b];
+            if (u.rules.K >= 0) m->logprob_slot(lj, u, row[b]);
+            if (filt[b]) {
+                const int j = sj.n++;
+                sj.logits[j] = row[b]; sj.ngen[j] = u.counters + 1;
+                sj.blk_val[j] = m->l_blk_val[b]; sj.blk_idx[j] = m->l_blk_idx[b]; sj.sample[j] = u.samp;
+                sj.pen[j] = pen[b];
+            }
+        }
+        if (batched) {   // one pass over the table for the group: 97 us (four activation rows, always) against n x 70
+            VH_TRY(vhk_decb_lmhead(st, hv, m->final_norm, eps, m->lm_head, m->Vn, H, hdp, m->lm_grid, m->v0), "batched lm_head");
+        } else {
+            VH_TRY(vhk_dec_lmhead(st, x_in[g0], delta[g0], m->final_norm, eps, m->lm_head, m->Vn, H, m->logits, m->l_blk_val[0],
+                                  m->l_blk_idx[0], m->lm_grid, hdp.ngen[0], hist, m->v0, V, a.cx, &hdp.sample[0], &hdp.pen[0]), "lm_head");
+        }
+        if (a.logits_out)   // before the filter kernel's turn: it reads the rows, it does not change them
+            for (int b = 0; b < gn; ++b)
+                (void)hipMemcpyAsync(a.logits_out + (size_t)(g0 + b) * V, row[b], (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, st);
+        if (sj.n > 0) VH_TRY(vhk_dec_sample(st, sj), "sample");   // one workgroup per filtered member of the group
+        for (int b = 0; b < gn; ++b) {
+            const vh_mixtral::Unit& u = *units[g0 + b];
+            int nblk = filt[b] ? 1 : m->lm_grid;
+            const int keyed = u.samp.T > 0.0 ? 1 : 0;   // sampled candidates travel as exact keys of their double scores
+            if (a.sharded && !filt[b]) {
+                nblk = m->cand_world();
+                const int rc = exchange_candidates(m, st, m->l_blk_val[b], m->l_blk_idx[b], m->l_cand[b], nblk, keyed);
+                if (rc != VH_OK) return rc;
+            }
+            VH_TRY(vhk_dec_select(st, m->l_blk_val[b], m->l_blk_idx[b], nblk, m->embed, H, V, u.xa, u.counters, u.counters + 1, u.tokens,
+                                  m->c.max_new, a.mode, a.set_pos ? a.set_pos[g0 + b] : 0, keyed, const_cast<unsigned*>(pen[b].seen)), "select");
+        }
+        if (lj.n > 0) VH_TRY(vhk_dec_logprobs(st, lj), "logprobs");   // one workgroup per member of the group that asked for them
+    }
+    return VH_OK;
+}
+// The single-sequence form (a decode step or a one-segment prefill on unit u): n = 1, the engine's score history (logit_rows), the
+// fused exchange of the step, and a loop-back communicator counts as a sharded head
+static int head_one(vh_mixtral* m, hipStream_t st, vh_mixtral::Unit& u, const float* x_in, const float* delta, int mode, int set_pos,
+                    const VhXchg* cx) {
+    vh_mixtral::Unit* up = &u;
+    HeadArgs a;
+    a.mode = mode; a.set_pos = &set_pos; a.hist_rows = m->hist_rows(); a.cx = cx; a.sharded = m->head_sharded(/*loopback_counts=*/true);
+    return head(m, st, &up, 1, &x_in, &delta, a);
+}
+
+// One pass over the weights for the rows of nseg segments, back to back in embeds, each on the unit it names.  One segment: unit 0 (the
+// single-sequence engine, contiguous rows) or a slot.  Several: distinct slots, addressed in place — everything row-wise runs on all
+// Sn rows at once; RoPE + KV write and attention take the segment descriptors, the head runs on the list of units.
+struct PfSeg { int unit, len, pos0; };
+static int prefill_enqueue(vh_mixtral* m, const float* embeds, const PfSeg* sg, int nseg, float* logits_out, float* hidden_dbg,
+                           hipStream_t st);
+// The host mirrors of a prefill move here: a pass that was enqueued whole advances its units; one that was not loses its slots (a
+// slot is then poisoned until freed; unit 0 is not — its next prefill starts over anyway).  A one-segment pass clears the flag of its
+// unit once it is under way (prefill_enqueue).
 static int prefill_impl(vh_mixtral* m, const float* embeds, const PfSeg* sg, int nseg, float* logits_out, float* hidden_dbg,
                         hipStream_t st) {
+    const int rc = prefill_enqueue(m, embeds, sg, nseg, logits_out, hidden_dbg, st);
+    for (int i = 0; i < nseg; ++i) {
+        vh_mixtral::Unit& u = m->units[sg[i].unit];
+        if (rc == VH_OK) u.host_pos = sg[i].pos0 + sg[i].len;
+        else if (sg[i].unit > 0) u.poisoned = 1;
+    }
+    return rc;
+}
+static int prefill_enqueue(vh_mixtral* m, const float* embeds, const PfSeg* sg, int nseg, float* logits_out, float* hidden_dbg,
+                           hipStream_t st) {
     int Sn = 0, kmax = 0;
     for (int i = 0; i < nseg; ++i) {
         if (sg[i].len < 1) return fail(VH_E_SHAPE, "prefill length %d outside [1,%d]", sg[i].len, m->c.max_prefill);
@@ -1032,6 +1154,7 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, const PfSeg* sg, int
     if (Sn < 1 || Sn > m->c.max_prefill) return fail(VH_E_SHAPE, "prefill length %d outside [1,%d]", Sn, m->c.max_prefill);
     const bool multi = nseg > 1;
     const int pos0 = sg[0].pos0;
+    vh_mixtral::Unit& u0 = m->units[sg[0].unit];   // the unit of a one-segment pass
     const int H = m->H, nq = m->nq, nkv = m->nkv, hd = m->hd, KO = nq * hd;
     const bool tp = m->c.tp_world > 1 || vh_tuning()->force_allreduce;
     const float scale = 1.0f / sqrtf((float)hd);
@@ -1039,20 +1162,21 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, const PfSeg* sg, int
     if (hipMemcpyAsync(m->px, embeds, (size_t)Sn * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
         return fail(VH_E_HIP, "prefill: embed copy failed");
     if (multi) {
-        // the descriptors go up once, before layer 0, from storage that outlives the copy; every listed slot starts as the one bound
-        // sequence does below (counters 1-3 zeroed)
+        // the descriptors go up once, before layer 0, from storage that outlives the copy; every listed slot starts as the unit of a
+        // one-segment pass does below (counters 1-3 zeroed)
         m->segs_host.resize(nseg);
         int row0 = 0;
         for (int i = 0; i < nseg; ++i) {
-            m->segs_host[i] = VhSeg{row0, sg[i].len, sg[i].pos0, 0, m->seq_table + (size_t)sg[i].seq * m->max_splits};
+            const vh_mixtral::Unit& u = m->units[sg[i].unit];
+            m->segs_host[i] = VhSeg{row0, sg[i].len, sg[i].pos0, 0, u.table};
             row0 += sg[i].len;
-            if (hipMemsetAsync(m->seq_counters + 4 * sg[i].seq + 1, 0, 3 * sizeof(int), st) != hipSuccess) return fail(VH_E_HIP, "memset failed");
+            if (hipMemsetAsync(u.counters + 1, 0, 3 * sizeof(int), st) != hipSuccess) return fail(VH_E_HIP, "memset failed");
         }
         if (hipMemcpyAsync(m->seq_segs, m->segs_host.data(), (size_t)nseg * sizeof(VhSeg), hipMemcpyHostToDevice, st) != hipSuccess)
             return fail(VH_E_HIP, "prefill: segment descriptor upload failed");
     } else {
-        if (hipMemsetAsync(m->counters + 1, 0, 3 * sizeof(int), st) != hipSuccess) return fail(VH_E_HIP, "memset failed");
-        m->poisoned = 0;
+        if (hipMemsetAsync(u0.counters + 1, 0, 3 * sizeof(int), st) != hipSuccess) return fail(VH_E_HIP, "memset failed");
+        u0.poisoned = 0;
     }
     if (m->c.vocab_n > 0 && m->c.tp_world > 1 &&
         hipMemsetAsync(m->logits, 0, (size_t)m->hist_rows() * m->V * sizeof(float), st) != hipSuccess)
@@ -1110,13 +1234,13 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, const PfSeg* sg, int
             VH_TRY(vhk_gemm_ps(st, g), "qkv gemm");
             if (use_img)   // one-shot prefill under the flash kernel: RoPE + cache write + the K / V tile images in one pass
                 VH_TRY(vhk_rope_kv_img(st, m->py, m->nqkv, m->pq, kc, vc, m->rope_cos, m->rope_sin, Sn, nq, nkv, m->c.max_ctx,
-                                       m->table, m->pnslab + 1, g.c_split_stride, m->kv_img, m->img_tiles), "rope + images");
+                                       u0.table, m->pnslab + 1, g.c_split_stride, m->kv_img, m->img_tiles), "rope + images");
             else if (multi)   // all segments in one launch: row -> (segment, position, page row) from the descriptors
                 VH_TRY(vhk_rope_kv_segs(st, m->py, m->nqkv, m->pq, kc, vc, m->rope_cos, m->rope_sin, Sn, m->seq_segs, nseg, nq, nkv,
                                         m->c.max_ctx, m->pnslab + 1, g.c_split_stride), "rope");
             else
                 VH_TRY(vhk_rope_kv(st, m->py, m->nqkv, m->pq, kc, vc, m->rope_cos, m->rope_sin, Sn, pos0, nq, nkv,
-                                   m->c.max_ctx, m->table, m->pnslab + 1, g.c_split_stride), "rope");
+                                   m->c.max_ctx, u0.table, m->pnslab + 1, g.c_split_stride), "rope");
         } else {
             VH_TRY(vhk_rmsnorm(st, m->px, m->pxn, w.attn_norm, Sn, H, m->c.rms_eps), "rmsnorm");
             VhGemmArgs g{};
@@ -1128,7 +1252,7 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, const PfSeg* sg, int
                                         m->c.max_ctx, nullptr, 0), "rope");
             else
                 VH_TRY(vhk_rope_kv(st, m->pqkv, m->nqkv, m->pq, kc, vc, m->rope_cos, m->rope_sin, Sn, pos0, nq, nkv,
-                                   m->c.max_ctx, m->table, nullptr, 0), "rope");
+                                   m->c.max_ctx, u0.table, nullptr, 0), "rope");
         }
         // ---- attention
         VhAttnArgs a{};
@@ -1138,7 +1262,7 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, const PfSeg* sg, int
         a.O = m->pattn; a.ldo = KO;
         a.B = 1; a.Hq = nq; a.Hkv = nkv; a.Sq = Sn; a.Sk = pos0 + Sn; a.d = hd;
         a.causal = 1; a.q_off = pos0; a.klen = pos0 + Sn; a.chunk = 0; a.left = -1; a.scale = scale;
-        a.ktable = m->table; a.kv_rows = m->c.max_ctx;
+        a.ktable = u0.table; a.kv_rows = m->c.max_ctx;
         if (multi) {   // every segment against its own sequence's pages, one call
             a.segs = m->seq_segs; a.segs_host = m->segs_host.data(); a.nseg = nseg;
             a.Sk = kmax; a.klen = kmax; a.q_off = 0; a.ktable = nullptr;
@@ -1222,17 +1346,19 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, const PfSeg* sg, int
     // vita_mixtral.py:171-172 + HF greedy argmax(logits[:, -1]))
     if (multi) {
         // the first token of every segment: final norm + LM head + select on the segments' last rows, each with its slot's sampling,
-        // counters and next-embedding row (the batched head of a decode iteration; host positions advance in the caller)
-        std::vector<int> ids(nseg), set_pos(nseg);
+        // counters and next-embedding row (the head of a batched decode iteration)
+        std::vector<vh_mixtral::Unit*> us(nseg);
+        std::vector<int> set_pos(nseg);
         std::vector<const float*> xin(nseg), dl(nseg, nullptr);
         for (int i = 0; i < nseg; ++i) {
-            ids[i] = sg[i].seq; set_pos[i] = sg[i].pos0 + sg[i].len;
+            us[i] = &m->units[sg[i].unit]; set_pos[i] = sg[i].pos0 + sg[i].len;
             xin[i] = m->px + (size_t)(m->segs_host[i].row0 + sg[i].len - 1) * H;
         }
-        if ((rc = batched_head(m, st, ids.data(), nseg, xin.data(), dl.data(), /*mode=*/0, set_pos.data(), logits_out)) != VH_OK) return rc;
+        HeadArgs ha;
+        ha.mode = 0; ha.set_pos = set_pos.data(); ha.sharded = m->head_sharded(/*loopback_counts=*/false); ha.logits_out = logits_out;
+        if ((rc = head(m, st, us.data(), nseg, xin.data(), dl.data(), ha)) != VH_OK) return rc;
     } else {
-        if ((rc = head_and_select(m, st, m->px + (size_t)(Sn - 1) * H, nullptr, /*mode=*/0, /*set_pos=*/pos0 + Sn)) != VH_OK) return rc;
-        m->host_pos = pos0 + Sn;
+        if ((rc = head_one(m, st, u0, m->px + (size_t)(Sn - 1) * H, nullptr, /*mode=*/0, /*set_pos=*/pos0 + Sn, nullptr)) != VH_OK) return rc;
         if (logits_out)
             (void)hipMemcpyAsync(logits_out, m->logits, (size_t)m->V * sizeof(float), hipMemcpyDeviceToDevice, st);
     }
@@ -1351,55 +1477,8 @@ int vh_mixtral_prefill(vh_mixtral_t* m, const float* embeds, int Sn, int pos0, f
                        void* stream) {
     if (!m || !embeds) return fail(VH_E_ARG, "vh_mixtral_prefill: null pointer");
     if (m->live_seqs() > 0) return fail(VH_E_ARG, "vh_mixtral_prefill: sequences own pages of the KV pool (free them or reset)");
-    const PfSeg one{-1, Sn, pos0};
+    const PfSeg one{0, Sn, pos0};
     return prefill_impl(m, embeds, &one, 1, logits_out, hidden_dbg, S(stream));
-}
-
-// Vocab-sharded head: this rank's best per-block candidate (value, index; a 4-float key when sampled) goes into its slot of
-// cand, the all-reduce fills the other world - 1 slots, and the world candidates replace the per-block ones for the select
-static int exchange_candidates(vh_mixtral* m, hipStream_t st, float* blk_val, int* blk_idx, float* cand, int world, int keyed) {
-    VH_TRY(vhk_dec_cand(st, blk_val, blk_idx, m->lm_grid, cand, m->c.tp_rank, world, keyed), "candidates");
-    if (m->allreduce(cand, (keyed ? 4L : 2L) * world, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
-    VH_TRY(vhk_dec_cand_unpack(st, cand, world, blk_val, blk_idx, keyed), "candidates");
-    return VH_OK;
-}
-
-// Final norm + LM head + greedy selection.  Vocab-sharded head: every rank scores its rows, the (max, index) candidates
-// travel through the all-reduce hook, every rank takes the same global argmax; when scores are kept (logit_rows > 1)
-// the full row is assembled by an all-reduce of the zero-filled slices.
-static int head_and_select(vh_mixtral* m, hipStream_t st, const float* x_in, const float* delta, int mode, int set_pos,
-                           const VhXchg* cx) {
-    const bool sharded = m->c.vocab_n > 0 && (m->c.tp_world > 1 || (m->comm && vh_comm_is_loopback(m->comm)));
-    const bool filt = sampling_filters(m->samp, m->V);   // top-k / top-p: greedy head, then the filter kernel on the kept row
-    const int keyed = m->samp.T > 0.0 ? 1 : 0;           // sampled candidates travel as exact keys of their double scores
-    // penalties (off: a null table, the kernels and launches of an engine without rules): folded into the head's per-block compare,
-    // or applied on load by the filter kernel; the select counts the token into the table
-    const VhPenalty pen = m->pen_of(m->rules, m->unit());
-    VH_TRY(vhk_dec_lmhead(st, x_in, delta, m->final_norm, m->c.rms_eps, m->lm_head, m->Vn, m->H, m->logits, m->blk_val,
-                          m->blk_idx, m->lm_grid, m->counters + 1, m->hist_rows(), m->v0, m->V, cx, filt ? nullptr : &m->samp,
-                          filt ? nullptr : &pen), "lm_head");
-    int nblk = m->lm_grid;
-    if (filt) {
-        VhDecSampleJob j{};
-        j.n = 1; j.V = m->V; j.hist_rows = m->hist_rows();
-        j.logits[0] = m->logits; j.ngen[0] = m->counters + 1; j.blk_val[0] = m->blk_val; j.blk_idx[0] = m->blk_idx; j.sample[0] = m->samp;
-        j.pen[0] = pen;
-        VH_TRY(vhk_dec_sample(st, j), "sample");
-        nblk = 1;
-    } else if (sharded) {
-        nblk = m->cand_world();
-        const int rc = exchange_candidates(m, st, m->blk_val, m->blk_idx, m->cand, nblk, keyed);
-        if (rc != VH_OK) return rc;
-    }
-    VH_TRY(vhk_dec_select(st, m->blk_val, m->blk_idx, nblk, m->embed, m->H, m->V, m->xa, m->counters, m->counters + 1,
-                          m->out_tokens, m->c.max_new, mode, set_pos, keyed, const_cast<unsigned*>(pen.seen)), "select");
-    if (m->rules.K >= 0) {
-        VhDecLogprobJob lj{};
-        lj.V = m->V; lj.hist_rows = m->hist_rows(); lj.kmax = m->c.max_logprobs; lj.max_new = m->lp_rows();
-        m->logprob_slot(lj, m->unit(), m->rules, m->logits, m->counters + 1, m->out_tokens);
-        VH_TRY(vhk_dec_logprobs(st, lj), "logprobs");
-    }
-    return VH_OK;
 }
 
 int vh_mixtral_decode_schedule(const vh_mixtral_t* m) { return m ? m->schedule_state : -1; }
@@ -1411,8 +1490,22 @@ static bool fused_wanted(const vh_mixtral* m) {
     return vhk_dec_ablk_supported(m->H, m->nq, m->nkv) != 0;
 }
 
-// One decode step (all layers + LM head + token select) enqueued on st.  Returns VH_OK or an error code; the host
-// mirror of the position (host_pos) is advanced by the CALLER only after the step was enqueued without error.
+// gate|up and down GEMVs of one sequence's MoE in layer w, on its bf16 experts or (q8 set) its int8 ones; cx / px: the fused exchange
+// the launch consumes / produces (nullable)
+static int dec_gateup(const vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, const vh_mixtral_experts_i8* q8, const float* x_in,
+                      const float* delta, float* x_out, int* route, float* hbuf, const VhXchg* cx) {
+    return q8 ? vhk_dec_gateup_i8(st, x_in, delta, x_out, w.ffn_norm, m->c.rms_eps, w.wrouter, m->E, q8->w1, q8->s1, q8->w3, q8->s3, m->I,
+                                  m->H, route, hbuf, 0, cx)
+              : vhk_dec_gateup(st, x_in, delta, x_out, w.ffn_norm, m->c.rms_eps, w.wrouter, m->E, w.w1, w.w3, m->I, m->H, route, hbuf, 0, cx);
+}
+static int dec_down(const vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, const vh_mixtral_experts_i8* q8, const float* hbuf,
+                    const int* route, float* out, const VhXchg* px) {
+    return q8 ? vhk_dec_down_i8(st, hbuf, route, q8->w2, q8->s2, m->H, m->I, m->H, out, px)
+              : vhk_dec_down(st, hbuf, route, w.w2, m->H, m->I, out, px);
+}
+
+// One decode step of unit u (all layers + LM head + token select) enqueued on st.  Returns VH_OK or an error code; the host
+// mirrors move in step_unit, only after the step was enqueued without error.
 // Three launches per layer: the attention block (k_dec_ablk: fused QKV -> attention -> O projection; three launches with
 // vh_tune("dec_fused", 0)), gate|up, down.
 // Tensor parallel over the library's IPC transport: the two all-reduces of a layer are either FUSED into the kernels around
@@ -1422,8 +1515,8 @@ static bool fused_wanted(const vh_mixtral* m) {
 // with the expert GEMMs", web_demo/vllm_tools/vllm_file/mixtral.py:405-414,470-476; no launch per exchange) — the form the ranks
 // vote for when each owns its device — or one small all-reduce kernel per exchange (ranks sharing a device: a waiting consumer
 // grid would hold the CUs a peer's producer needs).
-static int decode_one_step(vh_mixtral* m, hipStream_t st) {
-    const int H = m->H, I = m->I, E = m->E, nq = m->nq, nkv = m->nkv, hd = m->hd;
+static int decode_one_step(vh_mixtral* m, vh_mixtral::Unit& u, hipStream_t st) {
+    const int H = m->H, I = m->I, nq = m->nq, nkv = m->nkv, hd = m->hd;
     const float scale = 1.0f / sqrtf((float)hd);
     const float eps = m->c.rms_eps;
     const bool fuse = m->comm != nullptr && m->exchanges() && vh_tuning()->tp_fuse != 0 && (H % 2) == 0 &&
@@ -1436,7 +1529,7 @@ static int decode_one_step(vh_mixtral* m, hipStream_t st) {
     const bool shared_dev = vh_tuning()->comm_ranks_per_device > 1 || (m->comm && vh_comm_ranks_per_device(m->comm) > 1);
     const bool fused_attn = fused_wanted(m) && !shared_dev;
     m->schedule_state = fused_attn ? 1 : 0;
-    int* err = m->counters + 3;
+    int* err = u.counters + 3;
     VhXchg xa{}, xm{};                           // attention / MoE exchange of the current layer
     bool have_xm = false;
     for (int l = 0; l < m->c.n_layers; ++l) {
@@ -1449,78 +1542,66 @@ static int decode_one_step(vh_mixtral* m, hipStream_t st) {
             return fail(VH_E_COMM, "fused exchange failed: %s", vh_comm_last_error());
         if (fused_attn) {
             VhDecAblk a{};
-            a.x_in = m->xa; a.delta = l == 0 ? nullptr : m->delta_moe; a.x_out = m->xb; a.norm_w = w.attn_norm; a.eps = eps;
+            a.x_in = u.xa; a.delta = l == 0 ? nullptr : u.dm; a.x_out = u.xb; a.norm_w = w.attn_norm; a.eps = eps;
             a.Wqkv = w.wqkv; a.nqkv = m->nqkv; a.H = H;
-            a.kcache = kc; a.vcache = vc; a.pos = m->host_pos; a.table = m->table; a.rope_cos = m->rope_cos; a.rope_sin = m->rope_sin;
+            a.kcache = kc; a.vcache = vc; a.pos = u.host_pos; a.table = u.table; a.rope_cos = m->rope_cos; a.rope_sin = m->rope_sin;
             a.part_o = m->part_o; a.part_ml = m->part_ml; a.cnt = m->attn_cnt; a.nq = nq; a.nkv = nkv; a.max_ctx = m->c.max_ctx;
-            a.max_splits = m->max_splits; a.nsplit = (m->host_pos + 1 + 63) / 64; a.scale = scale;
-            a.Wo = w.wo; a.out = m->delta_attn;
+            a.max_splits = m->max_splits; a.nsplit = (u.host_pos + 1 + 63) / 64; a.scale = scale;
+            a.Wo = w.wo; a.out = u.da;
             a.gq = VhGranVec{m->g_qkv, m->next_tag(), err}; a.ga = VhGranVec{m->g_attn, m->next_tag(), err};
             if (have_xm) a.cx = xm;
             if (fuse) a.px = xa;
             VH_TRY(vhk_dec_ablk(st, a), "dec attention block");
         } else {
-            VH_TRY(vhk_dec_qkv(st, m->xa, l == 0 ? nullptr : m->delta_moe, m->xb, w.attn_norm, eps, w.wqkv, m->nqkv, H,
+            VH_TRY(vhk_dec_qkv(st, u.xa, l == 0 ? nullptr : u.dm, u.xb, w.attn_norm, eps, w.wqkv, m->nqkv, H,
                                m->qkv, have_xm ? &xm : nullptr), "dec qkv");
-            VH_TRY(vhk_dec_attn(st, m->qkv, kc, vc, m->counters, m->rope_cos, m->rope_sin, m->part_o, m->part_ml,
-                                m->attn_cnt, m->attn_out, nq, nkv, m->c.max_ctx, m->max_splits, m->host_pos + 1,
-                                scale, m->table), "dec attn");
-            VH_TRY(vhk_dec_oproj(st, m->attn_out, w.wo, H, nq * hd, m->delta_attn, fuse ? &xa : nullptr), "dec oproj");
+            VH_TRY(vhk_dec_attn(st, m->qkv, kc, vc, u.counters, m->rope_cos, m->rope_sin, m->part_o, m->part_ml,
+                                m->attn_cnt, m->attn_out, nq, nkv, m->c.max_ctx, m->max_splits, u.host_pos + 1,
+                                scale, u.table), "dec attn");
+            VH_TRY(vhk_dec_oproj(st, m->attn_out, w.wo, H, nq * hd, u.da, fuse ? &xa : nullptr), "dec oproj");
         }
-        if (!fuse && m->allreduce(m->delta_attn, H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
+        if (!fuse && m->allreduce(u.da, H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
         // the consumer of the MoE exchange is the next layer's attention block (or fused-QKV GEMV), or the LM head after the last layer
         const int xm_blocks = l + 1 < m->c.n_layers ? (fused_attn ? vhk_dec_ablk_qkv_blocks(m->nqkv, H) : vhk_dec_consumer_blocks(0, m->nqkv, H, I))
                                                      : m->lm_grid;
         if (prof) (void)hipEventRecord(m->prof_ev[m->prof_used], st);
-        {
-            if (q8) {
-                VH_TRY(vhk_dec_gateup_i8(st, m->xb, m->delta_attn, m->xa, w.ffn_norm, eps, w.wrouter, E, q8->w1, q8->s1, q8->w3, q8->s3,
-                                         I, H, m->route, m->hbuf, 0, fuse ? &xa : nullptr), "dec gateup");
-            } else {
-                VH_TRY(vhk_dec_gateup(st, m->xb, m->delta_attn, m->xa, w.ffn_norm, eps, w.wrouter, E, w.w1, w.w3, I, H,
-                                      m->route, m->hbuf, 0, fuse ? &xa : nullptr), "dec gateup");
-            }
-            if (prof) { (void)hipEventRecord(m->prof_ev[m->prof_used + 1], st); m->prof_used += 2; }
-            if (fuse) {
-                if (vh_comm_xchg_next(m->comm, H, 1, xm_blocks, &xm, st) != VH_OK) return fail(VH_E_COMM, "fused exchange failed: %s", vh_comm_last_error());
-                have_xm = true;
-            }
-            if (q8) {
-                VH_TRY(vhk_dec_down_i8(st, m->hbuf, m->route, q8->w2, q8->s2, H, I, H, m->delta_moe, fuse ? &xm : nullptr), "dec down");
-            } else {
-                VH_TRY(vhk_dec_down(st, m->hbuf, m->route, w.w2, H, I, m->delta_moe, fuse ? &xm : nullptr), "dec down");
-            }
+        VH_TRY(dec_gateup(m, st, w, q8, u.xb, u.da, u.xa, m->route, m->hbuf, fuse ? &xa : nullptr), "dec gateup");
+        if (prof) { (void)hipEventRecord(m->prof_ev[m->prof_used + 1], st); m->prof_used += 2; }
+        if (fuse) {
+            if (vh_comm_xchg_next(m->comm, H, 1, xm_blocks, &xm, st) != VH_OK) return fail(VH_E_COMM, "fused exchange failed: %s", vh_comm_last_error());
+            have_xm = true;
         }
-        if (!fuse && m->allreduce(m->delta_moe, H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
+        VH_TRY(dec_down(m, st, w, q8, m->hbuf, m->route, u.dm, fuse ? &xm : nullptr), "dec down");
+        if (!fuse && m->allreduce(u.dm, H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
     }
-    {
-        const int rc = head_and_select(m, st, m->xa, m->delta_moe, /*mode=*/1, /*set_pos=*/0, have_xm ? &xm : nullptr);
-        if (rc != VH_OK) return rc;
-    }
-    const hipError_t e = hipGetLastError();   // checked per step: the mirrors below must not run ahead of a failed launch
+    const int rc = head_one(m, st, u, u.xa, u.dm, /*mode=*/1, /*set_pos=*/0, have_xm ? &xm : nullptr);
+    if (rc != VH_OK) return rc;
+    const hipError_t e = hipGetLastError();   // checked per step: the mirrors must not run ahead of a failed launch
     if (e != hipSuccess) return fail(VH_E_HIP, "decode: %s", hipGetErrorString(e));
     return VH_OK;
 }
 
+// The host mirrors of a decode step move here, for the step of one unit and for every member of a batched iteration alike: a step that
+// was enqueued whole advances the position; one that was not poisons its unit and leaves host_pos at the last COMPLETE step (the device
+// state of the partial step is discarded by unit 0's next prefill / reset; a slot is lost until it is freed).
+static int settle_step(vh_mixtral::Unit& u, int rc) {
+    if (rc == VH_OK) u.host_pos += 1;
+    else u.poisoned = 1;
+    return rc;
+}
+static int step_unit(vh_mixtral* m, vh_mixtral::Unit& u, hipStream_t st) { return settle_step(u, decode_one_step(m, u, st)); }
+
 int vh_mixtral_decode(vh_mixtral_t* m, int n_steps, void* stream) {
     if (!m) return fail(VH_E_ARG, "null engine");
-    hipStream_t st = S(stream);
-    if (m->poisoned) return fail(VH_E_ARG, "decode: a previous step failed; prefill or reset first");
+    vh_mixtral::Unit& u = m->units[0];
+    if (u.poisoned) return fail(VH_E_ARG, "decode: a previous step failed; prefill or reset first");
     if (m->live_seqs() > 0) return fail(VH_E_ARG, "vh_mixtral_decode: sequences own pages of the KV pool (use vh_mixtral_seq_decode)");
-    if (n_steps <= 0) return VH_OK;
-    int rc = VH_OK;
     for (int step = 0; step < n_steps; ++step) {
-        if (m->host_pos + 1 >= m->c.max_ctx) { rc = fail(VH_E_SHAPE, "decode: KV cache full (%d)", m->c.max_ctx); break; }
-        rc = decode_one_step(m, st);
-        if (rc != VH_OK) {
-            // the step was not (fully) enqueued: host_pos keeps its value, i.e. it describes the
-            // last COMPLETE step; the device state of the partial step is discarded by the next prefill / reset
-            m->poisoned = 1;
-            break;
-        }
-        m->host_pos += 1;
+        if (u.host_pos + 1 >= m->c.max_ctx) return fail(VH_E_SHAPE, "decode: KV cache full (%d)", m->c.max_ctx);
+        const int rc = step_unit(m, u, S(stream));
+        if (rc != VH_OK) return rc;
     }
-    return rc;
+    return VH_OK;
 }
 
 // ---- concurrent sequences (paged KV cache) ---------------------------------------------------------------------------
@@ -1533,7 +1614,7 @@ static int seq_ok(vh_mixtral* m, int s, const char* what) {
 int vh_mixtral_seq_alloc(vh_mixtral_t* m) {
     if (!m) return fail(VH_E_ARG, "null engine");
     for (int s = 0; s < (int)m->seqs.size(); ++s)
-        if (!m->seqs[s].live) { m->seqs[s].live = true; m->seqs[s].samp = VhSampleParams{}; m->seqs[s].rules = vh_mixtral::Rules{}; return s; }
+        if (!m->seqs[s].live) { m->seqs[s].live = true; m->slot(s).samp = VhSampleParams{}; m->slot(s).rules = vh_mixtral::Rules{}; return s; }
     return fail(VH_E_FULL, "vh_mixtral_seq_alloc: all %d sequence slots are in use", (int)m->seqs.size());
 }
 
@@ -1550,47 +1631,34 @@ int vh_mixtral_seq_set_sampling(vh_mixtral_t* m, int s, const vh_sampling* smp) 
     VhSampleParams p;
     const int rc = engine_sampling(m, smp, &p, "vh_mixtral_seq_set_sampling");
     if (rc != VH_OK) return rc;
-    m->seqs[s].samp = p;
+    m->slot(s).samp = p;
     return VH_OK;
 }
 
 int vh_mixtral_seq_set_logit_rules(vh_mixtral_t* m, int s, const vh_logit_rules* r, const int* ids, int n_prompt, int n_output) {
     const int rc0 = seq_ok(m, s, "vh_mixtral_seq_set_logit_rules");
     if (rc0 != VH_OK) return rc0;
-    vh_mixtral::Rules v;
-    const int rc = engine_rules(m, 1 + s, r, ids, n_prompt, n_output, &v, "vh_mixtral_seq_set_logit_rules");
-    if (rc != VH_OK) return rc;
-    m->seqs[s].rules = v;
-    return VH_OK;
+    return engine_rules(m, m->slot(s), r, ids, n_prompt, n_output, "vh_mixtral_seq_set_logit_rules");
 }
+// accessors: the engine-level ones read unit 0, the per-slot ones the slot's record.  seq_pos / seq_table answer for a LIVE slot only;
+// the buffer getters answer for any slot index (a freed sequence's ids and counters can still be read)
 static bool slot_ok(const vh_mixtral_t* m, int s) { return m && s >= 0 && s < (int)m->seqs.size(); }
-const float* vh_mixtral_logprobs_token(const vh_mixtral_t* m) { return m ? m->lp_tok : nullptr; }
-const int* vh_mixtral_logprobs_top_ids(const vh_mixtral_t* m) { return m ? m->lp_top_id : nullptr; }
-const float* vh_mixtral_logprobs_top(const vh_mixtral_t* m) { return m ? m->lp_top : nullptr; }
-const float* vh_mixtral_seq_logprobs_token(const vh_mixtral_t* m, int s) {
-    return (slot_ok(m, s) && m->lp_tok) ? m->lp_tok + (size_t)(1 + s) * m->lp_rows() : nullptr;
-}
-const int* vh_mixtral_seq_logprobs_top_ids(const vh_mixtral_t* m, int s) {
-    return (slot_ok(m, s) && m->lp_top_id) ? m->lp_top_id + (size_t)(1 + s) * m->lp_rows() * m->c.max_logprobs : nullptr;
-}
-const float* vh_mixtral_seq_logprobs_top(const vh_mixtral_t* m, int s) {
-    return (slot_ok(m, s) && m->lp_top) ? m->lp_top + (size_t)(1 + s) * m->lp_rows() * m->c.max_logprobs : nullptr;
-}
-const uint32_t* vh_mixtral_seen(const vh_mixtral_t* m) { return m ? m->seen_of(0) : nullptr; }
-const uint32_t* vh_mixtral_seq_seen(const vh_mixtral_t* m, int s) { return slot_ok(m, s) ? m->seen_of(1 + s) : nullptr; }
+static bool live_ok(const vh_mixtral_t* m, int s) { return slot_ok(m, s) && m->seqs[s].live; }
+const float* vh_mixtral_logprobs_token(const vh_mixtral_t* m) { return m ? m->units[0].lp_tok : nullptr; }
+const int* vh_mixtral_logprobs_top_ids(const vh_mixtral_t* m) { return m ? m->units[0].lp_top_id : nullptr; }
+const float* vh_mixtral_logprobs_top(const vh_mixtral_t* m) { return m ? m->units[0].lp_top : nullptr; }
+const float* vh_mixtral_seq_logprobs_token(const vh_mixtral_t* m, int s) { return slot_ok(m, s) ? m->slot(s).lp_tok : nullptr; }
+const int* vh_mixtral_seq_logprobs_top_ids(const vh_mixtral_t* m, int s) { return slot_ok(m, s) ? m->slot(s).lp_top_id : nullptr; }
+const float* vh_mixtral_seq_logprobs_top(const vh_mixtral_t* m, int s) { return slot_ok(m, s) ? m->slot(s).lp_top : nullptr; }
+const uint32_t* vh_mixtral_seen(const vh_mixtral_t* m) { return m ? m->units[0].seen : nullptr; }
+const uint32_t* vh_mixtral_seq_seen(const vh_mixtral_t* m, int s) { return slot_ok(m, s) ? m->slot(s).seen : nullptr; }
 
 int vh_mixtral_pages_free(const vh_mixtral_t* m) { return m ? (int)m->free_pages.size() : 0; }
-int vh_mixtral_seq_pos(const vh_mixtral_t* m, int s) {
-    return (m && s >= 0 && s < (int)m->seqs.size() && m->seqs[s].live) ? m->seqs[s].host_pos : -1;
-}
-const int* vh_mixtral_seq_tokens(const vh_mixtral_t* m, int s) {
-    return (m && s >= 0 && s < (int)m->seqs.size()) ? m->seq_tokens + (size_t)s * (m->c.max_new > 0 ? m->c.max_new : 1) : nullptr;
-}
-const int* vh_mixtral_seq_counters(const vh_mixtral_t* m, int s) {
-    return (m && s >= 0 && s < (int)m->seqs.size()) ? m->seq_counters + 4 * s : nullptr;
-}
+int vh_mixtral_seq_pos(const vh_mixtral_t* m, int s) { return live_ok(m, s) ? m->slot(s).host_pos : -1; }
+const int* vh_mixtral_seq_tokens(const vh_mixtral_t* m, int s) { return slot_ok(m, s) ? m->slot(s).tokens : nullptr; }
+const int* vh_mixtral_seq_counters(const vh_mixtral_t* m, int s) { return slot_ok(m, s) ? m->slot(s).counters : nullptr; }
 int vh_mixtral_seq_table(const vh_mixtral_t* m, int s, int* pages_out, int cap) {
-    if (!m || s < 0 || s >= (int)m->seqs.size() || !m->seqs[s].live) return -1;
+    if (!live_ok(m, s)) return -1;
     const vh_mixtral::Seq& q = m->seqs[s];
     for (int j = 0; j < q.npages && j < cap; ++j) pages_out[j] = q.pages[j];
     return q.npages;
@@ -1601,18 +1669,14 @@ int vh_mixtral_seq_prefill(vh_mixtral_t* m, int s, const float* embeds, int Sn, 
     if (rc0 != VH_OK) return rc0;
     if (!embeds) return fail(VH_E_ARG, "vh_mixtral_seq_prefill: null pointer");
     hipStream_t st = S(stream);
-    const int pos0 = m->seqs[s].host_pos;       // appends to the sequence (0 for a new one): chunked prompts, later turns
+    const int pos0 = m->slot(s).host_pos;       // appends to the sequence (0 for a new one): chunked prompts, later turns
     if (Sn < 1 || pos0 + Sn >= m->c.max_ctx) return fail(VH_E_SHAPE, "prefill of %d tokens at %d exceeds the pool", Sn, pos0);
     const int pr = m->ensure_pages(s, pos0 + Sn, st);
     if (pr == -1) return fail(VH_E_FULL, "KV pool exhausted: %d pages free, sequence %d needs %d more", (int)m->free_pages.size(),
                               s, (pos0 + Sn + 63) / 64 - m->seqs[s].npages);
     if (pr != 0) return fail(VH_E_HIP, "page table upload failed");
-    m->bind(s);
-    const PfSeg one{s, Sn, pos0};
-    const int rc = prefill_impl(m, embeds, &one, 1, logits_out, nullptr, st);
-    if (rc != VH_OK) m->poisoned = 1;
-    m->unbind();
-    return rc;
+    const PfSeg one{1 + s, Sn, pos0};
+    return prefill_impl(m, embeds, &one, 1, logits_out, nullptr, st);
 }
 
 int vh_mixtral_seq_prefill_batch(vh_mixtral_t* m, const int* seqs, const int* lens, int n, const float* embeds, float* logits_out,
@@ -1627,14 +1691,15 @@ int vh_mixtral_seq_prefill_batch(vh_mixtral_t* m, const int* seqs, const int* le
         const int rc = seq_ok(m, seqs[i], what);
         if (rc != VH_OK) return rc;
         const vh_mixtral::Seq& q = m->seqs[seqs[i]];
-        if (q.poisoned) return fail(VH_E_ARG, "sequence %d: a previous step failed; free it", seqs[i]);
+        const int pos = m->slot(seqs[i]).host_pos;
+        if (m->slot(seqs[i]).poisoned) return fail(VH_E_ARG, "sequence %d: a previous step failed; free it", seqs[i]);
         for (int j = 0; j < i; ++j)
             if (seqs[j] == seqs[i]) return fail(VH_E_ARG, "%s: sequence %d is listed twice", what, seqs[i]);
         if (lens[i] < 1) return fail(VH_E_SHAPE, "%s: segment %d has %d rows", what, i, lens[i]);
-        if (q.host_pos + (long)lens[i] >= m->c.max_ctx)
-            return fail(VH_E_SHAPE, "prefill of %d tokens at %d exceeds the pool", lens[i], q.host_pos);
+        if (pos + (long)lens[i] >= m->c.max_ctx)
+            return fail(VH_E_SHAPE, "prefill of %d tokens at %d exceeds the pool", lens[i], pos);
         rows += lens[i];
-        const int need = (q.host_pos + lens[i] + 63) / 64;
+        const int need = (pos + lens[i] + 63) / 64;
         if (need > q.npages) pages += need - q.npages;
     }
     if (rows > m->c.max_prefill) return fail(VH_E_SHAPE, "%s: %ld rows exceed max_prefill %d", what, rows, m->c.max_prefill);
@@ -1645,9 +1710,8 @@ int vh_mixtral_seq_prefill_batch(vh_mixtral_t* m, const int* seqs, const int* le
     std::vector<int> had(n);
     for (int i = 0; i < n; ++i) had[i] = m->seqs[seqs[i]].npages;
     for (int i = 0; i < n; ++i) {
-        vh_mixtral::Seq& q = m->seqs[seqs[i]];
-        sg[i] = PfSeg{seqs[i], lens[i], q.host_pos};
-        if (m->ensure_pages(seqs[i], q.host_pos + lens[i], st) != 0) {
+        sg[i] = PfSeg{1 + seqs[i], lens[i], m->slot(seqs[i]).host_pos};
+        if (m->ensure_pages(seqs[i], sg[i].pos0 + lens[i], st) != 0) {
             for (int j = i; j >= 0; --j) {          // pages taken for this call go back, in the order they would be handed out again
                 vh_mixtral::Seq& r = m->seqs[seqs[j]];
                 while (r.npages > had[j]) m->free_pages.push_back(r.pages[--r.npages]);
@@ -1655,89 +1719,7 @@ int vh_mixtral_seq_prefill_batch(vh_mixtral_t* m, const int* seqs, const int* le
             return fail(VH_E_HIP, "page table upload failed");
         }
     }
-    const int rc = prefill_impl(m, embeds, sg.data(), n, logits_out, nullptr, st);
-    for (int i = 0; i < n; ++i) {
-        vh_mixtral::Seq& q = m->seqs[seqs[i]];
-        if (rc != VH_OK) q.poisoned = 1;        // enqueued in part: exactly the listed sequences are lost
-        else q.host_pos += lens[i];
-    }
-    return rc;
-}
-
-// Final norm + LM head + token select for n sequence slots (ids), in groups of up to VH_BMAX per pass over the table: row b is
-// x_in[b] (+ delta[b]; all null or all set), drawn with slot ids[b]'s sampling parameters at its own draw index; the token, the
-// counters and the next embedding land in the slot.  mode 1: a decode step (append, pos++); mode 0: the end of a prefill (first token,
-// pos = set_pos[b]).  logits_out (nullable): device fp32 [n][vocab], row b = the scores of x_in[b] (a vocab-sharded head: this rank's
-// slice, zeros elsewhere).  Shared by decode_iteration and the batched prefill pass.
-static int batched_head(vh_mixtral* m, hipStream_t st, const int* ids, int n, const float* const* x_in, const float* const* delta,
-                        int mode, const int* set_pos, float* logits_out) {
-    const int H = m->H;
-    const float eps = m->c.rms_eps;
-    const bool sharded = m->c.vocab_n > 0 && m->c.tp_world > 1;
-    if (logits_out && sharded &&
-        (hipMemsetAsync(m->samp_rows, 0, (size_t)VH_BMAX * m->V * sizeof(float), st) != hipSuccess ||
-         hipMemsetAsync(m->logits, 0, (size_t)m->V * sizeof(float), st) != hipSuccess))
-        return fail(VH_E_HIP, "memset failed");
-    for (int g0 = 0; g0 < n; g0 += VH_BMAX) {
-        const int gn = n - g0 < VH_BMAX ? n - g0 : VH_BMAX;
-        VhDecBatchVec hv{};
-        VhDecBatchHead hdp{};
-        VhDecSampleJob sj{};
-        VhDecLogprobJob lj{};
-        VhPenalty pen[VH_BMAX] = {};
-        bool filt[VH_BMAX] = {};
-        hv.n = gn;
-        sj.V = m->V; sj.hist_rows = 1;
-        lj.V = m->V; lj.hist_rows = 1; lj.kmax = m->c.max_logprobs; lj.max_new = m->lp_rows();
-        for (int b = 0; b < gn; ++b) {
-            const VhSampleParams& sp = m->seqs[ids[g0 + b]].samp;
-            int* cnt = m->seq_counters + 4 * ids[g0 + b];
-            hv.x_in[b] = x_in[g0 + b]; hv.delta[b] = delta[g0 + b];
-            hdp.blk_val[b] = m->l_blk_val[b]; hdp.blk_idx[b] = m->l_blk_idx[b];
-            hdp.ngen[b] = cnt + 1;
-            const vh_mixtral::Rules& rl = m->seqs[ids[g0 + b]].rules;
-            pen[b] = m->pen_of(rl, 1 + ids[g0 + b]);
-            filt[b] = sampling_filters(sp, m->V);
-            if (!filt[b]) { hdp.sample[b] = sp; hdp.pen[b] = pen[b]; }
-            if (filt[b] || logits_out || rl.K >= 0) hdp.logits[b] = m->samp_rows + (size_t)b * m->V;
-            if (rl.K >= 0)
-                m->logprob_slot(lj, 1 + ids[g0 + b], rl, gn >= 2 ? hdp.logits[b] : m->logits, cnt + 1,
-                                m->seq_tokens + (size_t)ids[g0 + b] * m->lp_rows());
-            if (filt[b]) {
-                const int j = sj.n++;
-                sj.logits[j] = gn >= 2 ? hdp.logits[b] : m->logits; sj.ngen[j] = cnt + 1;
-                sj.blk_val[j] = m->l_blk_val[b]; sj.blk_idx[j] = m->l_blk_idx[b]; sj.sample[j] = sp;
-                sj.pen[j] = pen[b];
-            }
-        }
-        if (gn >= 2) {   // one pass over the table for the group: 97 us (four activation rows, always) against n x 70
-            VH_TRY(vhk_decb_lmhead(st, hv, m->final_norm, eps, m->lm_head, m->Vn, H, hdp, m->lm_grid, m->v0), "batched lm_head");
-        } else {
-            VH_TRY(vhk_dec_lmhead(st, x_in[g0], delta[g0], m->final_norm, eps, m->lm_head, m->Vn, H, m->logits, m->l_blk_val[0],
-                                  m->l_blk_idx[0], m->lm_grid, hdp.ngen[0], 1, m->v0, m->V, nullptr, &hdp.sample[0], &hdp.pen[0]), "lm_head");
-        }
-        if (logits_out)   // before the filter kernel's turn: it reads the rows, it does not change them
-            for (int b = 0; b < gn; ++b)
-                (void)hipMemcpyAsync(logits_out + (size_t)(g0 + b) * m->V, gn >= 2 ? hdp.logits[b] : m->logits, (size_t)m->V * sizeof(float),
-                                     hipMemcpyDeviceToDevice, st);
-        if (sj.n > 0) VH_TRY(vhk_dec_sample(st, sj), "sample");   // one workgroup per filtered sequence of the group
-        for (int b = 0; b < gn; ++b) {
-            const int sb = g0 + b;
-            int* cnt = m->seq_counters + 4 * ids[sb];
-            int nblk = filt[b] ? 1 : m->lm_grid;
-            const int keyed = m->seqs[ids[sb]].samp.T > 0.0 ? 1 : 0;
-            if (sharded && !filt[b]) {
-                nblk = m->c.tp_world;
-                const int rc = exchange_candidates(m, st, m->l_blk_val[b], m->l_blk_idx[b], m->l_cand[b], nblk, keyed);
-                if (rc != VH_OK) return rc;
-            }
-            VH_TRY(vhk_dec_select(st, m->l_blk_val[b], m->l_blk_idx[b], nblk, m->embed, H, m->V, m->seq_x + (size_t)ids[sb] * 4 * H, cnt, cnt + 1,
-                                  m->seq_tokens + (size_t)ids[sb] * (m->c.max_new > 0 ? m->c.max_new : 1), m->c.max_new, mode,
-                                  set_pos ? set_pos[sb] : 0, keyed, const_cast<unsigned*>(pen[b].seen)), "select");
-        }
-        if (lj.n > 0) VH_TRY(vhk_dec_logprobs(st, lj), "logprobs");   // one workgroup per sequence of the group that asked for them
-    }
-    return VH_OK;
+    return prefill_impl(m, embeds, sg.data(), n, logits_out, nullptr, st);   // enqueued in part: exactly the listed sequences are lost
 }
 
 // One decode ITERATION of n concurrent sequences (n <= max_seqs, all distinct).  The attention side (fused QKV GEMV,
@@ -1748,17 +1730,17 @@ static int batched_head(vh_mixtral* m, hipStream_t st, const int* ids, int n, co
 //       (k_gemm_ps cfg 0, <= 64 rows per tile — with its few-row rules: vh_gemm_ps_inl.h K-split estimator, vh_gemm_ps.hip cache hint;
 //       "continuous batching");
 //   otherwise per sequence with the batch-1 GEMV kernels.
-// Sequence state is addressed in place (slots); the MoE delta of a sequence is a row of the shared `ptmp` buffer.
+// Sequence state is addressed in place (the slots' records); under the streaming MoE the delta of a sequence is a row of the shared
+// `ptmp` buffer.
 static int decode_iteration(vh_mixtral* m, hipStream_t st, const int* ids, int n) {
     const int H = m->H, I = m->I, E = m->E, nq = m->nq, nkv = m->nkv, hd = m->hd;
     const float scale = 1.0f / sqrtf((float)hd);
     const float eps = m->c.rms_eps;
     const bool tp = m->c.tp_world > 1 || vh_tuning()->force_allreduce;
-    std::vector<float*> xa(n), xb(n), da(n), dm(n);
-    for (int b = 0; b < n; ++b) {
-        float* x = m->seq_x + (size_t)ids[b] * 4 * H;
-        xa[b] = x; xb[b] = x + H; da[b] = x + 2 * H; dm[b] = x + 3 * H;
-    }
+    std::vector<vh_mixtral::Unit*> us(n);
+    std::vector<const float*> xa(n);
+    std::vector<float*> dm(n);     // MoE delta of sequence b: its own, or its row of ptmp
+    for (int b = 0; b < n; ++b) { us[b] = &m->slot(ids[b]); xa[b] = us[b]->xa; dm[b] = us[b]->dm; }
     const int moe_min = vh_tuning()->batch_moe_min;
     const bool stream_moe = moe_min > 0 && n >= moe_min && n <= m->c.max_prefill && H <= 4096 && (H % 64) == 0 && (I % 64) == 0;
     if (stream_moe) {
@@ -1785,19 +1767,20 @@ static int decode_iteration(vh_mixtral* m, hipStream_t st, const int* ids, int n
             q.n = gn; o.n = gn;
             for (int b = 0; b < gn; ++b) {
                 const int sb = g0 + b;
-                q.x_in[b] = xa[sb]; q.delta[b] = l == 0 ? nullptr : dm[sb]; q.x_out[b] = xb[sb]; q.out[b] = m->l_qkv[b];
-                at.qkv[b] = m->l_qkv[b]; at.pos[b] = m->seqs[ids[sb]].host_pos;
-                at.table[b] = m->seq_table + (size_t)ids[sb] * m->max_splits;
+                const vh_mixtral::Unit& u = *us[sb];
+                q.x_in[b] = u.xa; q.delta[b] = l == 0 ? nullptr : dm[sb]; q.x_out[b] = u.xb; q.out[b] = m->l_qkv[b];
+                at.qkv[b] = m->l_qkv[b]; at.pos[b] = u.host_pos;
+                at.table[b] = u.table;
                 at.part_o[b] = m->l_part_o[b]; at.part_ml[b] = m->l_part_ml[b]; at.cnt[b] = m->l_attn_cnt[b];
                 at.attn_out[b] = m->l_attn_out[b];
-                o.x_in[b] = m->l_attn_out[b]; o.out[b] = da[sb];
+                o.x_in[b] = m->l_attn_out[b]; o.out[b] = u.da;
             }
             VH_TRY(vhk_decb_gemv(st, q, w.attn_norm, eps, w.wqkv, m->nqkv, H, 1), "batched qkv");
             VH_TRY(vhk_decb_attn(st, at, gn, kc, vc, m->rope_cos, m->rope_sin, nq, nkv, m->c.max_ctx, m->max_splits, scale), "batched attn");
             VH_TRY(vhk_decb_gemv(st, o, nullptr, 0.f, w.wo, H, nq * hd, 0), "batched oproj");
         }
         for (int b = 0; b < n; ++b)
-            if (m->allreduce(da[b], H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
+            if (m->allreduce(us[b]->da, H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
         if (stream_moe) {
             // x = xb + delta_attn for every sequence -> rows of px (and each sequence's xa, as the GEMV path's x_out)
             VH_TRY(vhk_gather_rows(st, m->seq_x, m->seq_batch, n, H, m->px), "gather");
@@ -1810,28 +1793,20 @@ static int decode_iteration(vh_mixtral* m, hipStream_t st, const int* ids, int n
             if ((rc = moe_down(m, st, w, moe, n, 0, H, m->ptmp)) != VH_OK) return rc;
             if (tp && m->allreduce(m->ptmp, (long)n * H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
         } else {
-            for (int g0 = 0; g0 < n; g0 += VH_BMAX) {
-                const int gn = n - g0 < VH_BMAX ? n - g0 : VH_BMAX;
-                    for (int b = 0; b < gn; ++b) {
-                        if (q8) {
-                            VH_TRY(vhk_dec_gateup_i8(st, xb[g0 + b], da[g0 + b], xa[g0 + b], w.ffn_norm, eps, w.wrouter, E, q8->w1, q8->s1,
-                                                     q8->w3, q8->s3, I, H, m->l_route[b], m->l_hbuf[b], 0), "dec gateup");
-                            VH_TRY(vhk_dec_down_i8(st, m->l_hbuf[b], m->l_route[b], q8->w2, q8->s2, H, I, H, dm[g0 + b]), "dec down");
-                            continue;
-                        }
-                        VH_TRY(vhk_dec_gateup(st, xb[g0 + b], da[g0 + b], xa[g0 + b], w.ffn_norm, eps, w.wrouter, E, w.w1, w.w3, I, H,
-                                              m->l_route[b], m->l_hbuf[b], 0), "dec gateup");
-                        VH_TRY(vhk_dec_down(st, m->l_hbuf[b], m->l_route[b], w.w2, H, I, dm[g0 + b]), "dec down");
-                    }
+            for (int b = 0; b < n; ++b) {
+                const vh_mixtral::Unit& u = *us[b];
+                const int lane = b % VH_BMAX;   // the scratch lane the sequence had in its attention group
+                VH_TRY(dec_gateup(m, st, w, q8, u.xb, u.da, u.xa, m->l_route[lane], m->l_hbuf[lane], nullptr), "dec gateup");
+                VH_TRY(dec_down(m, st, w, q8, m->l_hbuf[lane], m->l_route[lane], dm[b], nullptr), "dec down");
             }
             for (int b = 0; b < n; ++b)
                 if (m->allreduce(dm[b], H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
         }
     }
-    {
-        const int rc = batched_head(m, st, ids, n, xa.data(), dm.data(), /*mode=*/1, nullptr, nullptr);
-        if (rc != VH_OK) return rc;
-    }
+    HeadArgs ha;   // a decode step: one score row per member, no fused exchange, loop-back does not count as sharded
+    ha.sharded = m->head_sharded(/*loopback_counts=*/false);
+    const int rc = head(m, st, us.data(), n, xa.data(), dm.data(), ha);
+    if (rc != VH_OK) return rc;
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(VH_E_HIP, "batched decode: %s", hipGetErrorString(e));
     return VH_OK;
@@ -1843,7 +1818,7 @@ int vh_mixtral_seq_decode(vh_mixtral_t* m, const int* ids, int n, void* stream) 
     for (int i = 0; i < n; ++i) {               // validate the whole batch before anything is enqueued
         const int rc = seq_ok(m, ids[i], "vh_mixtral_seq_decode");
         if (rc != VH_OK) return rc;
-        const vh_mixtral::Seq& q = m->seqs[ids[i]];
+        const vh_mixtral::Unit& q = m->slot(ids[i]);
         if (q.poisoned) return fail(VH_E_ARG, "sequence %d: a previous step failed; free it", ids[i]);
         if (q.host_pos < 1) return fail(VH_E_ARG, "sequence %d has no prompt yet", ids[i]);
         if (q.host_pos + 1 >= m->c.max_ctx) return fail(VH_E_SHAPE, "sequence %d: context limit %d", ids[i], m->c.max_ctx);
@@ -1856,34 +1831,24 @@ int vh_mixtral_seq_decode(vh_mixtral_t* m, const int* ids, int n, void* stream) 
             for (int j = 0; j < i; ++j) if (ids[i] == ids[j]) { distinct = false; break; }
         if (distinct) {
             for (int i = 0; i < n; ++i) {
-                const int pr = m->ensure_pages(ids[i], m->seqs[ids[i]].host_pos + 1, st);
+                const int pr = m->ensure_pages(ids[i], m->slot(ids[i]).host_pos + 1, st);
                 if (pr == -1) return fail(VH_E_FULL, "KV pool exhausted at sequence %d (nothing of the batch advanced)", ids[i]);
                 if (pr != 0) return fail(VH_E_HIP, "page table upload failed");
             }
             const int rc = decode_iteration(m, st, ids, n);
-            if (rc != VH_OK) {
-                for (int i = 0; i < n; ++i) m->seqs[ids[i]].poisoned = 1;
-                return rc;
-            }
-            for (int i = 0; i < n; ++i) m->seqs[ids[i]].host_pos += 1;
-            return VH_OK;
+            for (int i = 0; i < n; ++i) settle_step(m->slot(ids[i]), rc);   // a failed iteration poisons exactly the listed slots
+            return rc;
         }
     }
-    if (n <= 0) return VH_OK;
-    int rc = VH_OK;
     for (int i = 0; i < n; ++i) {
         const int s = ids[i];
-        const int pr = m->ensure_pages(s, m->seqs[s].host_pos + 1, st);   // the step writes K/V of position host_pos
-        if (pr == -1) { rc = fail(VH_E_FULL, "KV pool exhausted at sequence %d (%d of the batch advanced)", s, i); break; }
-        if (pr != 0) { rc = fail(VH_E_HIP, "page table upload failed"); break; }
-        m->bind(s);
-        rc = decode_one_step(m, st);
-        if (rc != VH_OK) m->poisoned = 1;
-        else m->host_pos += 1;
-        m->unbind();
-        if (rc != VH_OK) break;
+        const int pr = m->ensure_pages(s, m->slot(s).host_pos + 1, st);   // the step writes K/V of position host_pos
+        if (pr == -1) return fail(VH_E_FULL, "KV pool exhausted at sequence %d (%d of the batch advanced)", s, i);
+        if (pr != 0) return fail(VH_E_HIP, "page table upload failed");
+        const int rc = step_unit(m, m->slot(s), st);
+        if (rc != VH_OK) return rc;
     }
-    return rc;
+    return VH_OK;
 }
 
 }  // extern "C"
