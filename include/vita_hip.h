@@ -171,6 +171,18 @@ int vh_layernorm(const float* x, long ldx, float* y, long ldy, const float* w, c
 int vh_rmsnorm(const float* x, float* y, const float* w, int rows, int cols, float eps, void* stream);
 int vh_add(float* x, const float* y, long n, void* stream);
 int vh_cast_bf16_f32(const uint16_t* in, float* out, long n, void* stream);
+/* Content digests of embedded prompt rows, the keys of the serving layer's prefix cache (vLLM: enable_prefix_caching; its block
+ * hashes are over token ids, which do not identify spliced image / audio rows, so here the rows themselves are hashed).
+ * For every COMPLETE block b of 64 rows of x (fp32 [rows][cols], row stride ldx) one 128-bit digest out[b][0..4) over the raw 32-bit
+ * patterns (-0.0 and 0.0 differ, NaN payloads count); a trailing partial block gets nothing, rows < 64 is VH_OK and writes nothing.
+ * With word i = r * cols + c the pattern of x[64 b + r][c] (r < 64), all arithmetic modulo 2^32:
+ *     fmix32(h):  h ^= h >> 16;  h *= 0x85EBCA6B;  h ^= h >> 13;  h *= 0xC2B2AE35;  h ^= h >> 16      (MurmurHash3's finaliser)
+ *     out[b][j] = fmix32( sum_i fmix32( word_i ^ fmix32(4 i + j + 0x9E3779B9) )  +  (j + 1) * 0x9E3779B9 ),   j = 0..3
+ * - a function of the block's words and their positions inside the block only (not of b, ldx or the address); every reduction step
+ * is a wrapping add, so the result does not depend on the grid or on the order of the partial sums.  A block is spread over 32
+ * workgroups which add their partial sums into out (zeroed by this call) with vector integer atomics; a second tiny launch applies
+ * the outer fmix32.  cols <= 2^23.  NOT cryptographic: whoever chooses the rows can construct collisions. */
+int vh_hash_row_blocks(const float* x, long ldx, int rows, int cols, uint32_t* out /* device [rows / 64][4] */, void* stream);
 /* Synthetic bf16 weights from a counter-based generator whose values are exact in bf16 (integers in [-126, 126] x 2^-11,
  * sigma 0.018): element (r, c) of the [rows, cols] view is sample idx0 + r * ld_src + c of stream `seed`, so shards of a
  * logical tensor hold the full tensor's values.  The host twin is oracle/hashfill.c — identical weights on both sides
@@ -345,7 +357,7 @@ int vh_mixtral_decode_schedule(const vh_mixtral_t* m);
 const int* vh_mixtral_tokens(const vh_mixtral_t* m);     /* int[max_new]: generated ids   */
 const int* vh_mixtral_counters(const vh_mixtral_t* m);   /* int[4]: {pos, n_generated, attn hand-off counter, device error flag (0 = ok)} */
 const float* vh_mixtral_logits(const vh_mixtral_t* m);   /* fp32[max(1,logit_rows)][vocab]; row i = scores that produced token i */
-int vh_mixtral_reset(vh_mixtral_t* m, void* stream);     /* n_generated = 0, pos = 0      */
+int vh_mixtral_reset(vh_mixtral_t* m, void* stream);     /* n_generated = 0, pos = 0; frees every sequence and drops every page hold */
 /* ---- concurrent sequences over a paged KV cache: what the reference's serving plugin receives from vLLM as
  * `kv_caches` + `attn_metadata` block tables (web_demo/vllm_tools/vllm_file/mixtral.py:491-501,1130-1186; the engine
  * that schedules them: web_interactive_demo.py:942-996).  The KV pool is cut into 64-token pages; a sequence is a slot
@@ -384,6 +396,33 @@ int vh_mixtral_seq_pos(const vh_mixtral_t* m, int seq);                  /* toke
 const int* vh_mixtral_seq_tokens(const vh_mixtral_t* m, int seq);        /* device int[max_new]  */
 const int* vh_mixtral_seq_counters(const vh_mixtral_t* m, int seq);      /* device int[4], as vh_mixtral_counters */
 int vh_mixtral_seq_table(const vh_mixtral_t* m, int seq, int* pages_out /* host */, int cap);   /* -> number of pages */
+/* ---- shared pages: prefix caching over the block tables (vLLM's enable_prefix_caching; what it replaces is the plugin's use of
+ * vLLM's block tables, web_demo/vllm_tools/vllm_file/mixtral.py:491-501, where a cached block appears in several tables).
+ * Every page has a reference count in host memory: a sequence that has the page in its table counts 1, every HOLD counts 1.  A page
+ * is on the free list exactly when its count is 0, and vh_mixtral_pages_free is the number of such pages.  While none of the entries
+ * below is called, pages are handed out and returned in exactly the order they were before these entries existed.
+ *   INVARIANT: the engine never writes a row of a page whose count is above 1 - adoption starts a sequence on a page boundary, holds
+ * cover only full pages below the owner's position, and a sequence only writes at or above its own position.
+ *   Each entry checks the WHOLE call before it changes anything and answers VH_E_ARG (text in vh_last_error) on a violation.  They are
+ * host calls; tensor-parallel ranks make them with the same arguments.
+ *   seq_hold_prefix  one more hold on each of the first n_pages (>= 1) pages of a live, unpoisoned sequence; their ids go to
+ *                    pages_out.  Requires 64 * n_pages <= vh_mixtral_seq_pos(seq): only pages in which every position is written.
+ *   pages_release    drops one count from each listed page (a page listed k times needs a count >= k).  Pages that reach 0 return to
+ *                    the free list LAST LISTED FIRST, i.e. in the order seq_free returns a table: releasing the list seq_hold_prefix
+ *                    gave, after the sequence was freed, leaves the free list as seq_free alone would have left it.
+ *   seq_adopt        a live sequence at position 0 without pages takes the n (>= 1) listed pages as the first entries of its table, one
+ *                    count each; table and position (64 * n: host mirror and device counters[0]) are uploaded on `stream`.  Every
+ *                    page must have a count >= 1, none listed twice, n <= the table's capacity, 64 * n + 1 < max_ctx.  The next
+ *                    seq_prefill / seq_prefill_batch segment of the sequence appends at 64 * n; work enqueued on `stream` earlier -
+ *                    the prefill that wrote the pages - is ordered before it.
+ *   page_refs        the count, -1 for a bad index.
+ * seq_free drops the sequence's count of each of its pages; vh_mixtral_reset does that for every sequence and ALSO drops every hold
+ * (the pool is one; pages that were only held return highest id first).  vh_mixtral_prefill / vh_mixtral_decode address the pool as
+ * contiguous rows and answer VH_E_ARG while any page has a count > 0. */
+int vh_mixtral_seq_hold_prefix(vh_mixtral_t* m, int seq, int n_pages, int* pages_out /* host */);
+int vh_mixtral_pages_release(vh_mixtral_t* m, const int* pages /* host */, int n);
+int vh_mixtral_seq_adopt(vh_mixtral_t* m, int seq, const int* pages /* host */, int n, void* stream);
+int vh_mixtral_page_refs(const vh_mixtral_t* m, int page);
 
 /* ---- batch-1 decode operators, one entry per kernel group ---------------------------------------------------
  * The steps vh_mixtral_decode chains inside one HF MixtralDecoderLayer (third-party modeling_mixtral.py, reached from

@@ -149,6 +149,7 @@ SIGNATURES = {
     "vh_rmsnorm": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "vh_add": (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
     "vh_cast_bf16_f32": (c_int, [c_void_p, c_void_p, c_long, c_void_p]),
+    "vh_hash_row_blocks": (c_int, [c_void_p, c_long, c_int, c_int, c_void_p, c_void_p]),
     "vh_fill_hash_bf16": (c_int, [c_void_p, c_long, c_long, c_long, c_long, c_long, C.c_uint64, c_void_p]),
     "vh_vit_embed": (c_int, [c_void_p, c_void_p]),
     "vh_vit_patchify": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
@@ -210,6 +211,10 @@ SIGNATURES = {
     "vh_mixtral_seq_tokens": (c_void_p, [c_void_p, c_int]),
     "vh_mixtral_seq_counters": (c_void_p, [c_void_p, c_int]),
     "vh_mixtral_seq_table": (c_int, [c_void_p, c_int, C.POINTER(c_int), c_int]),
+    "vh_mixtral_seq_hold_prefix": (c_int, [c_void_p, c_int, c_int, C.POINTER(c_int)]),
+    "vh_mixtral_pages_release": (c_int, [c_void_p, C.POINTER(c_int), c_int]),
+    "vh_mixtral_seq_adopt": (c_int, [c_void_p, c_int, C.POINTER(c_int), c_int, c_void_p]),
+    "vh_mixtral_page_refs": (c_int, [c_void_p, c_int]),
     "vh_mixtral_set_sampling": (c_int, [c_void_p, C.POINTER(Sampling)]),
     "vh_mixtral_seq_set_sampling": (c_int, [c_void_p, c_int, C.POINTER(Sampling)]),
     "vh_sample_rows": (c_int, [c_void_p, c_long, c_int, c_int, C.POINTER(Sampling), c_void_p, c_void_p]),

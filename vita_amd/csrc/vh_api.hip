@@ -164,6 +164,12 @@ int vh_rmsnorm(const float* x, float* y, const float* w, int rows, int cols, flo
     return check_launch("vh_rmsnorm", vhk_rmsnorm(S(stream), x, y, w, rows, cols, eps));
 }
 int vh_add(float* x, const float* y, long n, void* stream) { return check_launch("vh_add", vhk_add(S(stream), x, y, n)); }
+int vh_hash_row_blocks(const float* x, long ldx, int rows, int cols, uint32_t* out, void* stream) {
+    if (rows < 0 || cols < 1 || ldx < cols) return fail(VH_E_ARG, "vh_hash_row_blocks: rows %d, cols %d, ldx %ld", rows, cols, ldx);
+    if (rows < 64) return VH_OK;                 // no complete block: nothing is written
+    if (!x || !out) return fail(VH_E_ARG, "vh_hash_row_blocks: null pointer");
+    return check_launch("vh_hash_row_blocks", vhk_hash_row_blocks(S(stream), x, ldx, rows, cols, out));
+}
 int vh_cast_bf16_f32(const uint16_t* in, float* out, long n, void* stream) {
     return check_launch("vh_cast_bf16_f32", vhk_cast_bf16_f32(S(stream), in, out, n));
 }
@@ -399,6 +405,15 @@ struct vh_mixtral {
     };
     std::vector<Seq> seqs;
     std::vector<int> free_pages;
+    // Reference counts of the pages (host memory): a sequence that has the page in its table counts 1, every hold
+    // (vh_mixtral_seq_hold_prefix) counts 1; a page is on the free list exactly when its count is 0.
+    // INVARIANT: the engine never writes a row of a page whose count is above 1.  It holds because (1) vh_mixtral_seq_adopt starts a
+    // sequence on a page boundary, behind the pages it shares; (2) a hold covers only full pages below its owner's position; (3) a
+    // sequence writes K/V only at or above its own position (prefill appends at host_pos, a decode step writes row host_pos).
+    std::vector<int> page_refs;
+    int take_page() { const int pg = free_pages.back(); free_pages.pop_back(); page_refs[pg] = 1; return pg; }
+    void unref_page(int pg) { if (--page_refs[pg] == 0) free_pages.push_back(pg); }
+    bool pages_in_use() const { return (int)free_pages.size() < n_pages(); }
     std::vector<int> batch_ids_host;   // slot list last uploaded to seq_batch (storage reserved once)
     std::vector<VhSeg> segs_host;      // segment descriptors of the current batched prefill pass (storage reserved once: uploads read from it)
     VhSeg* seq_segs = nullptr;         // [max_seqs] the same on the device
@@ -428,7 +443,7 @@ struct vh_mixtral {
         const int need = (n_tokens + 63) / 64, had = q.npages;
         if (need <= had) return 0;
         if (need > max_splits || (int)free_pages.size() < need - had) return -1;
-        for (int j = had; j < need; ++j) { q.pages[j] = free_pages.back(); free_pages.pop_back(); }
+        for (int j = had; j < need; ++j) q.pages[j] = take_page();
         q.npages = need;
         if (hipMemcpyAsync(slot(s).table + had, q.pages.data() + had, (size_t)(need - had) * sizeof(int),
                            hipMemcpyHostToDevice, st) != hipSuccess) return -2;
@@ -436,7 +451,7 @@ struct vh_mixtral {
     }
     void release(int s) {
         Seq& q = seqs[s];
-        for (int j = q.npages - 1; j >= 0; --j) free_pages.push_back(q.pages[j]);
+        for (int j = q.npages - 1; j >= 0; --j) unref_page(q.pages[j]);
         q.npages = 0; q.live = false;
         slot(s).fresh();
     }
@@ -445,6 +460,7 @@ struct vh_mixtral {
         for (Seq& q : seqs) q.pages.assign(max_splits, 0);
         free_pages.clear();
         for (int pg = n_pages() - 1; pg >= 0; --pg) free_pages.push_back(pg);   // page 0 is handed out first
+        page_refs.assign(n_pages() > 0 ? n_pages() : 0, 0);
         batch_ids_host.clear();
         batch_ids_host.reserve(seqs.size() + 1);
         segs_host.clear();
@@ -800,6 +816,9 @@ int vh_mixtral_reset(vh_mixtral_t* m, void* stream) {
     m->units[0].fresh();                         // greedy again, no logit rules (released sequences too)
     for (int s = 0; s < (int)m->seqs.size(); ++s)
         if (m->seqs[s].live) m->release(s);      // the pool is one: a reset returns every page
+    if (m->pages_in_use())                       // ... the held ones too (vh_mixtral_seq_hold_prefix): highest id first, so the lowest is
+        for (int pg = m->n_pages() - 1; pg >= 0; --pg)   // handed out first among them
+            if (m->page_refs[pg] > 0) { m->page_refs[pg] = 0; m->free_pages.push_back(pg); }
     return VH_OK;
 }
 
@@ -1477,6 +1496,9 @@ int vh_mixtral_prefill(vh_mixtral_t* m, const float* embeds, int Sn, int pos0, f
                        void* stream) {
     if (!m || !embeds) return fail(VH_E_ARG, "vh_mixtral_prefill: null pointer");
     if (m->live_seqs() > 0) return fail(VH_E_ARG, "vh_mixtral_prefill: sequences own pages of the KV pool (free them or reset)");
+    if (m->pages_in_use())
+        return fail(VH_E_ARG, "%s: pages of the KV pool are held (vh_mixtral_seq_hold_prefix; serving: the prefix cache): release them "
+                              "(vh_mixtral_pages_release / reset_prefix_cache) or reset", "vh_mixtral_prefill");
     const PfSeg one{0, Sn, pos0};
     return prefill_impl(m, embeds, &one, 1, logits_out, hidden_dbg, S(stream));
 }
@@ -1596,6 +1618,9 @@ int vh_mixtral_decode(vh_mixtral_t* m, int n_steps, void* stream) {
     vh_mixtral::Unit& u = m->units[0];
     if (u.poisoned) return fail(VH_E_ARG, "decode: a previous step failed; prefill or reset first");
     if (m->live_seqs() > 0) return fail(VH_E_ARG, "vh_mixtral_decode: sequences own pages of the KV pool (use vh_mixtral_seq_decode)");
+    if (m->pages_in_use())
+        return fail(VH_E_ARG, "%s: pages of the KV pool are held (vh_mixtral_seq_hold_prefix; serving: the prefix cache): release them "
+                              "(vh_mixtral_pages_release / reset_prefix_cache) or reset", "vh_mixtral_decode");
     for (int step = 0; step < n_steps; ++step) {
         if (u.host_pos + 1 >= m->c.max_ctx) return fail(VH_E_SHAPE, "decode: KV cache full (%d)", m->c.max_ctx);
         const int rc = step_unit(m, u, S(stream));
@@ -1664,6 +1689,71 @@ int vh_mixtral_seq_table(const vh_mixtral_t* m, int s, int* pages_out, int cap) 
     return q.npages;
 }
 
+// ---- shared pages (prefix caching): holds, release, adoption.  Host calls; each checks the WHOLE call before it changes anything.
+int vh_mixtral_page_refs(const vh_mixtral_t* m, int page) {
+    return m && page >= 0 && page < (int)m->page_refs.size() ? m->page_refs[page] : -1;
+}
+
+int vh_mixtral_seq_hold_prefix(vh_mixtral_t* m, int s, int n_pages, int* pages_out) {
+    const char* what = "vh_mixtral_seq_hold_prefix";
+    const int rc = seq_ok(m, s, what);
+    if (rc != VH_OK) return rc;
+    if (!pages_out) return fail(VH_E_ARG, "%s: null pointer", what);
+    if (m->slot(s).poisoned) return fail(VH_E_ARG, "sequence %d: a previous step failed; free it", s);
+    if (n_pages < 1 || 64L * n_pages > m->slot(s).host_pos)
+        return fail(VH_E_ARG, "%s: %d pages are not all below position %d of sequence %d (only full pages can be held)", what, n_pages,
+                    m->slot(s).host_pos, s);
+    const vh_mixtral::Seq& q = m->seqs[s];
+    for (int j = 0; j < n_pages; ++j) { m->page_refs[q.pages[j]] += 1; pages_out[j] = q.pages[j]; }
+    return VH_OK;
+}
+
+int vh_mixtral_pages_release(vh_mixtral_t* m, const int* pages, int n) {
+    const char* what = "vh_mixtral_pages_release";
+    if (!m || (!pages && n > 0)) return fail(VH_E_ARG, "%s: null pointer", what);
+    if (n < 0) return fail(VH_E_ARG, "%s: n = %d", what, n);
+    std::vector<int> drop(m->page_refs.size(), 0);
+    for (int i = 0; i < n; ++i) {
+        const int pg = pages[i];
+        if (pg < 0 || pg >= (int)drop.size()) return fail(VH_E_ARG, "%s: page %d outside [0,%d)", what, pg, (int)drop.size());
+        if (++drop[pg] > m->page_refs[pg])
+            return fail(VH_E_ARG, "%s: page %d is listed %d times and has %d references", what, pg, drop[pg], m->page_refs[pg]);
+    }
+    for (int i = n - 1; i >= 0; --i) m->unref_page(pages[i]);   // last listed first: as seq_free returns a table
+    return VH_OK;
+}
+
+int vh_mixtral_seq_adopt(vh_mixtral_t* m, int s, const int* pages, int n, void* stream) {
+    const char* what = "vh_mixtral_seq_adopt";
+    const int rc = seq_ok(m, s, what);
+    if (rc != VH_OK) return rc;
+    if (!pages) return fail(VH_E_ARG, "%s: null pointer", what);
+    vh_mixtral::Seq& q = m->seqs[s];
+    vh_mixtral::Unit& u = m->slot(s);
+    if (u.poisoned) return fail(VH_E_ARG, "sequence %d: a previous step failed; free it", s);
+    if (u.host_pos != 0 || q.npages != 0)
+        return fail(VH_E_ARG, "%s: sequence %d is at position %d with %d pages (only a new sequence adopts)", what, s, u.host_pos, q.npages);
+    if (n < 1 || n > m->max_splits || 64L * n + 1 >= m->c.max_ctx)
+        return fail(VH_E_ARG, "%s: %d pages outside [1,%d] or no room for a token behind them (pool %d tokens)", what, n, m->max_splits,
+                    m->c.max_ctx);
+    for (int i = 0; i < n; ++i) {
+        const int pg = pages[i];
+        if (pg < 0 || pg >= (int)m->page_refs.size() || m->page_refs[pg] < 1)
+            return fail(VH_E_ARG, "%s: page %d is free or out of range", what, pg);
+        for (int j = 0; j < i; ++j)
+            if (pages[j] == pg) return fail(VH_E_ARG, "%s: page %d is listed twice", what, pg);
+    }
+    hipStream_t st = S(stream);
+    for (int i = 0; i < n; ++i) q.pages[i] = pages[i];          // the upload reads the mirror (entries above npages are unused)
+    if (hipMemcpyAsync(u.table, q.pages.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(u.counters), 64 * n, 1, st) != hipSuccess)
+        return fail(VH_E_HIP, "%s: table / position upload failed", what);
+    for (int i = 0; i < n; ++i) m->page_refs[pages[i]] += 1;
+    q.npages = n;
+    u.host_pos = 64 * n;
+    return VH_OK;
+}
+
 int vh_mixtral_seq_prefill(vh_mixtral_t* m, int s, const float* embeds, int Sn, float* logits_out, void* stream) {
     const int rc0 = seq_ok(m, s, "vh_mixtral_seq_prefill");
     if (rc0 != VH_OK) return rc0;
@@ -1714,7 +1804,7 @@ int vh_mixtral_seq_prefill_batch(vh_mixtral_t* m, const int* seqs, const int* le
         if (m->ensure_pages(seqs[i], sg[i].pos0 + lens[i], st) != 0) {
             for (int j = i; j >= 0; --j) {          // pages taken for this call go back, in the order they would be handed out again
                 vh_mixtral::Seq& r = m->seqs[seqs[j]];
-                while (r.npages > had[j]) m->free_pages.push_back(r.pages[--r.npages]);
+                while (r.npages > had[j]) m->unref_page(r.pages[--r.npages]);
             }
             return fail(VH_E_HIP, "page table upload failed");
         }

@@ -198,6 +198,57 @@ __global__ void k_add(float* __restrict__ x, const float* __restrict__ y, long n
 
 // x[r, :] += [a[r, :] | b[r, :]]  (a, b: the two column halves [rows][cols/2] of the overlapped TP prefill)
 
+// ---- content digests of 64-row blocks (vh_hash_row_blocks, include/vita_hip.h): lane j of block b is
+// fmix32(sum_i fmix32(word_i ^ fmix32(4 i + j + GOLD)) + (j + 1) GOLD), i = position of the word inside the block.  Every reduction
+// step is a wrapping add, so neither the split of a block over workgroups nor the order of the atomics shows in the result.
+__device__ __forceinline__ uint32_t fmix32(uint32_t h) {   // MurmurHash3's 32-bit finaliser (a bijection)
+    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
+    return h;
+}
+constexpr uint32_t HASH_GOLD = 0x9E3779B9u;
+constexpr int HASH_ROWS_PER_WG = 2;   // 32 workgroups per 64-row block: S = 2344 (36 blocks) puts 1152 workgroups on 256 CUs
+__device__ __forceinline__ void hash_word(uint32_t w, uint32_t i, uint32_t (&acc)[4]) {
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) acc[j] += fmix32(w ^ fmix32(4u * i + j + HASH_GOLD));
+}
+// grid (64 / HASH_ROWS_PER_WG, blocks); VEC: rows are 16-byte aligned and cols % 4 == 0 (one 16-byte load per four words)
+template <bool VEC>
+__global__ void __launch_bounds__(256) k_hash_row_blocks(const float* __restrict__ x, long ldx, int cols, uint32_t* __restrict__ out) {
+    const int blk = blockIdx.y, r0 = blockIdx.x * HASH_ROWS_PER_WG;
+    const float* base = x + ((long)blk * 64 + r0) * ldx;
+    uint32_t acc[4] = {0u, 0u, 0u, 0u};
+    if (VEC) {
+        const int c4n = cols / 4;
+        for (int t = threadIdx.x; t < HASH_ROWS_PER_WG * c4n; t += 256) {
+            const int r = t / c4n, c = (t - r * c4n) * 4;
+            const uint4 v = *reinterpret_cast<const uint4*>(base + (long)r * ldx + c);
+            const uint32_t i = (uint32_t)(r0 + r) * (uint32_t)cols + (uint32_t)c;
+            hash_word(v.x, i, acc); hash_word(v.y, i + 1, acc); hash_word(v.z, i + 2, acc); hash_word(v.w, i + 3, acc);
+        }
+    } else {
+        for (int t = threadIdx.x; t < HASH_ROWS_PER_WG * cols; t += 256) {
+            const int r = t / cols, c = t - r * cols;
+            hash_word(__float_as_uint(base[(long)r * ldx + c]), (uint32_t)(r0 + r) * (uint32_t)cols + (uint32_t)c, acc);
+        }
+    }
+    // wave sums, then the workgroup's four lane sums through LDS: one 16-byte group of atomics per workgroup
+    __shared__ uint32_t part[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        uint32_t v = acc[j];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_down((int)v, off, 64);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][j] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4)
+        atomicAdd(out + (long)blk * 4 + threadIdx.x, part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x]);
+}
+__global__ void k_hash_finish(uint32_t* __restrict__ out, int n) {   // n = 4 * blocks
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n) out[t] = fmix32(out[t] + (uint32_t)((t & 3) + 1) * HASH_GOLD);
+}
+
 // dst (+)= sum of the K-split partial slabs of a projection (slab k at src + k * stride; count read on the device)
 __global__ void k_sum_slabs(float* __restrict__ dst, long ldd, const float* __restrict__ src, long lds, int rows, int cols4,
                             const int* __restrict__ nslab_dev, int nslab, long stride, int accumulate) {
@@ -703,6 +754,19 @@ int vhk_add_halves(hipStream_t st, float* x, const float* a, const float* b, int
     if (cols % 8 != 0) return -1;
     if (rows == 0) return 0;
     hipLaunchKernelGGL(k_add_halves, dim3(grid_for((long)rows * (cols / 4), 256)), dim3(256), 0, st, x, a, b, rows, cols / 4);
+    return 0;
+}
+int vhk_hash_row_blocks(hipStream_t st, const float* x, long ldx, int rows, int cols, uint32_t* out) {
+    // word positions are 32-bit: 4 * (64 * cols) + 3 must not wrap
+    if (rows < 0 || cols < 1 || cols > (1 << 23) || ldx < cols) return -1;
+    const int nblk = rows / 64;
+    if (nblk == 0) return 0;
+    if (hipMemsetAsync(out, 0, (size_t)nblk * 4 * sizeof(uint32_t), st) != hipSuccess) return -3;
+    const bool vec = (cols % 4) == 0 && (ldx % 4) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+    const dim3 grid(64 / HASH_ROWS_PER_WG, nblk);
+    if (vec) hipLaunchKernelGGL(k_hash_row_blocks<true>, grid, dim3(256), 0, st, x, ldx, cols, out);
+    else hipLaunchKernelGGL(k_hash_row_blocks<false>, grid, dim3(256), 0, st, x, ldx, cols, out);
+    hipLaunchKernelGGL(k_hash_finish, dim3((nblk * 4 + 255) / 256), dim3(256), 0, st, out, nblk * 4);
     return 0;
 }
 int vhk_quant_rows_i8(hipStream_t st, const uint16_t* w, long rows, int cols, long ld_src, int col0, int ncols, int8_t* q,

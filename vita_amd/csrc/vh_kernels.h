@@ -309,6 +309,8 @@ int vhk_layernorm(hipStream_t st, const float* x, long ldx, float* y, long ldy, 
 int vhk_rmsnorm(hipStream_t st, const float* x, float* y, const float* w, int rows, int cols, float eps);
 int vhk_add(hipStream_t st, float* x, const float* y, long n);
 int vhk_add_halves(hipStream_t st, float* x, const float* a, const float* b, int rows, int cols);
+// content digests of the complete 64-row blocks of x (vh_hash_row_blocks): memset of out + two launches; -1 bad shape, -3 memset failed
+int vhk_hash_row_blocks(hipStream_t st, const float* x, long ldx, int rows, int cols, uint32_t* out);
 int vhk_vit_patchify(hipStream_t st, const float* pix, float* out, int n, int img, int patch, int kpad);
 int vhk_vit_assemble(hipStream_t st, const float* patches, const uint16_t* cls, const uint16_t* pos, float* x, int n,
                      int ntok, int hid);

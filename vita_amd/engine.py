@@ -370,6 +370,29 @@ class MixtralEngine:
     def pages_free(self):
         return self.lib.vh_mixtral_pages_free(self.h)
 
+    # ---- shared pages (prefix caching): host-side reference counts, include/vita_hip.h "shared pages" --------------------
+    def seq_hold_prefix(self, s, n_pages):
+        """one more hold on each of the first n_pages pages of sequence s (all below its position) -> their page ids.  A held page
+        survives seq_free; give it back with pages_release."""
+        buf = (C.c_int * max(int(n_pages), 1))()
+        check(self.lib.vh_mixtral_seq_hold_prefix(self.h, int(s), int(n_pages), buf), "vh_mixtral_seq_hold_prefix")
+        return list(buf[:int(n_pages)])
+
+    def pages_release(self, pages):
+        """drop one reference from each listed page; pages that reach zero return to the pool."""
+        arr = (C.c_int * max(len(pages), 1))(*[int(x) for x in pages])
+        check(self.lib.vh_mixtral_pages_release(self.h, arr, len(pages)), "vh_mixtral_pages_release")
+
+    def seq_adopt(self, s, pages):
+        """the new sequence s takes the listed (held or owned) pages as the head of its table and starts at position 64 * len(pages):
+        its next seq_prefill / seq_prefill_batch segment appends there."""
+        arr = (C.c_int * max(len(pages), 1))(*[int(x) for x in pages])
+        check(self.lib.vh_mixtral_seq_adopt(self.h, int(s), arr, len(pages), self._stream()), "vh_mixtral_seq_adopt")
+
+    def page_refs(self, page):
+        """reference count of a page (sequences that have it in their table + holds), -1 for a bad index."""
+        return self.lib.vh_mixtral_page_refs(self.h, int(page))
+
     def generated(self):
         """(synchronising) list of token ids generated so far."""
         c = self.check_device_flag()

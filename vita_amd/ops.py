@@ -236,6 +236,22 @@ def rmsnorm(x, w, eps, out=None):
     return out
 
 
+def hash_row_blocks(x, out=None):
+    """128-bit content digests of the complete 64-row blocks of x fp32 [rows, cols] (rows may be strided) -> uint32 words as int32
+    [rows // 64, 4] on the device (vh_hash_row_blocks; the definition is in include/vita_hip.h).  Enqueued on the current stream."""
+    _dev(x)
+    _f32(_c(x, "x"), "x")
+    if x.ndim != 2:
+        raise ValueError("hash_row_blocks takes a [rows, cols] tensor")
+    rows, cols = x.shape
+    if out is None:
+        out = torch.empty((rows // 64, 4), dtype=torch.int32, device=x.device)
+    elif out.dtype != torch.int32 or not out.is_contiguous() or out.numel() < (rows // 64) * 4:
+        raise ValueError("out must be a contiguous int32 tensor of at least [rows // 64, 4]")
+    check(_lib.load().vh_hash_row_blocks(_p(x), x.stride(0) if rows > 1 else cols, rows, cols, _p(out), _stream()), "vh_hash_row_blocks")
+    return out
+
+
 def vit_patchify(pix, patch, kpad):
     _dev(pix)
     pix = _dense(pix)

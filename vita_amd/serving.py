@@ -26,6 +26,7 @@ every running sequence per iteration, free on finish, preempt-by-recompute when 
 (the offline demo) keeps serving one request at a time on the same engine."""
 import asyncio
 import collections
+import hashlib
 import json
 import os
 import threading
@@ -109,6 +110,7 @@ class RequestOutput:
     outputs: List[CompletionOutput] = field(default_factory=list)
     finished: bool = True
     metrics: dict = field(default_factory=dict)
+    num_cached_tokens: int = 0                      # prompt tokens whose K/V came from the prefix cache (vLLM's name; 0 without it)
 
 
 def audio_feature_size(n_frames: int) -> int:
@@ -173,8 +175,13 @@ def completion(index, text, token_ids, reason, logprobs=None):
 class LLM:
     def __init__(self, model, dtype=None, tensor_parallel_size=1, trust_remote_code=True, gpu_memory_utilization=None,
                  disable_custom_all_reduce=True, limit_mm_per_prompt=None, max_new_tokens=1024, device="cuda",
-                 max_num_seqs=0, kv_pool_tokens=None, quantization=None, max_logprobs=0, penalty_tables=None, **_):
+                 max_num_seqs=0, kv_pool_tokens=None, quantization=None, max_logprobs=0, penalty_tables=None,
+                 enable_prefix_caching=False, **_):
         from .model.builder import load_pretrained_model
+        # vLLM's switch: AsyncLLMEngine's batcher then keeps finished prompts' KV pages under content keys (PrefixCache).  generate()
+        # here serves one request at a time on the contiguous pool and does not use the cache; the engine refuses it while the cache
+        # holds pages (its error names reset_prefix_cache)
+        self.enable_prefix_caching = bool(enable_prefix_caching)
         # vLLM's quantization="experts_int8": the MoE experts as int8 with per-output-row scales
         if quantization not in (None, "experts_int8"):
             raise ValueError(f"quantization={quantization!r}: vita_amd supports None and 'experts_int8'")
@@ -373,6 +380,115 @@ class LLM:
         return [self._one(p, sp) for p in batch]
 
 
+# ---- prefix caching: KV pages of earlier prompts, found again by content -----------------------------------------------------
+PREFIX_ROOT_KEY = hashlib.blake2b(b"vita_amd prefix cache v1", digest_size=16).digest()      # key_{-1} of every chain
+
+
+def chain_keys(digests, cols, parent=PREFIX_ROOT_KEY):
+    """digests: the 16-byte content digests of consecutive 64-row blocks (vh_hash_row_blocks) -> their chain keys
+    key_b = blake2b(key_{b-1} || digest_b || cols as 8 little-endian bytes, digest_size=16): a key names the WHOLE prefix up to and
+    including its block, for rows of that width."""
+    keys, tail = [], int(cols).to_bytes(8, "little")
+    for d in digests:
+        parent = hashlib.blake2b(parent + bytes(d) + tail, digest_size=16).digest()
+        keys.append(parent)
+    return keys
+
+
+def device_digests(rows):
+    """fp32 [n, H] device rows -> the digests of its complete 64-row blocks as 16-byte strings: ONE vh_hash_row_blocks launch and one
+    small device-to-host copy, which waits for the stream — the only synchronisation prefix caching adds."""
+    from . import ops
+    if int(rows.shape[0]) < 64:
+        return []
+    words = ops.hash_row_blocks(rows).cpu().numpy()
+    return [words[b].tobytes() for b in range(words.shape[0])]
+
+
+class PrefixCache:
+    """Store of the prefix cache (vLLM's enable_prefix_caching over this engine's pages): chain key -> [page, parent key, children,
+    last-use tick].  Every entry owns ONE hold of its page (MixtralEngine.seq_hold_prefix), so the page outlives the sequence that
+    wrote it; a sequence that adopts it (seq_adopt) adds its own count.  The entries form a forest closed under `parent`: a block is
+    cached only together with the whole prefix in front of it.
+
+    Nothing here looks at a clock or iterates a dict of unequal things in hash order: `tick` is a counter the batcher bumps per
+    admitted request, eviction orders by (tick, key).  Tensor-parallel ranks fed the same requests reach the same decisions.
+
+    Eviction: only entries whose page has page_refs == 1 (the cache's hold alone), unpinned and without children; least recently
+    used first; exactly as many as asked for.
+
+    The device digest is a content hash, not a cryptographic one (include/vita_hip.h vh_hash_row_blocks): a miss is always safe, a
+    false hit would not be, which is why the cache is opt-in."""
+
+    def __init__(self, engine, digests=None):
+        self.eng = engine
+        self.digests = digests or device_digests
+        self.entries = {}
+        self.pinned = set()               # pages a request of the current admission pass is about to adopt
+        self.tick = 0
+        self.evictions = 0
+
+    def keys_after(self, keys, rows):
+        """keys of the complete blocks of `rows`, which continue the prefix whose keys are `keys`."""
+        return chain_keys(self.digests(rows), int(rows.shape[1]), keys[-1] if keys else PREFIX_ROOT_KEY)
+
+    def match(self, keys, limit):
+        """-> pages of the longest cached chain among the first `limit` keys; the chain is touched."""
+        pages = []
+        for k in keys[:max(int(limit), 0)]:
+            e = self.entries.get(k)
+            if e is None:
+                break
+            e[3] = self.tick
+            pages.append(e[0])
+        return pages
+
+    def insert(self, key, parent, page):
+        """`page` (already held once for the cache) under `key`; parent: the key in front of it, None for block 0."""
+        self.entries[key] = [int(page), parent, 0, self.tick]
+        if parent is not None:
+            self.entries[parent][2] += 1
+
+    def _idle(self, e):
+        return e[0] not in self.pinned and self.eng.page_refs(e[0]) == 1
+
+    def evictable(self):
+        """entries evict() could remove: idle ones all of whose descendants are idle."""
+        blocked = set()
+        for k, e in self.entries.items():
+            if not self._idle(e):
+                while k is not None and k not in blocked:
+                    blocked.add(k)
+                    k = self.entries[k][1]
+        return len(self.entries) - len(blocked)
+
+    def evict(self, n):
+        """give up to n pages back to the pool -> how many."""
+        done = 0
+        while done < n:
+            # the least recently used childless idle entry, ties by key; a chain shares one tick and only its leaf is childless: the
+            # parent becomes a candidate when the leaf is gone
+            leaves = sorted((e[3], k) for k, e in self.entries.items() if e[2] == 0)
+            k = next((k for _, k in leaves if self._idle(self.entries[k])), None)
+            if k is None:
+                break
+            page, parent = self.entries.pop(k)[:2]
+            if parent is not None:
+                self.entries[parent][2] -= 1
+            self.eng.pages_release([page])
+            done += 1
+        self.evictions += done
+        return done
+
+    def clear(self):
+        """drop every entry and its hold (pages a running sequence adopted stay that sequence's until it ends)."""
+        pages = sorted(e[0] for e in self.entries.values())
+        self.entries.clear()
+        self.pinned.clear()
+        if pages:
+            self.eng.pages_release(pages)
+
+
 # ---- concurrent requests: iteration-level scheduling over the paged KV cache -------------------------------------------
 class ContinuousBatcher:
     """The scheduler half of vLLM's engine for this path (what drives the plugin's forward with `kv_caches` +
@@ -391,10 +507,26 @@ class ContinuousBatcher:
       abort(request_id)
 
     A sequence's ids do not depend on what else is scheduled (same kernels, same arithmetic per sequence); tokens decoded
-    past an eos inside a window are discarded, as MixtralEngine's single-request lookahead does."""
+    past an eos inside a window are discarded, as MixtralEngine's single-request lookahead does.
 
-    def __init__(self, engine, embed_tokens=None, max_batch=None, window=1):
+    prefix_cache=True (or a PrefixCache): vLLM's enable_prefix_caching.  On admission the prompt's 64-row blocks are keyed by content
+    (one vh_hash_row_blocks launch + one small device-to-host copy per admitted request: the only synchronisation the feature adds);
+    the longest cached chain, at most (S - 1) // 64 pages since one row must be prefilled for the first token's logits, is adopted
+    (seq_alloc, seq_adopt) and only emb[64 * hit:] is prefilled, as a member of the admission group like any other prompt (it counts
+    S - 64 * hit rows against max_prefill).  Right after a request's prefill is enqueued its full prompt pages that are not cached yet
+    are held and inserted — everything runs on one stream, so an adopter's kernels are ordered after the writer's; two requests of
+    the SAME admission group therefore do not share.  With an embed_tokens hook, a request that finishes, is aborted or is preempted
+    also registers its pages that lie entirely below its position, the ones filled by generated tokens included (keys continue the
+    chain over cat(open block's prompt rows, embed_tokens(out[:-1]))): a follow-up turn that repeats prompt + response finds them,
+    and a preempted request finds its own pages.  Pool accounting is "free + evictable - promised"; cached pages are evicted
+    (childless first, least recently used first, exactly as many as needed) before any running sequence is preempted.
+    stats: prefix_queries (lookups), prefix_hit_tokens, prefix_evictions, prefill_rows (rows sent to prefill calls, counted with the
+    cache off as well); cached_tokens[request id] is the hit of a request's first admission (the caller pops it)."""
+
+    def __init__(self, engine, embed_tokens=None, max_batch=None, window=1, prefix_cache=False):
         self.eng, self.embed_tokens = engine, embed_tokens
+        self.cache = prefix_cache if isinstance(prefix_cache, PrefixCache) else (PrefixCache(engine) if prefix_cache else None)
+        self.cached_tokens = {}
         self.max_batch = int(max_batch or engine.c.max_seqs)
         if engine.c.max_seqs < 1:
             raise ValueError("the engine was created without sequence slots (max_seqs = 0)")
@@ -402,7 +534,8 @@ class ContinuousBatcher:
         self.waiting = collections.deque()
         self.running = []                 # admission order
         self.errors = {}                  # request id -> exception of a request that failed alone (event reason "error")
-        self.stats = {"iterations": 0, "prefills": 0, "prefill_calls": 0, "preemptions": 0, "decode_steps": 0, "failed": 0}
+        self.stats = {"iterations": 0, "prefills": 0, "prefill_calls": 0, "preemptions": 0, "decode_steps": 0, "failed": 0,
+                      "prefix_queries": 0, "prefix_hit_tokens": 0, "prefix_evictions": 0, "prefill_rows": 0}
         self.logprobs = {}                # request id -> per-token {id: logprob} of requests with rules["logprobs"] >= 0; the entry of a
                                           # finished request stays until the caller pops it (a failed or aborted one is dropped here)
 
@@ -423,8 +556,10 @@ class ContinuousBatcher:
 
     def abort(self, request_id):
         self.logprobs.pop(request_id, None)
+        self.cached_tokens.pop(request_id, None)
         for r in list(self.running):
             if r["id"] == request_id:
+                self._register_written(r)
                 self.eng.seq_free(r["seq"])
                 self.running.remove(r)
                 return True
@@ -443,12 +578,70 @@ class ContinuousBatcher:
     def _prefill(self, r):
         """the prompt of a request — or, after a preemption, prompt + generated tokens, which may exceed what one prefill call
         takes — in chunks of max_prefill (seq_prefill appends at the sequence's position)."""
-        emb, mp = r["emb"], int(self.eng.max_prefill)
+        emb, mp = self._suffix(r), int(self.eng.max_prefill)
         for s0 in range(0, int(emb.shape[0]), mp):
             if s0 > 0 and s0 + mp >= int(emb.shape[0]):
                 self._arm(r)                 # a chunked re-prompt: only the LAST chunk's token is an output (the table counts it)
             self.eng.seq_prefill(r["seq"], emb[s0:s0 + mp])
             self.stats["prefill_calls"] += 1
+            self.stats["prefill_rows"] += int(emb[s0:s0 + mp].shape[0])
+
+    def _suffix(self, r):
+        """the rows of r's prompt that are prefilled: all of them, or what lies behind the pages it adopted."""
+        hit = r.get("hit", 0)
+        return r["emb"][64 * hit:] if hit else r["emb"]
+
+    # ---- prefix cache ----------------------------------------------------------------------------------------------------------
+    def _lookup(self, r):
+        """keys of r's complete prompt blocks (hashed once per prompt; a re-prompt after a preemption only grew) -> the cached pages
+        r may adopt, pinned until the admission pass ends."""
+        c, S = self.cache, int(r["emb"].shape[0])
+        keys = r.setdefault("keys", [])
+        if len(keys) < S // 64:
+            keys += c.keys_after(keys, r["emb"][64 * len(keys):])
+        pages = c.match(keys, (S - 1) // 64)
+        c.pinned.update(pages)
+        return pages
+
+    def _register(self, r, n_full):
+        """hold r's first n_full pages for the cache, as far as their keys are not cached yet (those form the tail of the chain)."""
+        c, keys = self.cache, r["keys"]
+        new = [b for b in range(min(n_full, len(keys))) if keys[b] not in c.entries]
+        if not new:
+            return
+        pages = self.eng.seq_hold_prefix(r["seq"], new[-1] + 1)
+        if new[0] > 0:
+            self.eng.pages_release(pages[:new[0]])             # the hold covers the table's head: the cached part goes back
+        for b in new:
+            c.insert(keys[b], keys[b - 1] if b else None, pages[b])
+
+    def _register_written(self, r, rows=None):
+        """before r's sequence is freed: register its pages that lie entirely below its position, those filled by generated tokens
+        included.  rows: r's prompt + embed_tokens(its output), when the caller has built it anyway (preemption)."""
+        if self.cache is None or self.embed_tokens is None or r.get("seq") is None:
+            return
+        S, keys = int(r["emb"].shape[0]), r.setdefault("keys", [])
+        gen = r["out"][r["base"]:]
+        # K/V of position S + i is the row of generated token i; the last accepted token was never fed (or its row is discarded)
+        valid = min(self.eng.seq_pos(r["seq"]), S + max(len(gen) - 1, 0))
+        if valid // 64 > len(keys):
+            k0 = 64 * len(keys)
+            if rows is None:
+                tail = self.embed_tokens(torch.tensor(gen[:-1], dtype=torch.long, device=r["emb"].device)).to(torch.float32)
+                rows = torch.cat([r["emb"][k0:], tail], dim=0)
+            else:
+                rows = rows[k0:]
+            keys += self.cache.keys_after(keys, rows[:64 * (valid // 64) - k0])
+        self._register(r, valid // 64)
+
+    def _make_room(self, short):
+        """the pool is `short` pages short: evict that many cached pages if the cache can -> True when it could."""
+        if short <= 0:
+            return True
+        if self.cache is None or self.cache.evictable() < short:
+            return False
+        self.stats["prefix_evictions"] += self.cache.evict(short)
+        return True
 
     def _arm(self, r):
         """the logit rules of r's slot with its history: the prompt set, and every token generated so far as outputs."""
@@ -460,6 +653,7 @@ class ContinuousBatcher:
         is touched.  Device-level failures (spin time-outs, launch errors seen at the synchronisation) still propagate."""
         self.errors[r["id"]] = exc
         self.logprobs.pop(r["id"], None)
+        self.cached_tokens.pop(r["id"], None)
         self.stats["failed"] += 1
         events.append((r["id"], [], True, "error"))
 
@@ -476,6 +670,8 @@ class ContinuousBatcher:
         r["fresh"] = True                    # its first token (tokens[0]) is not reported yet
         self.running.append(r)
         self.stats["prefills"] += 1
+        if self.cache is not None:           # the prefill is enqueued: its full prompt pages can be shared from here on
+            self._register(r, int(r["emb"].shape[0]) // 64)
 
     def _prefill_group(self, group, events):
         """the admitted requests of one group, in admission order: two or more in one pass over the weights.  A group call that
@@ -484,8 +680,9 @@ class ContinuousBatcher:
         done = False
         if len(group) >= 2:
             try:
-                self.eng.seq_prefill_batch([r["seq"] for r in group], [r["emb"] for r in group])
+                self.eng.seq_prefill_batch([r["seq"] for r in group], [self._suffix(r) for r in group])
                 self.stats["prefill_calls"] += 1
+                self.stats["prefill_rows"] += sum(int(self._suffix(r).shape[0]) for r in group)
                 done = True
             except Exception:
                 done = False
@@ -501,9 +698,19 @@ class ContinuousBatcher:
         while self.waiting and len(self.running) + len(group) < self.max_batch:
             r = self.waiting[0]
             # the pool as it will be once the group is prefilled: the pages promised to its prompts are gone, its members run
-            free = self.eng.pages_free() - sum(self._pages(g["emb"].shape[0]) for g in group)
+            # (pages a member adopted from the prefix cache are in its table already)
+            free = self.eng.pages_free() - sum(self._pages(g["emb"].shape[0]) - g.get("hit", 0) for g in group)
             n_run = len(self.running) + len(group)
             need = self._pages(r["emb"].shape[0] + 1) + n_run                   # + one page of headroom per runner
+            hit = []
+            if self.cache is not None:
+                self.cache.tick += 1
+                hit = self._lookup(r)
+                need -= len(hit)
+                if not self._make_room(need - free):        # free + evictable - promised; the pinned pages are not evictable
+                    self.cache.pinned.difference_update(hit)
+                else:
+                    free = max(free, need)
             if need > free:
                 if n_run == 0:
                     self.waiting.popleft()
@@ -517,6 +724,19 @@ class ContinuousBatcher:
             except Exception as e:
                 self._fail(r, e, events)
                 continue
+            if self.cache is not None:
+                r["hit"] = len(hit)
+                self.stats["prefix_queries"] += 1
+                self.stats["prefix_hit_tokens"] += 64 * len(hit)
+                self.cached_tokens.setdefault(r["id"], 64 * len(hit))
+                if hit:
+                    try:
+                        self.eng.seq_adopt(r["seq"], hit)
+                    except Exception as e:
+                        self.eng.seq_free(r["seq"])
+                        r["seq"] = None
+                        self._fail(r, e, events)
+                        continue
             if r["sampling"] is not None:
                 # draw index of the next token = tokens already generated (r["base"] after a recompute preemption): the
                 # continued ids are the ones an unpreempted run draws
@@ -527,7 +747,7 @@ class ContinuousBatcher:
                     r["seq"] = None
                     self._fail(r, e, events)
                     continue
-            S = int(r["emb"].shape[0])
+            S = int(r["emb"].shape[0]) - 64 * r.get("hit", 0)     # the rows that are prefilled
             if S <= mp:                          # (a chunked re-prompt arms its rules in front of its last chunk: _prefill)
                 try:
                     self._arm(r)
@@ -547,6 +767,8 @@ class ContinuousBatcher:
             group.append(r)
             rows += S
         self._prefill_group(group, events)
+        if self.cache is not None:
+            self.cache.pinned.clear()
         return events
 
     def _preempt_for(self, steps):
@@ -554,15 +776,26 @@ class ContinuousBatcher:
         while True:
             new_pages = sum(self._pages(self.eng.seq_pos(r["seq"]) + steps) - len(self.eng.seq_pages(r["seq"]))
                             for r in self.running)
-            if new_pages <= self.eng.pages_free() or len(self.running) <= 1:
+            short = new_pages - self.eng.pages_free()
+            if short > 0 and self.cache is not None:              # cached pages yield before a running sequence does
+                self.stats["prefix_evictions"] += self.cache.evict(short)
+                short = new_pages - self.eng.pages_free()
+            if short <= 0 or len(self.running) <= 1:
                 return
             r = self.running.pop()
-            self.eng.seq_free(r["seq"])
+            keep = self.cache is not None and self.embed_tokens is not None   # register its written pages before they are freed
+            if not keep:
+                self.eng.seq_free(r["seq"])
             if r["out"] and self.embed_tokens is None:
                 raise RuntimeError("KV pool exhausted and no embed_tokens hook to recompute a preempted sequence")
+            emb = r["emb"]
             if r["out"][r["base"]:]:
                 tail = self.embed_tokens(torch.tensor(r["out"][r["base"]:], dtype=torch.long, device=r["emb"].device))
-                r["emb"] = torch.cat([r["emb"], tail.to(torch.float32)], dim=0)
+                emb = torch.cat([r["emb"], tail.to(torch.float32)], dim=0)
+            if keep:                                              # its written pages stay findable: the re-prompt adopts them
+                self._register_written(r, rows=emb)
+                self.eng.seq_free(r["seq"])
+            r["emb"] = emb
             r["base"], r["seq"] = len(r["out"]), None
             self.waiting.appendleft(r)
             self.stats["preemptions"] += 1
@@ -619,6 +852,7 @@ class ContinuousBatcher:
             if reason is None and (r is starved or self.eng.seq_pos(r["seq"]) + 2 >= self.eng.max_ctx):
                 reason = "length"                                 # the pool cannot hold another token of this sequence
             if reason:
+                self._register_written(r)
                 self.eng.seq_free(r["seq"])
                 self.running.remove(r)
             if accepted or reason:
@@ -643,6 +877,7 @@ class AsyncEngineArgs:
     device: str = "cuda"
     quantization: Optional[str] = None       # None or "experts_int8" (LLM)
     max_logprobs: int = 0                    # > 0 (<= 20): SamplingParams' penalties and logprobs on the device (LLM)
+    enable_prefix_caching: bool = False      # reuse the KV pages of earlier prompts with the same leading rows (ContinuousBatcher)
 
 
 class AsyncLLMEngine:
@@ -656,11 +891,14 @@ class AsyncLLMEngine:
     stream (encoders + prefill of admitted requests, then one decode step for every running sequence per iteration) and
     posts RequestOutputs to the callers' event loops."""
 
-    def __init__(self, llm: "LLM", max_num_seqs=None, window=1):
+    def __init__(self, llm: "LLM", max_num_seqs=None, window=1, enable_prefix_caching=None):
         self.llm = llm
         eng = llm.model.engine
+        if enable_prefix_caching is None:
+            enable_prefix_caching = getattr(llm, "enable_prefix_caching", False)
         self.batcher = ContinuousBatcher(eng, embed_tokens=lambda ids: llm.model.model.embed_tokens(ids),
-                                         max_batch=max_num_seqs, window=window)
+                                         max_batch=max_num_seqs, window=window, prefix_cache=bool(enable_prefix_caching))
+        self._cache_resets = []           # threading.Event per pending reset_prefix_cache()
         self._lock = threading.Lock()
         self._cv = threading.Condition(self._lock)
         self._incoming, self._aborts, self._sinks = [], [], {}
@@ -675,8 +913,19 @@ class AsyncLLMEngine:
                   gpu_memory_utilization=args.gpu_memory_utilization,
                   limit_mm_per_prompt=args.limit_mm_per_prompt, max_new_tokens=args.max_new_tokens, device=args.device,
                   max_num_seqs=args.max_num_seqs, kv_pool_tokens=pool, quantization=args.quantization,
-                  max_logprobs=args.max_logprobs)
+                  max_logprobs=args.max_logprobs, enable_prefix_caching=args.enable_prefix_caching)
         return cls(llm, max_num_seqs=args.max_num_seqs, **kw)
+
+    def reset_prefix_cache(self, timeout=30.0):
+        """drop every cached prefix (vLLM's name): done by the scheduler thread between two iterations; returns once it is done.
+        Pages that running requests adopted stay theirs until they end.  -> True (False: no cache, or the scheduler did not answer)."""
+        if self.batcher.cache is None:
+            return False
+        done = threading.Event()
+        with self._cv:
+            self._cache_resets.append(done)
+            self._cv.notify()
+        return done.wait(timeout)
 
     async def get_tokenizer(self):
         return self.llm.tokenizer
@@ -694,12 +943,17 @@ class AsyncLLMEngine:
         state = {}                                   # request id -> (prompt ids, sampling params, token list)
         while True:
             with self._cv:
-                while not (self._incoming or self._aborts or self.batcher.has_work() or self._closed):
+                while not (self._incoming or self._aborts or self._cache_resets or self.batcher.has_work() or self._closed):
                     self._cv.wait()
                 if self._closed:
                     return
                 incoming, self._incoming = self._incoming, []
                 aborts, self._aborts = self._aborts, []
+                resets, self._cache_resets = self._cache_resets, []
+            if resets:
+                self.batcher.cache.clear()
+                for ev in resets:
+                    ev.set()
             for rid in aborts:
                 self.batcher.abort(rid)
                 state.pop(rid, None)
@@ -734,8 +988,9 @@ class AsyncLLMEngine:
                 toks += new
                 text = self.llm.tokenizer.decode(toks, skip_special_tokens=sp.skip_special_tokens)
                 lps = self.batcher.logprobs.pop(rid, None) if finished else self.batcher.logprobs.get(rid)
+                cached = self.batcher.cached_tokens.pop(rid, 0) if finished else self.batcher.cached_tokens.get(rid, 0)
                 self._post(rid, RequestOutput(request_id=str(rid), prompt_token_ids=ids, finished=finished,
-                                              outputs=[completion(0, text, list(toks), reason, lps)]))
+                                              outputs=[completion(0, text, list(toks), reason, lps)], num_cached_tokens=cached))
                 if finished:
                     state.pop(rid)
 
