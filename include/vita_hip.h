@@ -458,6 +458,15 @@ int vh_rope_kv_append(const float* qkv, long ldqkv, float* q_out, float* kcache,
 int vh_attn_decode(const float* qkv, float* kcache, float* vcache, int pos, const float* rope_cos, const float* rope_sin,
                    int nq, int nkv, int max_ctx, float scale, const int* table, float* part_o, float* part_ml, int* tickets,
                    float* attn_out, void* stream);
+/* vh_attn_decode_batch: vh_attn_decode for n (1 ... 4) sequences of one paged K / V pool in ONE launch — the attention step of a
+ *   batched decode iteration (vh_mixtral_seq_decode), per sequence the arithmetic of vh_attn_decode.  qkv, pos, table, part_o,
+ *   part_ml, tickets and attn_out are HOST arrays of n entries: sequence b appends its token at pos[b] through its page table
+ *   table[b] (entry nullable: the contiguous layout) and attends over [0, pos[b]].  Every sequence has its own scratch (sizes as
+ *   for vh_attn_decode) and output; the sequences' pages must be disjoint.  VH_E_ARG: a null pointer, buffers shared between two
+ *   sequences; VH_E_SHAPE: n outside [1, 4], a position outside the cache.  Nothing is launched on an error.                  */
+int vh_attn_decode_batch(int n, const float* const* qkv, float* kcache, float* vcache, const int* pos, const float* rope_cos,
+                         const float* rope_sin, int nq, int nkv, int max_ctx, float scale, const int* const* table,
+                         float* const* part_o, float* const* part_ml, int* const* tickets, float* const* attn_out, void* stream);
 /* vh_lmhead_argmax (K27 + K28): logits = lm_head(norm(x + delta)) in fp32 (vita_mixtral.py:171-172) and their argmax
  *   (lowest index on ties, as torch.argmax in HF greedy search).  W bf16 [V][H]; logits fp32 [V]; token_out int[1];
  *   blk_val / blk_idx: nblk floats / ints of scratch (nblk = blocks of the launch, e.g. 1024).                               */

@@ -238,6 +238,32 @@ def test_c_abi_exports_every_declared_symbol():
     assert lib.vh_mixtral_workspace_bytes(ctypes.byref(cfg)) == 0 and b"head_dim" in lib.vh_last_error()
 
 
+def test_attn_decode_batch_checks_its_arguments_before_any_launch():
+    """vh_attn_decode_batch refuses n outside [1, 4], a position outside the cache, null pointers and buffers shared between two
+    sequences on the host (no GPU needed; tests/test_ops_gpu.py repeats this with real buffers and checks that nothing was written)."""
+    from vita_amd import _lib
+    lib = _lib.load()
+    arr = lambda *v: (ctypes.c_void_p * 4)(*v)
+    good = dict(qkv=arr(64, 128, 192, 256), table=arr(None, None, None, None), part_o=arr(1024, 2048, 3072, 4096),
+                part_ml=arr(5120, 6144, 7168, 8192), tickets=arr(9216, 9232, 9248, 9264), attn_out=arr(10240, 11264, 12288, 13312))
+
+    def call(n, pos=(0, 1, 2, 3), **over):
+        a = dict(good, **over)
+        rc = lib.vh_attn_decode_batch(n, a["qkv"], 64, 64, (ctypes.c_int * 4)(*pos), 64, 64, 8, 2, 128, 0.1, a["table"], a["part_o"],
+                                      a["part_ml"], a["tickets"], a["attn_out"], None)
+        return rc, lib.vh_last_error()
+
+    assert call(0)[0] == -1 and call(5) == (-1, b"vh_attn_decode_batch: 5 sequences outside [1, 4]")
+    assert call(4, pos=(0, 1, 2, 128)) == (-1, b"vh_attn_decode_batch: position 128 of sequence 3 outside the cache (128)")
+    assert call(2, pos=(0, -1, 2, 3))[0] == -1
+    assert call(2, part_o=arr(1024, 1024, 3072, 4096)) == (-2, b"vh_attn_decode_batch: sequences 0 and 1 share a scratch or output buffer")
+    assert call(3, tickets=arr(9216, 9232, 9216, 9264))[0] == -2 and call(2, attn_out=arr(10240, 10240, 1, 2))[0] == -2
+    assert call(2, qkv=arr(64, None, 192, 256)) == (-2, b"vh_attn_decode_batch: null pointer (sequence 1)")
+    assert call(1, part_ml=None) == (-2, b"vh_attn_decode_batch: null pointer")
+    assert call(4, pos=(0, 127, 64, 5), qkv=arr(64, 128, 192, None))[0] == -2
+    # (every call above is refused: nothing here may reach a launch, the pointers are made up)
+
+
 def test_removed_knobs_are_rejected():
     """vh_tune refuses keys of variants that no longer exist (a script that still sets them must fail loudly)."""
     import pytest

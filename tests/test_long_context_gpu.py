@@ -20,6 +20,7 @@ import pytest
 import torch
 
 from oracle import mixtral as om
+from tests.seq_scores import check_sequence
 from tests.util import assert_close, to_np
 from vita_amd.checkpoint import pack_mixtral, round_bf16, synth_state_dict
 from vita_amd.config import TextConfig, VitaConfig
@@ -176,7 +177,7 @@ def test_prompt_at_model_limit_skewed_routing(dev):
 
 
 # ---- c. a served sequence of more than 64 pages ------------------------------------------------------------------------------
-PAGED_SEED, PAGED_STEPS, PAGED_CHUNK = 9, 10, 2048
+PAGED_SEED, PAGED_STEPS, PAGED_CHUNK, PAGED_LOGPROBS = 9, 10, 2048, 20
 
 
 @pytest.mark.timeout(600)
@@ -185,7 +186,9 @@ def test_paged_sequence_past_64_pages(dev):
     long one is prefilled in chunks of max_prefill = 2048 (the flash form through the page table, k_rope_kv with `table`) with the
     short one's prefill in between, so that its 66 pages are not contiguous; then both advance together through the batched decode
     kernels.  Ids equal each request's own oracle; the prefill score rows, and the row a one-token prefill at position 4209 takes
-    from K / V rows written by the decode steps, within 1e-3 (the sequence API exposes no per-step scores)."""
+    from K / V rows written by the decode steps, within 1e-3.  Every batched step's scores: both sequences keep logprobs = 20, and
+    every generated token's log-probability and top-20 list are held to the oracle's row of that step within 2 LOGIT_TOL
+    (tests/seq_scores.py) — 66 splits next to 1 in one k_decb_attn launch, the second lane round of its merge."""
     from vita_amd.engine import MixtralEngine
     cfg = _cfg(2, hidden=512, nq=8, nkv=2)
     t = cfg.text
@@ -200,9 +203,11 @@ def test_paged_sequence_past_64_pages(dev):
         _assert_margins(refs[-1])
     pool = 70 * 64                       # 66 + 1 pages are needed
     eng = MixtralEngine(cfg, pack_mixtral(sd, cfg, dev), dev, max_ctx=pool, max_prefill=PAGED_CHUNK, max_new=PAGED_STEPS + 4,
-                        max_seqs=2)
+                        max_seqs=2, max_logprobs=PAGED_LOGPROBS)
     try:
         a, b = eng.seq_alloc(), eng.seq_alloc()
+        eng.seq_set_logit_rules(a, logprobs=PAGED_LOGPROBS)
+        eng.seq_set_logit_rules(b, logprobs=PAGED_LOGPROBS)
         A, B = embs
         eng.seq_prefill(a, A[:PAGED_CHUNK])
         lg_b = eng.seq_prefill(b, B, want_logits=True)              # B's page lands between A's
@@ -222,6 +227,9 @@ def test_paged_sequence_past_64_pages(dev):
             print(f"sequence of {S}: oracle {ref['ids'][:PAGED_STEPS]} device {got}")
             assert got == ref["ids"][:PAGED_STEPS], f"sequence of {S} tokens differs from its oracle"
             assert eng.seq_pos(s) == S + PAGED_STEPS - 1
+            lp = tuple(x.cpu().numpy().copy() for x in eng.logprobs(s))
+            worst = check_sequence(ref["logits"], got, lp, PAGED_LOGPROBS, LOGIT_TOL, what=f"sequence of {S}")
+            print(f"sequence of {S}: log-probabilities of {PAGED_STEPS} tokens within {worst:.2e} (bound {2 * LOGIT_TOL:.0e})")
         # one more row of A through the prefill path: it attends to the K / V rows the batched decode steps appended
         last = torch.from_numpy(sd["model.embed_tokens.weight"][refs[0]["ids"][PAGED_STEPS - 1]][None]).to(dev)
         lg = eng.seq_prefill(a, last, want_logits=True)

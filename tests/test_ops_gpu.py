@@ -749,6 +749,50 @@ def _steer(q_roped, target):
     return Q.T @ np.linalg.solve(Q @ Q.T, np.full(Q.shape[0], float(target)))
 
 
+_ATTN_PATTERNS = {"late-max-20": (70 * 64 + 9, 25.0, None), "late-max-100": (70 * 64 + 9, 100.0, None),
+                  "late-splits-underflow": (5, 60.0, -60.0)}
+
+
+def _steer_pattern(rng, pattern, qkv, kl, pos, c, s, nq, nkv, scale):
+    """the score patterns of test_attn_decode_long_context, written into the logical K rows kl [nkv, rows, 128] and (underflow) the
+    appended key of qkv, both in place."""
+    if pattern == "random":
+        return
+    d, G = 128, nq // nkv
+    qr = _rope64(qkv[:nq * d].reshape(nq, d), c, s)
+    hi_key, hi, lo = _ATTN_PATTERNS[pattern]
+    for h in range(nkv):
+        Qg = qr[h * G:(h + 1) * G]
+        kl[h, hi_key] = _steer(Qg, hi / scale).astype(np.float32)
+        if lo is not None:
+            kl[h, 65 * 64:pos] = (_steer(Qg, lo / scale)[None, :] + 0.1 * rng.standard_normal((pos - 65 * 64, d))).astype(np.float32)
+            kn = _unrope64(_steer(Qg, lo / scale), c, s)          # the appended key lies in split 71 as well
+            qkv[(nq + h) * d:(nq + h + 1) * d] = kn.astype(np.float32)
+
+
+def _attn_decode_ref(qkv, kl, vl, pos, c, s, nq, nkv, scale, pattern="random"):
+    """fp64 attention of one token at `pos` over the logical rows kl / vl [nkv, >= pos, 128] and its own appended row -> (output
+    [nq * 128], RoPE'd appended K rows [nkv, 128], appended V rows); asserts that a steered pattern is what it claims to be."""
+    d, G = 128, nq // nkv
+    qr = _rope64(qkv[:nq * d].reshape(nq, d), c, s)
+    k_new = _rope64(qkv[nq * d:(nq + nkv) * d].reshape(nkv, d), c, s)
+    v_new = qkv[(nq + nkv) * d:].reshape(nkv, d)
+    K = kl[:, :pos + 1].astype(np.float64)
+    V = vl[:, :pos + 1].astype(np.float64)
+    K[:, pos], V[:, pos] = k_new, v_new
+    ref = np.empty(nq * d)
+    for hq in range(nq):
+        sc = K[hq // G] @ qr[hq] * scale
+        if pattern == "late-splits-underflow":
+            assert sc.max() - sc[65 * 64:].max() > 110          # the late splits' weights are exactly 0 in fp32
+        elif pattern != "random":
+            hi_key = _ATTN_PATTERNS[pattern][0]
+            assert np.argmax(sc) == hi_key and sc[hi_key] - np.delete(sc, hi_key).max() > 19
+        p = np.exp(sc - sc.max())
+        ref[hq * d:(hq + 1) * d] = (p / p.sum()) @ V[hq // G]
+    return ref, k_new, v_new
+
+
 @pytest.mark.parametrize("paged", [False, True], ids=["contiguous", "paged"])
 @pytest.mark.parametrize("nq,nkv", [(32, 8), (8, 2)])
 @pytest.mark.parametrize("pos,pattern", [(63, "random"), (64, "random"), (127, "random"), (4095, "random"), (4096, "random"),
@@ -776,39 +820,167 @@ def test_attn_decode_long_context(dev, nq, nkv, pos, pattern, paged):
     std = 1.0 if pattern == "random" else 0.1
     kl = (rng.standard_normal((nkv, LONG_CTX, d), dtype=np.float32) * std).astype(np.float32)
     vl = rng.standard_normal((nkv, LONG_CTX, d), dtype=np.float32)
-    qr = _rope64(qkv[:nq * d].reshape(nq, d), c, s)
-    if pattern != "random":
-        hi_key, hi, lo = {"late-max-20": (70 * 64 + 9, 25.0, None), "late-max-100": (70 * 64 + 9, 100.0, None),
-                          "late-splits-underflow": (5, 60.0, -60.0)}[pattern]
-        for h in range(nkv):
-            Qg = qr[h * G:(h + 1) * G]
-            kl[h, hi_key] = _steer(Qg, hi / scale).astype(np.float32)
-            if lo is not None:
-                kl[h, 65 * 64:pos] = (_steer(Qg, lo / scale)[None, :] + 0.1 * rng.standard_normal((pos - 65 * 64, d))).astype(np.float32)
-                kn = _unrope64(_steer(Qg, lo / scale), c, s)          # the appended key lies in split 71 as well
-                qkv[(nq + h) * d:(nq + h + 1) * d] = kn.astype(np.float32)
+    _steer_pattern(rng, pattern, qkv, kl, pos, c, s, nq, nkv, scale)
     perm = rng.permutation(LONG_CTX // 64) if paged else None
     table = _dev(perm, dev, torch.int32) if paged else None
     kc, vc = _dev(_to_pages(kl, perm), dev), _dev(_to_pages(vl, perm), dev)
     out = ops.attn_decode(_dev(qkv, dev), kc, vc, pos, _dev(cos, dev), _dev(sin, dev), nq, nkv, scale, table=table)
-    k_new = _rope64(qkv[nq * d:(nq + nkv) * d].reshape(nkv, d), c, s)
-    v_new = qkv[(nq + nkv) * d:].reshape(nkv, d)
-    K = kl[:, :pos + 1].astype(np.float64)
-    V = vl[:, :pos + 1].astype(np.float64)
-    K[:, pos], V[:, pos] = k_new, v_new
-    ref = np.empty(nq * d)
-    for hq in range(nq):
-        sc = K[hq // G] @ qr[hq] * scale
-        if pattern == "late-splits-underflow":
-            assert sc.max() - sc[65 * 64:].max() > 110          # the late splits' weights are exactly 0 in fp32
-        elif pattern != "random":
-            assert np.argmax(sc) == hi_key and sc[hi_key] - np.delete(sc, hi_key).max() > 19
-        p = np.exp(sc - sc.max())
-        ref[hq * d:(hq + 1) * d] = (p / p.sum()) @ V[hq // G]
+    ref, k_new, v_new = _attn_decode_ref(qkv, kl, vl, pos, c, s, nq, nkv, scale, pattern)
     kb, vb = _from_pages(to_np(kc), perm), _from_pages(to_np(vc), perm)
     assert_close(f"appended K row at {pos}", kb[:, pos], k_new, atol=5e-5)
     assert_close(f"appended V row at {pos}", vb[:, pos], v_new, atol=0)
     assert_close(f"attn_decode pos={pos} {pattern}", to_np(out), ref, atol=5e-5)
+
+
+# ---- the batched decode attention (vh_attn_decode_batch: k_decb_attn, the attention launch of a batched decode iteration) ---------
+_ATTN_BATCHES = [
+    ((8, 2), [63], None), ((32, 8), [63], None),
+    ((8, 2), [64, 63], None),
+    ((8, 2), [0, 127, 4095], None),
+    ((8, 2), [4600, 37, 4096, 4097], None),
+    ((8, 2), [37, 4097, 4096, 4600], None),                                                   # the longest last
+    ((8, 2), [4600] * 4, ["random", "random", "late-max-100", "late-splits-underflow"]),
+    ((32, 8), [4600] * 4, ["random", "random", "late-max-100", "late-splits-underflow"]),
+]
+
+
+def _attn_batch_setup(dev, nq, nkv, positions, patterns, seed):
+    """n sequences over ONE pool: every sequence owns ceil((pos + 1) / 64) pages dealt from one random permutation of the pool's
+    pages (so the sequences' pages interleave; 3 pages belong to nobody), random rows everywhere — stale rows past a sequence's
+    position in its last page included.  -> inputs on the device and the fp64 references per member."""
+    from vita_amd.engine import rope_tables
+    rng = np.random.default_rng(seed)
+    d, n = 128, len(positions)
+    scale = d ** -0.5
+    cos, sin = rope_tables(LONG_CTX, d, 1e6)
+    need = [p // 64 + 1 for p in positions]
+    n_pages = sum(need) + 3
+    perm = rng.permutation(n_pages)
+    pages = [perm[sum(need[:b]):sum(need[:b + 1])] for b in range(n)]
+    kp = rng.standard_normal((nkv, n_pages * 64, d), dtype=np.float32)
+    vp = rng.standard_normal((nkv, n_pages * 64, d), dtype=np.float32)
+    members = []
+    for b, pos in enumerate(positions):
+        pattern = patterns[b] if patterns else "random"
+        c, s = cos[pos].astype(np.float64), sin[pos].astype(np.float64)
+        qkv = rng.standard_normal((nq + 2 * nkv) * d, dtype=np.float32)
+        std = 1.0 if pattern == "random" else 0.1
+        kl = (rng.standard_normal((nkv, need[b] * 64, d), dtype=np.float32) * std).astype(np.float32)
+        vl = rng.standard_normal((nkv, need[b] * 64, d), dtype=np.float32)
+        _steer_pattern(rng, pattern, qkv, kl, pos, c, s, nq, nkv, scale)
+        for p, q in enumerate(pages[b]):
+            kp[:, q * 64:(q + 1) * 64] = kl[:, p * 64:(p + 1) * 64]
+            vp[:, q * 64:(q + 1) * 64] = vl[:, p * 64:(p + 1) * 64]
+        ref, k_new, v_new = _attn_decode_ref(qkv, kl, vl, pos, c, s, nq, nkv, scale, pattern)
+        members.append(dict(pos=pos, qkv=_dev(qkv, dev), table=_dev(pages[b], dev, torch.int32), ref=ref, k_new=k_new, v_new=v_new,
+                            row=int(pages[b][pos // 64]) * 64 + pos % 64))
+    # the pages interleave: no sequence of several pages holds a contiguous ascending run
+    assert all(len(pg) < 2 or not np.array_equal(pg, np.arange(pg[0], pg[0] + len(pg))) for pg in pages)
+    return dict(kc=_dev(kp, dev), vc=_dev(vp, dev), cos=_dev(cos, dev), sin=_dev(sin, dev), scale=scale, members=members)
+
+
+@pytest.mark.parametrize("heads,positions,patterns", _ATTN_BATCHES,
+                         ids=[f"{h[0]}-{h[1]}-" + "-".join(map(str, p)) + ("-patterns" if pt else "") for h, p, pt in _ATTN_BATCHES])
+def test_attn_decode_batch(dev, heads, positions, patterns):
+    """vh_attn_decode_batch = one k_decb_attn launch, grid (nkv, max splits of the batch, n): sequences of very different lengths
+    (73 splits next to 1: most blocks of the short ones leave at once), the longest in the first and in the last lane, a lone
+    sequence, positions on both sides of a page boundary and of the 64-split boundary of the merge, and the merge patterns of
+    test_attn_decode_long_context in lanes 2 and 3 next to random neighbours.  Per member against fp64: the output and the appended
+    K row within the batch-1 operator's 5e-5, the appended V row exactly.  Every other row of the pool stays bit-unchanged.  The
+    kernel promises the batch-1 arithmetic per sequence: every output, and the pool, are BIT-equal to vh_attn_decode run on the
+    members one after the other (own scratch, a copy of the pool).  A second call on the same scratch gives the same bits (the
+    tickets were left reset)."""
+    from vita_amd import ops
+    nq, nkv = heads
+    t = _attn_batch_setup(dev, nq, nkv, positions, patterns, seed=sum(positions) * 3 + nq + len(positions))
+    ms, kc, vc = t["members"], t["kc"], t["vc"]
+    k0, v0 = kc.clone(), vc.clone()
+    scratch = ops.attn_decode_scratch(len(ms), nq, nkv, kc.shape[1], dev)
+    for sc in scratch:
+        sc[3].fill_(float("nan"))
+    args = ([m["qkv"] for m in ms], kc, vc, [m["pos"] for m in ms], t["cos"], t["sin"], nq, nkv, t["scale"], [m["table"] for m in ms])
+    outs = [o.clone() for o in ops.attn_decode_batch(*args, scratch=scratch)]
+    torch.cuda.synchronize()
+    assert all(int(sc[2].abs().sum().item()) == 0 for sc in scratch), "tickets were not left at zero"
+    kg, vg = to_np(kc), to_np(vc)
+    for b, m in enumerate(ms):
+        what = f"member {b} of {positions} at pos {m['pos']}"
+        assert_close(f"attn_decode_batch {what}", to_np(outs[b]), m["ref"], atol=5e-5)
+        assert_close(f"appended K row, {what}", kg[:, m["row"]], m["k_new"], atol=5e-5)
+        assert_close(f"appended V row, {what}", vg[:, m["row"]], m["v_new"], atol=0)
+    rows = torch.tensor([m["row"] for m in ms], device=dev)
+    k0[:, rows], v0[:, rows] = kc[:, rows], vc[:, rows]
+    assert torch.equal(k0, kc) and torch.equal(v0, vc), "a pool row other than the appended ones changed"
+    # the members alone, one after the other, on a copy of the pool as it was before the call
+    k1, v1 = k0.clone(), v0.clone()
+    k1[:, rows], v1[:, rows] = float("nan"), float("nan")               # (the appended rows are written, never read)
+    for b, m in enumerate(ms):
+        solo = ops.attn_decode(m["qkv"], k1, v1, m["pos"], t["cos"], t["sin"], nq, nkv, t["scale"], table=m["table"])
+        assert torch.equal(solo, outs[b]), f"member {b} of {positions}: the batched output is not the batch-1 operator's, bit for bit"
+    assert torch.equal(k1, kc) and torch.equal(v1, vc), "the pool after the batched call is not the pool after the batch-1 calls"
+    again = ops.attn_decode_batch(*args, scratch=scratch)
+    for b in range(len(ms)):
+        assert torch.equal(again[b], outs[b]), f"member {b} of {positions}: a second call on the same scratch differs"
+    assert torch.equal(k1, kc) and torch.equal(v1, vc)
+
+
+def test_attn_decode_batch_refuses_bad_arguments(dev):
+    """n outside [1, VH_BMAX = 4], a position outside the pool, null pointers and scratch shared between two members are refused
+    before anything is launched: outputs, tickets and pool stay as they were."""
+    import ctypes as C
+    from vita_amd import _lib, ops
+    nq, nkv = 8, 2
+    t = _attn_batch_setup(dev, nq, nkv, [70, 5, 64, 130, 9], None, seed=3)
+    ms, kc, vc = t["members"], t["kc"], t["vc"]
+    max_ctx = kc.shape[1]
+    k0, v0 = kc.clone(), vc.clone()
+    scratch = ops.attn_decode_scratch(5, nq, nkv, max_ctx, dev)
+    for sc in scratch:
+        sc[3].fill_(float("nan"))
+
+    def call(idx, positions=None, scr=None, tables=None):
+        positions = [ms[i]["pos"] for i in idx] if positions is None else positions
+        return ops.attn_decode_batch([ms[i]["qkv"] for i in idx], kc, vc, positions, t["cos"], t["sin"], nq, nkv, t["scale"],
+                                     [ms[i]["table"] for i in idx] if tables is None else tables,
+                                     scratch=[scratch[i] for i in idx] if scr is None else scr)
+
+    with pytest.raises(_lib.VitaHipError, match="outside"):
+        call([0, 1, 2, 3, 4])                                           # five sequences
+    with pytest.raises(_lib.VitaHipError, match="outside"):
+        call([])
+    for bad in (max_ctx, -1, 1 << 30):
+        with pytest.raises(_lib.VitaHipError, match="outside the cache"):
+            call([0, 1], positions=[ms[0]["pos"], bad])
+    with pytest.raises(_lib.VitaHipError, match="share"):
+        call([0, 1], scr=[scratch[0], scratch[0]])
+    with pytest.raises(_lib.VitaHipError, match="share"):
+        call([0, 1, 2], scr=[scratch[0], scratch[1], scratch[0][:3] + (scratch[2][3],)])
+    # null pointers: the arrays themselves, an entry of them (a null page table is the contiguous layout and is accepted)
+    lib = _lib.load()
+    two = lambda ts: (C.c_void_p * 2)(*[tt.data_ptr() if tt is not None else None for tt in ts])
+    arrs = dict(qkv=two([ms[0]["qkv"], ms[1]["qkv"]]), table=two([ms[0]["table"], ms[1]["table"]]), part_o=two([scratch[0][0], scratch[1][0]]),
+                part_ml=two([scratch[0][1], scratch[1][1]]), tickets=two([scratch[0][2], scratch[1][2]]),
+                attn_out=two([scratch[0][3], scratch[1][3]]))
+    pos = (C.c_int * 2)(ms[0]["pos"], ms[1]["pos"])
+
+    def raw(**over):
+        a = dict(arrs, pos=pos, kc=kc.data_ptr(), vc=vc.data_ptr(), cos=t["cos"].data_ptr(), sin=t["sin"].data_ptr())
+        a.update(over)
+        return lib.vh_attn_decode_batch(2, a["qkv"], a["kc"], a["vc"], a["pos"], a["cos"], a["sin"], nq, nkv, max_ctx, t["scale"], a["table"],
+                                        a["part_o"], a["part_ml"], a["tickets"], a["attn_out"], None)
+
+    for name in ("qkv", "kc", "vc", "pos", "cos", "sin", "table", "part_o", "part_ml", "tickets", "attn_out"):
+        assert raw(**{name: None}) == -2 and b"null pointer" in lib.vh_last_error(), name          # VH_E_ARG
+    for name, ts in (("qkv", [ms[0]["qkv"], None]), ("part_o", [scratch[0][0], None]), ("part_ml", [None, scratch[1][1]]),
+                     ("tickets", [scratch[0][2], None]), ("attn_out", [None, scratch[1][3]])):
+        assert raw(**{name: two(ts)}) == -2 and b"null pointer" in lib.vh_last_error(), name
+    torch.cuda.synchronize()
+    assert torch.equal(k0, kc) and torch.equal(v0, vc), "a refused call wrote to the pool"
+    assert all(bool(torch.isnan(sc[3]).all()) and int(sc[2].abs().sum().item()) == 0 for sc in scratch), "a refused call wrote an output"
+    outs = call([0, 1])                                                  # and the same arguments, all valid, are accepted
+    torch.cuda.synchronize()
+    for b in (0, 1):
+        assert_close(f"member {b} after the refusals", to_np(outs[b]), ms[b]["ref"], atol=5e-5)
 
 
 @pytest.mark.parametrize("nq,nkv", [(32, 8), (8, 2)])

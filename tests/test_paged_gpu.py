@@ -13,11 +13,14 @@ import pytest
 import torch
 
 from oracle import mixtral as om
+from tests.seq_scores import LOGIT_TOL, check_sequence
 from tests.util import assert_close, to_np
 from vita_amd.checkpoint import pack_mixtral, synth_state_dict
 from vita_amd.config import VitaConfig
 
 pytestmark = pytest.mark.gpu
+
+LOGPROBS = 20          # top-K kept per generated token where a test also checks scores
 
 
 def _setup(dev, lens, n_new, seed=0, pool=1024, max_seqs=4, max_new=None, text=None):
@@ -295,7 +298,8 @@ def test_six_sequences_batched_kernels_real_width_match_oracle(dev, moe_min):
     attention / LM-head kernels, and the layer's MoE ONCE per iteration on the weight-streaming GEMM (k_gemm_ps tiles of <= 64 rows,
     device-chosen K split of the down projection, the few-row rules of r05: moe_min = 3, the default) or per sequence on the
     batch-1 expert GEMVs (moe_min = 0).  Every sequence's greedy ids == the layer-streamed fp32 oracle's for THAT sequence alone
-    (oracle/stream.py, teacher-forced over its own tokens)."""
+    (oracle/stream.py, teacher-forced over its own tokens), and every generated token's log-probability and top-20 list (logprobs = 20
+    per sequence) are the oracle's rows' within 2 LOGIT_TOL (tests/seq_scores.py)."""
     from oracle import stream
     from vita_amd import _lib
     from vita_amd.checkpoint import synth_mixtral_device
@@ -306,7 +310,7 @@ def test_six_sequences_batched_kernels_real_width_match_oracle(dev, moe_min):
     cfg.text.num_hidden_layers = layers
     t = cfg.text
     packed = synth_mixtral_device(cfg, dev, seed=seed)
-    eng = MixtralEngine(cfg, packed, dev, max_ctx=1024, max_prefill=160, max_new=n_new + 4, max_seqs=6)
+    eng = MixtralEngine(cfg, packed, dev, max_ctx=1024, max_prefill=160, max_new=n_new + 4, max_seqs=6, max_logprobs=LOGPROBS)
     rng = np.random.default_rng(23)
     prompts = [rng.integers(3, t.vocab_size, size=S).tolist() for S in lens]
     _lib.tune("batch_moe_min", moe_min)
@@ -314,11 +318,13 @@ def test_six_sequences_batched_kernels_real_width_match_oracle(dev, moe_min):
         seqs = []
         for ids in prompts:
             sq = eng.seq_alloc()
+            eng.seq_set_logit_rules(sq, logprobs=LOGPROBS)
             eng.seq_prefill(sq, packed["embed"][torch.as_tensor(ids, device=dev)].float())
             seqs.append(sq)
         for _ in range(n_new - 1):
             eng.seq_decode(seqs)                       # 6 sequences: 4 + 2
         toks = [_ids(eng, q, n_new) for q in seqs]
+        lps = [tuple(x.cpu().numpy().copy() for x in eng.logprobs(q)) for q in seqs]
     finally:
         _lib.tune("batch_moe_min", 3)
     eng.close()
@@ -329,7 +335,12 @@ def test_six_sequences_batched_kernels_real_width_match_oracle(dev, moe_min):
     for i, (tk, ref) in enumerate(zip(toks, refs)):
         ref_ids = ref["logits"].argmax(-1).tolist()
         assert tk == ref_ids, f"sequence {i} (prompt {lens[i]}): device {tk} vs oracle {ref_ids}"
-    print(f"six sequences at the released widths, {layers} layers, batch_moe_min = {moe_min}: ids == the streamed oracle's")
+    # ref["logits"] are the rows of the generated tokens (from the prompt's last row on): every token's log-probability and top-20
+    # list against them (tests/seq_scores.py) — the H = 4096 instantiations of k_decb_gemv / k_decb_lmhead, the streamed MoE with 6 rows
+    worst = max(check_sequence(ref["logits"], tk, lp, LOGPROBS, LOGIT_TOL, what=f"sequence {i} (prompt {lens[i]})")
+                for i, (tk, lp, ref) in enumerate(zip(toks, lps, refs)))
+    print(f"six sequences at the released widths, {layers} layers, batch_moe_min = {moe_min}: ids == the streamed oracle's, "
+          f"log-probabilities within {worst:.2e} (bound {2 * LOGIT_TOL:.0e})")
 
 
 def test_batcher_preempts_by_recompute_when_the_pool_runs_dry(dev):

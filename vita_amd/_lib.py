@@ -170,6 +170,8 @@ SIGNATURES = {
                                   c_int, c_void_p, c_void_p]),
     "vh_attn_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vh_attn_decode_batch": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vh_lmhead_argmax": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int, c_void_p]),
     "vh_mixtral_workspace_bytes": (c_size_t, [C.POINTER(MixtralCfg)]),

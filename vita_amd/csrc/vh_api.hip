@@ -282,9 +282,33 @@ int vh_attn_decode(const float* qkv, float* kcache, float* vcache, int pos, cons
                                                       tickets, attn_out, nq, nkv, max_ctx, max_splits, pos + 1, scale, table));
 }
 
+int vh_attn_decode_batch(int n, const float* const* qkv, float* kcache, float* vcache, const int* pos, const float* rope_cos,
+                         const float* rope_sin, int nq, int nkv, int max_ctx, float scale, const int* const* table,
+                         float* const* part_o, float* const* part_ml, int* const* tickets, float* const* attn_out, void* stream) {
+    if (!qkv || !kcache || !vcache || !pos || !rope_cos || !rope_sin || !table || !part_o || !part_ml || !tickets || !attn_out)
+        return fail(VH_E_ARG, "vh_attn_decode_batch: null pointer");
+    if (n < 1 || n > VH_BMAX) return fail(VH_E_SHAPE, "vh_attn_decode_batch: %d sequences outside [1, %d]", n, VH_BMAX);
+    if (nq < 1 || nkv < 1 || max_ctx < 1) return fail(VH_E_SHAPE, "vh_attn_decode_batch: nq, nkv and max_ctx must be positive");
+    VhDecBatchAttn at{};
+    for (int b = 0; b < n; ++b) {
+        if (!qkv[b] || !part_o[b] || !part_ml[b] || !tickets[b] || !attn_out[b])
+            return fail(VH_E_ARG, "vh_attn_decode_batch: null pointer (sequence %d)", b);
+        if (pos[b] < 0 || pos[b] >= max_ctx)
+            return fail(VH_E_SHAPE, "vh_attn_decode_batch: position %d of sequence %d outside the cache (%d)", pos[b], b, max_ctx);
+        for (int a = 0; a < b; ++a)      // every sequence has its own scratch and output: the blocks of all of them run side by side
+            if (part_o[a] == part_o[b] || part_ml[a] == part_ml[b] || tickets[a] == tickets[b] || attn_out[a] == attn_out[b])
+                return fail(VH_E_ARG, "vh_attn_decode_batch: sequences %d and %d share a scratch or output buffer", a, b);
+        at.qkv[b] = qkv[b]; at.pos[b] = pos[b]; at.table[b] = table[b];
+        at.part_o[b] = part_o[b]; at.part_ml[b] = part_ml[b]; at.cnt[b] = tickets[b]; at.attn_out[b] = attn_out[b];
+    }
+    const int max_splits = (max_ctx + 63) / 64;
+    return check_launch("vh_attn_decode_batch", vhk_decb_attn(S(stream), at, n, kcache, vcache, rope_cos, rope_sin, nq, nkv, max_ctx,
+                                                            max_splits, scale));
+}
+
 int vh_lmhead_argmax(const float* x, const float* delta, const float* norm_w, float eps, const uint16_t* W, int V, int H,
                      float* logits, int* token_out, float* blk_val, int* blk_idx, int nblk, void* stream) {
-    if (!x || !norm_w || !W || !logits || !token_out || !blk_val || !blk_idx) return fail(VH_E_ARG, "vh_lmhead_argmax: null pointer");
+    if (!x ||!norm_w || !W || !logits || !token_out || !blk_val || !blk_idx) return fail(VH_E_ARG, "vh_lmhead_argmax: null pointer");
     if (nblk < 1 || nblk > 4096 || H % 8) return fail(VH_E_SHAPE, "vh_lmhead_argmax: 1 <= nblk <= 4096, H %% 8 == 0");
     const int grid = nblk < (V + 7) / 8 ? nblk : (V + 7) / 8;
     int rc = check_launch("vh_lmhead_argmax", vhk_dec_lmhead(S(stream), x, delta, norm_w, eps, W, V, H, logits, blk_val, blk_idx, grid,

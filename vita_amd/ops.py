@@ -518,6 +518,38 @@ def attn_decode(qkv, kcache, vcache, pos, rope_cos, rope_sin, nq, nkv, scale, ta
     return out
 
 
+def attn_decode_scratch(n, nq, nkv, max_ctx, device):
+    """scratch and outputs of attn_decode_batch for n sequences: per sequence (part_o, part_ml, tickets (zeroed), attn_out)."""
+    ns = (max_ctx + 63) // 64
+    return [(torch.empty((nq, ns, 128), dtype=torch.float32, device=device), torch.empty((nq, ns, 2), dtype=torch.float32, device=device),
+             torch.zeros(nkv, dtype=torch.int32, device=device), torch.empty(nq * 128, dtype=torch.float32, device=device))
+            for _ in range(n)]
+
+
+def attn_decode_batch(qkvs, kcache, vcache, positions, rope_cos, rope_sin, nq, nkv, scale, tables, scratch=None):
+    """attn_decode for up to 4 sequences of one paged pool in ONE launch (vh_attn_decode_batch, the batched decode iteration's
+    attention kernel): sequence b appends qkvs[b] at positions[b] through its page table tables[b] (int32, disjoint pages) and
+    attends over [0, positions[b]] -> list of fp32 [nq * 128] (the attn_out tensors of `scratch`, default: fresh
+    attn_decode_scratch buffers; tickets must be zero before the first call and are left zero)."""
+    _dev(kcache, vcache, *qkvs)
+    n, max_ctx = len(qkvs), kcache.shape[1]
+    if not (n == len(positions) == len(tables)) or (scratch is not None and len(scratch) != n):
+        raise ValueError("attn_decode_batch: one position, page table and scratch entry per sequence")
+    for q in qkvs:
+        _f32(_c(q, "qkv"), "qkv")
+    if scratch is None:
+        scratch = attn_decode_scratch(n, nq, nkv, max_ctx, kcache.device)
+
+    def ptrs(ts):
+        return (C.c_void_p * max(n, 1))(*[None if t is None else t.data_ptr() for t in ts])
+    pos =(C.c_int * max(n, 1))(*[int(p) for p in positions])
+    check(_lib.load().vh_attn_decode_batch(n, ptrs(qkvs), _p(kcache), _p(vcache), pos, _p(rope_cos), _p(rope_sin), nq, nkv, max_ctx,
+                                           float(scale), ptrs(tables), ptrs([s[0] for s in scratch]), ptrs([s[1] for s in scratch]),
+                                           ptrs([s[2] for s in scratch]), ptrs([s[3] for s in scratch]), _stream()),
+          "vh_attn_decode_batch")
+    return [s[3] for s in scratch]
+
+
 def lmhead_argmax(x, norm_w, eps, w, delta=None, nblk=1024):
     """logits = lm_head(rmsnorm(x + delta)) fp32 [V] and their argmax (int32 [1], lowest index on ties)."""
     _dev(x, w)
