@@ -4,43 +4,16 @@ that request's iterator, duplicate request ids are refused, shutdown joins the s
 import asyncio
 import os
 import sys
-import types
 
 import pytest
-import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from tests.test_scheduler_cpu import FakeEngine, _emb, _expected   # noqa: E402
-
-
-class _Tok:
-    def decode(self, ids, skip_special_tokens=False):
-        return " ".join(str(i) for i in ids)
-
-
-class FakeLLM:
-    """the surface AsyncLLMEngine uses: model.engine / model.device / model.model.embed_tokens, _prepare, _embed, tokenizer."""
-
-    def __init__(self, pool_tokens=64 * 16, max_seqs=3):
-        eng = FakeEngine(pool_tokens, max_seqs, max_new=64)
-        table = torch.eye(FakeEngine.V)
-        self.model = types.SimpleNamespace(engine=eng, device=torch.device("cpu"),
-                                           model=types.SimpleNamespace(embed_tokens=lambda ids: table[ids]))
-        self.tokenizer = _Tok()
-
-    def _prepare(self, inputs, sp):
-        ids = list(inputs["prompt_token_ids"])
-        if any(i < 0 for i in ids):
-            raise ValueError("placeholder without data")
-        return dict(ids=ids, max_tokens=min(sp.max_tokens, 64), eos=set(sp.stop_token_ids or []))
-
-    def _embed(self, req):
-        return _emb(req["ids"])
+from tests.scripted_engine import FakeLLM, _expected, no_cuda_sync   # noqa: E402
 
 
 @pytest.fixture(autouse=True)
 def _no_cuda_sync(monkeypatch):
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: type("S", (), {"synchronize": lambda self: None})())
+    no_cuda_sync(monkeypatch)
 
 
 def test_concurrent_streams_abort_and_errors():

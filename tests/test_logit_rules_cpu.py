@@ -204,27 +204,12 @@ def test_async_engine_carries_logprobs_and_releases_them(monkeypatch):
     seq_set_logit_rules, and ContinuousBatcher.logprobs is empty once every request has finished, failed or been left early."""
     import asyncio
     import time
-    import torch
-    from tests.test_async_engine_cpu import FakeLLM
-    from tests.test_scheduler_cpu import FakeEngine, _expected
+    from tests.scripted_engine import FakeLLM, ScriptedEngine, _expected, no_cuda_sync
     from vita_amd.serving import AsyncLLMEngine, SamplingParams, rules_of
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: type("S", (), {"synchronize": lambda self: None})())
-    K = 3
-
-    class RulesEngine(FakeEngine):
-        armed = []
-
-        def seq_set_logit_rules(self, s, prompt_ids=None, output_ids=None, **kw):
-            self.armed.append((s, list(prompt_ids), list(output_ids), kw))
-
-        def logprobs(self, s):
-            toks = torch.tensor(self.seqs[s]["toks"] + [0] * (self.max_new - len(self.seqs[s]["toks"])))
-            ids = torch.stack([toks + j + 1 for j in range(K)], dim=1).to(torch.int32)          # top-K ids: token + 1 .. token + K
-            top = -(ids.float() + 0.5)
-            return -toks.float() - 0.25, ids, top                                               # chosen id's logprob: -(token + 1/4)
-
+    no_cuda_sync(monkeypatch)
+    K = ScriptedEngine.K              # its logprobs(): top-K ids token + 1 .. token + K at -(id + 1/2), the chosen id at -(token + 1/4)
     llm = FakeLLM()
-    llm.model.engine = eng = RulesEngine(64 * 16, 3, max_new=64)
+    llm.model.engine = eng = ScriptedEngine(64 * 16, 3, max_new=64, batch=False, sharing=False)
     prepare = llm._prepare
 
     def _prepare(inputs, sp):
@@ -265,8 +250,9 @@ def test_async_engine_carries_logprobs_and_releases_them(monkeypatch):
                 assert list(d) == [t + 1, t + 2, t + 3, t] and d[t] == -t - 0.25 and d[t + 1] == -(t + 1.5)
             assert o.cumulative_logprob == sum(-t - 0.25 for t in o.token_ids)
     assert n_c >= 1
-    assert {tuple(x[1]) for x in eng.armed} >= {(1, 2, 3), (4, 5)} and all(x[2] == [] for x in eng.armed)
-    assert all(x[3] == dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.5, logprobs=K) for x in eng.armed[:2])
+    armed = [(s, list(prompt), list(out), kw) for _, s, prompt, out, kw in eng.trace("set_logit_rules")]
+    assert {tuple(x[1]) for x in armed} >= {(1, 2, 3), (4, 5)} and all(x[2] == [] for x in armed)
+    assert all(x[3] == dict(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.5, logprobs=K) for x in armed[:2])
     for _ in range(200):
         if not engine.batcher.has_work() and not eng.seqs:
             break

@@ -349,7 +349,7 @@ def test_recompute_preemption_keeps_ids_and_logprobs(dev):
             for rid, new, finished, reason in bt.step():
                 got.setdefault(rid, []).extend(new)
             for r in bt.waiting:                      # a preempted request waits with base = tokens it had generated
-                first_cut.setdefault(r["id"], r["base"])
+                first_cut.setdefault(r.id, r.base)
         assert all(len(got[i]) == n_new for i in range(2)), {i: len(v) for i, v in got.items()}
         runs.append((got, bt.stats["preemptions"], {i: list(bt.logprobs[i]) for i in range(2)}, first_cut))
         eng.close()

@@ -1,36 +1,30 @@
-"""ContinuousBatcher's grouped prefill (vita_amd/serving.py) on a scripted engine, without a GPU: the admitted requests of a step
+"""ContinuousBatcher's grouped prefill (vita_amd/scheduler.py) on the scripted engine, without a GPU: the admitted requests of a step
 are prefilled in groups of up to max_prefill rows, a group of two or more through ONE seq_prefill_batch call; admission itself
 (FIFO order, slot and page rules) is what it was, with the pages promised to a group counted until its call has run.  The engine
-model is tests/test_scheduler_cpu.py's (a sequence's next token is a pure function of the tokens it has consumed) plus a
-seq_prefill_batch that checks the whole call before it touches anything, as the C entry point does."""
+model is tests/scripted_engine.py's (a sequence's next token is a pure function of the tokens it has consumed), whose
+seq_prefill_batch checks the whole call before it touches anything, as the C entry point does."""
 import ctypes as C
 
 import pytest
 import torch
 
-from tests.test_scheduler_cpu import FakeEngine, _drain, _emb, _expected
+from tests.scripted_engine import ScriptedEngine, _drain, _emb, _expected, no_cuda_sync
 
 
-class BatchEngine(FakeEngine):
-    def seq_prefill_batch(self, seqs, embs):
-        lens = [int(e.shape[0]) for e in embs]
-        if len(set(seqs)) != len(seqs) or sum(lens) > self.max_prefill:
-            raise RuntimeError("batch rejected")
-        need = sum(-(-(len(self.seqs[s]["hist"]) + n) // 64) - self.seqs[s]["pages"] for s, n in zip(seqs, lens))
-        if need > self.free:
-            raise RuntimeError("KV pool exhausted")                      # nothing was touched
-        for s, e in zip(seqs, embs):
-            q = self.seqs[s]
-            ids = e.argmax(dim=1).tolist()
-            self._grow(q, len(q["hist"]) + len(ids))
-            q["hist"] += ids
-            q["toks"] = [self._next(q["hist"])]
-        self.calls.append(("prefill_batch", tuple(seqs), tuple(lens)))
+class BatchEngine(ScriptedEngine):
+    """with seq_prefill_batch, without the shared-page entries"""
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, sharing=False, **kw)
+
+
+def _prefills(eng):
+    return eng.trace("prefill", "prefill_batch", "rejected")
 
 
 @pytest.fixture(autouse=True)
 def _no_cuda_sync(monkeypatch):
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: type("S", (), {"synchronize": lambda self: None})())
+    no_cuda_sync(monkeypatch)
 
 
 def _drain_after(first_events, bt):
@@ -56,7 +50,7 @@ def test_admitted_requests_are_prefilled_in_groups():
     for i, p in enumerate(prompts):
         bt.add(i, _emb(p), max_tokens=6 + i)
     ev = bt.step()
-    first = [c for c in eng.calls if c[0] != "decode"]
+    first = _prefills(eng)
     # four slots: four requests admitted in the first step, (40, 97, 64) in ONE call (201 rows; 130 more would pass 256), 130 alone
     assert first == [("prefill_batch", (0, 1, 2), (40, 97, 64)), ("prefill", 3, 130)], first
     assert bt.stats["prefills"] == 4 and bt.stats["prefill_calls"] == 2 and len(bt.running) == 4
@@ -64,7 +58,7 @@ def test_admitted_requests_are_prefilled_in_groups():
     for i, p in enumerate(prompts):
         assert got[i] == _expected(p, 6 + i), i
     assert bt.stats["prefills"] == 5 and bt.stats["prefill_calls"] == 3 and bt.stats["failed"] == 0
-    assert [c for c in eng.calls if c[0] != "decode"][2][0] == "prefill" and eng.free == 64 and not eng.seqs
+    assert _prefills(eng)[2][0] == "prefill" and eng.free == 64 and not eng.seqs
 
 
 def test_pages_promised_to_the_group_are_counted():
@@ -76,7 +70,7 @@ def test_pages_promised_to_the_group_are_counted():
     for i, p in enumerate(prompts):
         bt.add(i, _emb(p), max_tokens=4)
     ev = bt.step()
-    assert [c for c in eng.calls if c[0] != "decode"] == [("prefill_batch", (0, 1), (120, 120))]
+    assert _prefills(eng) == [("prefill_batch", (0, 1), (120, 120))]
     assert len(bt.running) == 2 and len(bt.waiting) == 1 and not any(e[3] == "error" for e in ev)
     got, fin = _drain_after(ev, bt)
     assert fin == {0: "length", 1: "length", 2: "length"} and bt.stats["failed"] == 0
@@ -117,7 +111,7 @@ def test_a_rejected_group_is_retried_request_by_request():
     assert fin == {"ok1": "length", "bad": "error", "ok2": "length"}
     assert sum(1 for e in events if e[3] == "error") == 1
     assert got["ok1"] == _expected([1, 2, 3], 5) and got["ok2"] == _expected([4, 5], 5) and got["bad"] == []
-    assert eng.calls[:3] == [("rejected", (0, 1, 2)), ("prefill", 0, 3), ("prefill", 2, 2)], eng.calls[:3]
+    assert _prefills(eng)[:3] == [("rejected", (0, 1, 2)), ("prefill", 0, 3), ("prefill", 2, 2)], _prefills(eng)[:3]
     assert isinstance(bt.errors.pop("bad"), RuntimeError) and bt.stats["failed"] == 1 and bt.stats["prefills"] == 2
     assert eng.free == 8 and not eng.seqs
 
@@ -125,7 +119,7 @@ def test_a_rejected_group_is_retried_request_by_request():
 def test_recompute_longer_than_max_prefill_still_goes_in_chunks():
     from vita_amd.serving import ContinuousBatcher
     eng = BatchEngine(pool_tokens=64 * 4, max_seqs=2, max_new=100, max_prefill=64)
-    table = torch.eye(FakeEngine.V)
+    table = torch.eye(ScriptedEngine.V)
     bt = ContinuousBatcher(eng, embed_tokens=lambda ids: table[ids], window=4)
     pa, pb = list(range(1, 61)), list(range(20, 82))[:60]
     bt.add("a", _emb(pa), max_tokens=90)

@@ -1,17 +1,18 @@
 """Prefix caching without a GPU: the digest restatement (tests/prefix_ref.py) and its chain, and PrefixCache + ContinuousBatcher
-(vita_amd/serving.py) over a scripted engine with reference-counted pages.  The engine model keeps what was WRITTEN in its pages and
-computes a sequence's next token from what its page table reads back, so a wrong page in a table, a page evicted while in use or a
-row written into a shared page shows as a wrong id (or trips the model's own assertion)."""
+(vita_amd/scheduler.py) over the scripted engine with reference-counted pages (tests/scripted_engine.py).  The engine model keeps what
+was WRITTEN in its pages and computes a sequence's next token from what its page table reads back, so a wrong page in a table, a page
+evicted while in use or a row written into a shared page shows as a wrong id (or trips the model's own assertion)."""
 import os
 import sys
 
 import numpy as np
 import pytest
-import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from tests import prefix_ref  # noqa: E402
+from tests.scripted_engine import ScriptedEngine as RefEngine, _drain, _emb, _expected, _ids, no_cuda_sync  # noqa: E402
+from tests.scripted_engine import embed_tokens as _embed_tokens  # noqa: E402
 
 
 # ---- 1. the digest and the chain ------------------------------------------------------------------------------------------------
@@ -77,187 +78,19 @@ def test_product_chain_is_the_restatement():
     assert serving.chain_keys(db[1:], x.shape[1], parent=prefix_ref.chain(db[:1], x.shape[1])[0]) == prefix_ref.chain(db, x.shape[1])[1:]
 
 
-# ---- 2. PrefixCache and the batcher over a scripted engine with reference counts -------------------------------------------------
-class _Cfg:
-    def __init__(self, max_seqs):
-        self.max_seqs = max_seqs
-
-
-class RefEngine:
-    """seq_* surface of MixtralEngine with the shared-page entries: a free-list stack, a count per page, the ids written per page."""
-    V = 97
-
-    def __init__(self, pool_tokens, max_seqs, max_new=64, max_prefill=512):
-        self.c = _Cfg(max_seqs)
-        self.max_ctx, self.max_new, self.max_prefill = pool_tokens, max_new, max_prefill
-        self.n_pages = pool_tokens // 64
-        self.free = list(range(self.n_pages - 1, -1, -1))
-        self.refs = [0] * self.n_pages
-        self.data = [[None] * 64 for _ in range(self.n_pages)]
-        self.seqs = {}
-        self.calls = []
-
-    @staticmethod
-    def _next(hist):
-        h = 7
-        for t in hist:
-            h = (h * 31 + int(t) + 3) % 1000003
-        return h % RefEngine.V
-
-    def pages_free(self):
-        assert len(self.free) == sum(1 for r in self.refs if r == 0)
-        return len(self.free)
-
-    def page_refs(self, pg):
-        return self.refs[pg] if 0 <= pg < self.n_pages else -1
-
-    def _unref(self, pg):
-        assert self.refs[pg] >= 1
-        self.refs[pg] -= 1
-        if self.refs[pg] == 0:
-            self.free.append(pg)
-
-    def seq_alloc(self):
-        for s in range(self.c.max_seqs):
-            if s not in self.seqs:
-                self.seqs[s] = dict(pos=0, toks=[], pages=[])
-                self.calls.append(("alloc", s))
-                return s
-        raise RuntimeError("no slot")
-
-    def seq_free(self, s):
-        for pg in reversed(self.seqs.pop(s)["pages"]):
-            self._unref(pg)
-        self.calls.append(("free", s))
-
-    def _hist(self, q):
-        h = [self.data[q["pages"][p // 64]][p % 64] for p in range(q["pos"])]
-        assert None not in h, "a sequence reads a row nobody wrote"
-        return h
-
-    def _write(self, q, ids):
-        need = -(-(q["pos"] + len(ids)) // 64) - len(q["pages"])
-        if need > len(self.free):
-            raise RuntimeError("KV pool exhausted")
-        for _ in range(need):
-            pg = self.free.pop()
-            self.refs[pg] = 1
-            self.data[pg] = [None] * 64
-            q["pages"].append(pg)
-        for t in ids:
-            pg = q["pages"][q["pos"] // 64]
-            assert self.refs[pg] == 1, "the engine writes a row of a page whose count is above 1"
-            self.data[pg][q["pos"] % 64] = int(t)
-            q["pos"] += 1
-
-    def seq_prefill(self, s, emb):
-        q = self.seqs[s]
-        self._write(q, emb.argmax(dim=1).tolist())                # rows are one-hot ids
-        q["toks"] = [self._next(self._hist(q))]
-        self.calls.append(("prefill", s, int(emb.shape[0])))
-
-    def seq_prefill_batch(self, seqs, embs):
-        need = sum(-(-(self.seqs[s]["pos"] + int(e.shape[0])) // 64) - len(self.seqs[s]["pages"]) for s, e in zip(seqs, embs))
-        if need > len(self.free) or sum(int(e.shape[0]) for e in embs) > self.max_prefill:
-            raise RuntimeError("rejected as a whole")
-        for s, e in zip(seqs, embs):
-            q = self.seqs[s]
-            self._write(q, e.argmax(dim=1).tolist())
-            q["toks"] = [self._next(self._hist(q))]
-        self.calls.append(("prefill_batch", tuple(seqs), tuple(int(e.shape[0]) for e in embs)))
-
-    def seq_decode(self, seqs):
-        for s in seqs:
-            q = self.seqs[s]
-            self._write(q, [q["toks"][-1]])
-            q["toks"].append(self._next(self._hist(q)))
-        self.calls.append(("decode", tuple(seqs)))
-
-    def seq_pos(self, s):
-        return self.seqs[s]["pos"]
-
-    def seq_pages(self, s):
-        return list(self.seqs[s]["pages"])
-
-    def seq_tokens(self, s):
-        return torch.tensor(self.seqs[s]["toks"] + [0] * (self.max_new - len(self.seqs[s]["toks"])))
-
-    def seq_counters(self, s):
-        return torch.tensor([self.seqs[s]["pos"], len(self.seqs[s]["toks"]), 0, 0])
-
-    def check_device_flag(self, c):
-        return c
-
-    # ---- shared pages
-    def seq_hold_prefix(self, s, n):
-        q = self.seqs[s]
-        assert 1 <= n and 64 * n <= q["pos"], "hold past the position"
-        for pg in q["pages"][:n]:
-            self.refs[pg] += 1
-        self.calls.append(("hold", s, n))
-        return list(q["pages"][:n])
-
-    def pages_release(self, pages):
-        for pg in set(pages):
-            assert self.refs[pg] >= pages.count(pg) >= 1, "release of a page that is not held"
-        for pg in reversed(pages):
-            self._unref(pg)
-        self.calls.append(("release", tuple(pages)))
-
-    def seq_adopt(self, s, pages):
-        q = self.seqs[s]
-        assert q["pos"] == 0 and not q["pages"] and len(set(pages)) == len(pages) >= 1
-        assert all(self.refs[pg] >= 1 for pg in pages), "adopting a free page"
-        for pg in pages:
-            self.refs[pg] += 1
-        q["pages"], q["pos"] = list(pages), 64 * len(pages)
-        self.calls.append(("adopt", s, tuple(pages)))
-
-
+# ---- 2. PrefixCache and the batcher over the scripted engine ---------------------------------------------------------------------
 @pytest.fixture(autouse=True)
 def _no_cuda_sync(monkeypatch):
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: type("S", (), {"synchronize": lambda self: None})())
-
-
-def _emb(ids):
-    return torch.nn.functional.one_hot(torch.tensor(ids), RefEngine.V).float()
-
-
-def _embed_tokens(ids):
-    return torch.nn.functional.one_hot(ids, RefEngine.V).float()
+    no_cuda_sync(monkeypatch)
 
 
 def _digests(rows):
     return prefix_ref.digest_bytes(rows.numpy())
 
 
-def _expected(ids, n):
-    hist, out = list(ids), []
-    for _ in range(n):
-        out.append(RefEngine._next(hist))
-        hist.append(out[-1])
-    return out
-
-
 def _batcher(eng, **kw):
     from vita_amd.serving import ContinuousBatcher, PrefixCache
     return ContinuousBatcher(eng, embed_tokens=_embed_tokens, prefix_cache=PrefixCache(eng, digests=_digests), **kw)
-
-
-def _drain(bt, limit=10000):
-    got, fin = {}, {}
-    for _ in range(limit):
-        if not bt.has_work():
-            return got, fin
-        for rid, new, finished, reason in bt.step():
-            got.setdefault(rid, []).extend(new)
-            if finished:
-                fin[rid] = reason
-    raise AssertionError("scheduler did not terminate")
-
-
-def _ids(seed, n):
-    return np.random.default_rng(seed).integers(1, RefEngine.V, size=n).tolist()
 
 
 def _run(bt, rid, ids, n):
@@ -327,9 +160,9 @@ def _eviction_stream():
     _run(bt, "A", _ids(10, 128), 2)
     _run(bt, "B", _ids(11, 64), 2)
     assert len(bt.cache.entries) == 3 and eng.pages_free() == 1
-    a_root, a_leaf, b_root = (e[0] for e in sorted(bt.cache.entries.values(), key=lambda e: (e[3], e[2] == 0)))
+    a_root, a_leaf, b_root = (e.page for e in sorted(bt.cache.entries.values(), key=lambda e: (e.tick, e.children == 0)))
     _run(bt, "x", _ids(21, 63), 70)                          # 63 + 69 rows: two evictions, then its own two full pages are cached
-    x_root, x_leaf = (e[0] for e in sorted((e for e in bt.cache.entries.values() if e[3] == 3), key=lambda e: e[2] == 0))
+    x_root, x_leaf = (e.page for e in sorted((e for e in bt.cache.entries.values() if e.tick == 3), key=lambda e: e.children == 0))
     _run(bt, "y", _ids(22, 63), 70)
     released = [c[1][0] for c in eng.calls if c[0] == "release" and len(c[1]) == 1]
     return (a_root, a_leaf, b_root, x_root, x_leaf), released, eng.calls, dict(bt.stats)
@@ -369,7 +202,7 @@ def test_admission_never_evicts_the_pages_it_is_about_to_adopt():
     # the probe hits the three OLDEST entries and needs 5 - 3 + 0 = 2 pages: one eviction, which must take the other chain's leaf
     p = base + _ids(52, 100)
     n_calls = len(eng.calls)
-    warm_pages = [bt.cache.entries[k][0] for k in prefix_ref.keys(_emb(base).numpy())]
+    warm_pages = [bt.cache.entries[k].page for k in prefix_ref.keys(_emb(base).numpy())]
     hit, rows = _run(bt, "probe", p, 3)
     assert hit == 192 and rows == 100
     during = eng.calls[n_calls:]

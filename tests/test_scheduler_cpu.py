@@ -1,4 +1,4 @@
-"""ContinuousBatcher (vita_amd/serving.py) on a scripted engine: the scheduling decisions — FIFO admission under slot and
+"""ContinuousBatcher (vita_amd/scheduler.py) on the scripted engine (tests/scripted_engine.py): the scheduling decisions — FIFO admission under slot and
 page limits, one decode step per running sequence per iteration, eos / max_tokens, pages returned, abort, youngest-first
 recompute preemption — without a GPU.  The engine model: a sequence's next token is a pure function of the tokens it has
 consumed (prompt rows are one-hot ids), so a preempted and re-prefilled request must continue exactly where it was."""
@@ -11,108 +11,19 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-class _Cfg:
-    def __init__(self, max_seqs):
-        self.max_seqs = max_seqs
+from tests.scripted_engine import ScriptedEngine, _drain, _emb, _expected, no_cuda_sync  # noqa: E402
 
 
-class FakeEngine:
-    """seq_* surface of MixtralEngine: 64-token pages, per-sequence positions, tokens = f(history)."""
-    V = 97
+class FakeEngine(ScriptedEngine):
+    """the engine before grouped prefill and page sharing: no seq_prefill_batch, none of the shared-page entries"""
 
-    def __init__(self, pool_tokens, max_seqs, max_new=64, max_prefill=512):
-        self.c = _Cfg(max_seqs)
-        self.max_ctx, self.max_new, self.max_prefill = pool_tokens, max_new, max_prefill
-        self.free = pool_tokens // 64
-        self.seqs = {}
-        self.calls = []
-
-    @staticmethod
-    def _next(hist):
-        h = 7
-        for t in hist:
-            h = (h * 31 + int(t) + 3) % 1000003
-        return h % FakeEngine.V
-
-    def pages_free(self):
-        return self.free
-
-    def seq_alloc(self):
-        for s in range(self.c.max_seqs):
-            if s not in self.seqs:
-                self.seqs[s] = dict(hist=[], toks=[], pages=0)
-                return s
-        raise RuntimeError("no slot")
-
-    def seq_free(self, s):
-        self.free += self.seqs.pop(s)["pages"]
-
-    def _grow(self, q, n_tokens):
-        need = -(-n_tokens // 64) - q["pages"]
-        if need > self.free:
-            raise RuntimeError("KV pool exhausted")
-        self.free -= need
-        q["pages"] += need
-
-    def seq_prefill(self, s, emb):
-        q = self.seqs[s]
-        ids = emb.argmax(dim=1).tolist()                # rows are one-hot ids
-        self._grow(q, len(q["hist"]) + len(ids))
-        q["hist"] += ids
-        q["toks"] = [self._next(q["hist"])]
-        self.calls.append(("prefill", s, len(ids)))
-
-    def seq_decode(self, seqs):
-        for s in seqs:
-            q = self.seqs[s]
-            self._grow(q, len(q["hist"]) + 1)
-            q["hist"].append(q["toks"][-1])
-            q["toks"].append(self._next(q["hist"]))
-        self.calls.append(("decode", tuple(seqs)))
-
-    def seq_pos(self, s):
-        return len(self.seqs[s]["hist"])
-
-    def seq_pages(self, s):
-        return list(range(self.seqs[s]["pages"]))
-
-    def seq_tokens(self, s):
-        return torch.tensor(self.seqs[s]["toks"] + [0] * (self.max_new - len(self.seqs[s]["toks"])))
-
-    def seq_counters(self, s):
-        return torch.tensor([len(self.seqs[s]["hist"]), len(self.seqs[s]["toks"]), 0, 0])
-
-    def check_device_flag(self, c):
-        return c
-
-
-def _emb(ids):
-    return torch.nn.functional.one_hot(torch.tensor(ids), FakeEngine.V).float()
-
-
-def _expected(ids, n):
-    hist, out = list(ids), []
-    for _ in range(n):
-        out.append(FakeEngine._next(hist))
-        hist.append(out[-1])
-    return out
-
-
-def _drain(bt, limit=10000):
-    got, fin = {}, {}
-    for _ in range(limit):
-        if not bt.has_work():
-            return got, fin
-        for rid, new, finished, reason in bt.step():
-            got.setdefault(rid, []).extend(new)
-            if finished:
-                fin[rid] = reason
-    raise AssertionError("scheduler did not terminate")
+    def __init__(self, *a, **kw):
+        super().__init__(*a, batch=False, sharing=False, **kw)
 
 
 @pytest.fixture(autouse=True)
 def _no_cuda_sync(monkeypatch):
-    monkeypatch.setattr(torch.cuda, "current_stream", lambda *a, **k: type("S", (), {"synchronize": lambda self: None})())
+    no_cuda_sync(monkeypatch)
 
 
 def test_fifo_admission_slots_eos_and_length():
@@ -128,11 +39,12 @@ def test_fifo_admission_slots_eos_and_length():
     assert got[0] == exp[0] and got[1] == exp[1][:4] and got[3] == exp[3]
     assert got[2] == exp[2][:exp[2].index(eos2) + 1] and fin[2] == "stop" and fin[1] == "length"
     prefills = [c[1] for c in eng.calls if c[0] == "prefill"]
+    calls = eng.trace("prefill", "decode")
     assert len(prefills) == 4 and eng.free == 32 and not eng.seqs          # everything returned
     # never more than two sequences in one iteration, and requests 2 / 3 start only after a slot was freed
-    assert max(len(c[1]) for c in eng.calls if c[0] == "decode") == 2
-    first_decode_with = lambda n: next(i for i, c in enumerate(eng.calls) if c[0] == "decode" and len(c[1]) == n)
-    assert [c[0] for c in eng.calls[:2]] == ["prefill", "prefill"] and first_decode_with(2) == 2
+    assert max(len(c[1]) for c in calls if c[0] == "decode") == 2
+    first_decode_with = lambda n: next(i for i, c in enumerate(calls) if c[0] == "decode" and len(c[1]) == n)
+    assert [c[0] for c in calls[:2]] == ["prefill", "prefill"] and first_decode_with(2) == 2
 
 
 def test_abort_frees_pages_and_waiting_requests():

@@ -20,15 +20,15 @@ unseeded temperature <= 0.01 is greedy (the demo's setting) and unseeded samplin
 
 Concurrent requests (the interactive demo's AsyncLLMEngine, web_interactive_demo.py:126,315-328,942-951): the engine's
 KV cache is a pool of 64-token pages addressed through per-sequence block tables (vh_mixtral_seq_* in
-include/vita_hip.h); `ContinuousBatcher` is the iteration-level scheduler over it (admit -> prefill, one decode step for
-every running sequence per iteration, free on finish, preempt-by-recompute when the pool runs dry) and
+include/vita_hip.h); `ContinuousBatcher` (vita_amd/scheduler.py) is the iteration-level scheduler over it (admit -> prefill, one
+decode step for every running sequence per iteration, free on finish, preempt-by-recompute when the pool runs dry) and
 `AsyncLLMEngine.generate(inputs, sampling_params, request_id)` is the async iterator the demo consumes.  `LLM.generate`
 (the offline demo) keeps serving one request at a time on the same engine."""
 import asyncio
-import collections
-import hashlib
+import contextlib
 import json
 import os
+import queue
 import threading
 from dataclasses import dataclass, field
 from typing import List, Optional
@@ -37,6 +37,7 @@ import torch
 
 from .host.constants import AUDIO_TOKEN_INDEX, IMAGE_TOKEN_INDEX
 from .host.image_processing import dynamic_preprocess
+from .scheduler import PREFIX_ROOT_KEY, ContinuousBatcher, PrefixCache, Request, chain_keys, device_digests   # noqa: F401  (re-exported)
 
 
 @dataclass
@@ -195,7 +196,6 @@ class LLM:
         if world > 1:
             kw.update(rank=int(os.environ.get("RANK", "0")), world=world)
             device = f"cuda:{int(os.environ.get('LOCAL_RANK', '0'))}"
-        if world > 1:
             torch.cuda.set_device(torch.device(device))       # kernels launch on the CURRENT device's stream
         self.tokenizer, self.model, self.image_processor, _ = load_pretrained_model(
             model, None, os.path.basename(str(model).rstrip("/")), "mixtral-8x7b", device=device,
@@ -259,13 +259,13 @@ class LLM:
         normalized = False
         if audios:
             if len(audios) > 1:
-                T = max(int(a.shape[0]) for a in audios)
-                feats = torch.zeros((len(audios), T, audios[0].shape[1]))
+                T = max(len(a) for a in audios)
+                feats = torch.zeros((len(audios), T, audios[0].size(1)))
                 for i, a in enumerate(audios):
-                    feats[i, :a.shape[0]] = a.float()
+                    feats[i, :len(a)] = a.float()
             else:
                 feats = audios[0].float()[None]
-            lens = torch.tensor([int(a.shape[0]) for a in audios])
+            lens = torch.tensor([len(a) for a in audios])
             normalized = True                # WhaleFeatureExtractor already applied CMVN
         else:
             feats, lens = torch.zeros((1, 400, enc.acfg.input_dim)), torch.tensor([400])
@@ -279,25 +279,31 @@ class LLM:
                                  f"(this engine: max_logprobs={eng.c.max_logprobs}, penalty_tables={bool(eng.c.penalty_tables)})")
             # the prompt set of the penalties: the ids vLLM sees as prompt_token_ids (placeholders widened); ids that are not rows
             # of the LM head can never be generated and are left out
-            frames = [int(a.shape[0]) for a in audios]
+            frames = [len(a) for a in audios]
             exp = expanded_token_ids(sent, frames, image_token_index=self.image_token_index, audio_token_index=self.audio_token_index)
             V = int(self.model.config.vocab_size)
             prompt_set = sorted({t for t in exp if 0 <= t < V})
         return dict(ids=ids, sent=sent, pix=pix, feats=feats.to(dev), lens=lens.to(dev), normalized=normalized,
                     max_tokens=max_tokens, eos=eos, rules=rules, prompt_set=prompt_set)
 
+    @contextlib.contextmanager
+    def _audio_input(self, normalized):
+        """the audio encoder reads a prepared request's features as they are: CMVN-normalised already, or raw"""
+        enc = self.model.get_audio_encoder()
+        enc.normalized_input = normalized
+        try:
+            yield
+        finally:
+            enc.normalized_input = False
+
     @torch.no_grad()
     def _embed(self, req):
         """encoders + splice of a prepared request -> inputs_embeds [S, H] fp32 on the device."""
-        enc = self.model.get_audio_encoder()
-        enc.normalized_input = req["normalized"]
-        try:
-            dev = self.model.device
+        dev = self.model.device
+        with self._audio_input(req["normalized"]):
             out = self.model.prepare_inputs_labels_for_multimodal(
                 torch.tensor([req["sent"]], dtype=torch.long, device=dev), None, None, None, None, req["pix"],
                 {"audios": req["feats"], "lengths": req["lens"]}, audio_valid_rows=True)
-        finally:
-            enc.normalized_input = False
         return out[4][0].to(torch.float32)
 
     @torch.no_grad()
@@ -305,20 +311,16 @@ class LLM:
         req = self._prepare(inp, sp)
         ids, sent, pix, feats, lens, max_tokens = (req[k] for k in ("ids", "sent", "pix", "feats", "lens", "max_tokens"))
         dev = self.model.device
-        enc = self.model.get_audio_encoder()
-        enc.normalized_input = req["normalized"]
         rules = req.get("rules")
         rkw = {} if rules is None else dict(repetition_penalty=rules["repetition_penalty"], presence_penalty=rules["presence_penalty"],
                                              frequency_penalty=rules["frequency_penalty"], penalty_prompt_ids=req["prompt_set"],
                                              output_logprobs=rules["logprobs"] if rules["logprobs"] >= 0 else None)
-        try:
+        with self._audio_input(req["normalized"]):
             out = self.model.generate(torch.tensor([sent], dtype=torch.long, device=dev), images=pix,
                                       audios={"audios": feats.to(dev), "lengths": lens.to(dev)}, num_beams=1,
                                       return_dict_in_generate=True, max_new_tokens=max_tokens,
                                       eos_token_id=list(req["eos"]), streamer=streamer, audio_valid_rows=True,
                                       **sample_kwargs(sp), **rkw)
-        finally:
-            enc.normalized_input = False
         gen = out.sequences[0, len(sent):].tolist()
         eos = req["eos"]
         reason = "stop" if gen and gen[-1] in eos else "length"
@@ -332,8 +334,6 @@ class LLM:
         """Generator of RequestOutput with the CUMULATIVE text after every decode window — the shape of
         AsyncLLMEngine.generate's async iterator as web_interactive_demo.py:315-328 consumes it.  `should_stop()`
         is polled between windows; returning True interrupts the request (the duplex monitor hand-off)."""
-        import queue
-        import threading
         sp = sampling_params or SamplingParams()
         q = queue.Queue()
         state = {"toks": [], "abandoned": False}
@@ -378,486 +378,6 @@ class LLM:
         sp = sampling_params or SamplingParams()
         batch = prompts if isinstance(prompts, list) else [prompts]
         return [self._one(p, sp) for p in batch]
-
-
-# ---- prefix caching: KV pages of earlier prompts, found again by content -----------------------------------------------------
-PREFIX_ROOT_KEY = hashlib.blake2b(b"vita_amd prefix cache v1", digest_size=16).digest()      # key_{-1} of every chain
-
-
-def chain_keys(digests, cols, parent=PREFIX_ROOT_KEY):
-    """digests: the 16-byte content digests of consecutive 64-row blocks (vh_hash_row_blocks) -> their chain keys
-    key_b = blake2b(key_{b-1} || digest_b || cols as 8 little-endian bytes, digest_size=16): a key names the WHOLE prefix up to and
-    including its block, for rows of that width."""
-    keys, tail = [], int(cols).to_bytes(8, "little")
-    for d in digests:
-        parent = hashlib.blake2b(parent + bytes(d) + tail, digest_size=16).digest()
-        keys.append(parent)
-    return keys
-
-
-def device_digests(rows):
-    """fp32 [n, H] device rows -> the digests of its complete 64-row blocks as 16-byte strings: ONE vh_hash_row_blocks launch and one
-    small device-to-host copy, which waits for the stream — the only synchronisation prefix caching adds."""
-    from . import ops
-    if int(rows.shape[0]) < 64:
-        return []
-    words = ops.hash_row_blocks(rows).cpu().numpy()
-    return [words[b].tobytes() for b in range(words.shape[0])]
-
-
-class PrefixCache:
-    """Store of the prefix cache (vLLM's enable_prefix_caching over this engine's pages): chain key -> [page, parent key, children,
-    last-use tick].  Every entry owns ONE hold of its page (MixtralEngine.seq_hold_prefix), so the page outlives the sequence that
-    wrote it; a sequence that adopts it (seq_adopt) adds its own count.  The entries form a forest closed under `parent`: a block is
-    cached only together with the whole prefix in front of it.
-
-    Nothing here looks at a clock or iterates a dict of unequal things in hash order: `tick` is a counter the batcher bumps per
-    admitted request, eviction orders by (tick, key).  Tensor-parallel ranks fed the same requests reach the same decisions.
-
-    Eviction: only entries whose page has page_refs == 1 (the cache's hold alone), unpinned and without children; least recently
-    used first; exactly as many as asked for.
-
-    The device digest is a content hash, not a cryptographic one (include/vita_hip.h vh_hash_row_blocks): a miss is always safe, a
-    false hit would not be, which is why the cache is opt-in."""
-
-    def __init__(self, engine, digests=None):
-        self.eng = engine
-        self.digests = digests or device_digests
-        self.entries = {}
-        self.pinned = set()               # pages a request of the current admission pass is about to adopt
-        self.tick = 0
-        self.evictions = 0
-
-    def keys_after(self, keys, rows):
-        """keys of the complete blocks of `rows`, which continue the prefix whose keys are `keys`."""
-        return chain_keys(self.digests(rows), int(rows.shape[1]), keys[-1] if keys else PREFIX_ROOT_KEY)
-
-    def match(self, keys, limit):
-        """-> pages of the longest cached chain among the first `limit` keys; the chain is touched."""
-        pages = []
-        for k in keys[:max(int(limit), 0)]:
-            e = self.entries.get(k)
-            if e is None:
-                break
-            e[3] = self.tick
-            pages.append(e[0])
-        return pages
-
-    def insert(self, key, parent, page):
-        """`page` (already held once for the cache) under `key`; parent: the key in front of it, None for block 0."""
-        self.entries[key] = [int(page), parent, 0, self.tick]
-        if parent is not None:
-            self.entries[parent][2] += 1
-
-    def _idle(self, e):
-        return e[0] not in self.pinned and self.eng.page_refs(e[0]) == 1
-
-    def evictable(self):
-        """entries evict() could remove: idle ones all of whose descendants are idle."""
-        blocked = set()
-        for k, e in self.entries.items():
-            if not self._idle(e):
-                while k is not None and k not in blocked:
-                    blocked.add(k)
-                    k = self.entries[k][1]
-        return len(self.entries) - len(blocked)
-
-    def evict(self, n):
-        """give up to n pages back to the pool -> how many."""
-        done = 0
-        while done < n:
-            # the least recently used childless idle entry, ties by key; a chain shares one tick and only its leaf is childless: the
-            # parent becomes a candidate when the leaf is gone
-            leaves = sorted((e[3], k) for k, e in self.entries.items() if e[2] == 0)
-            k = next((k for _, k in leaves if self._idle(self.entries[k])), None)
-            if k is None:
-                break
-            page, parent = self.entries.pop(k)[:2]
-            if parent is not None:
-                self.entries[parent][2] -= 1
-            self.eng.pages_release([page])
-            done += 1
-        self.evictions += done
-        return done
-
-    def clear(self):
-        """drop every entry and its hold (pages a running sequence adopted stay that sequence's until it ends)."""
-        pages = sorted(e[0] for e in self.entries.values())
-        self.entries.clear()
-        self.pinned.clear()
-        if pages:
-            self.eng.pages_release(pages)
-
-
-# ---- concurrent requests: iteration-level scheduling over the paged KV cache -------------------------------------------
-class ContinuousBatcher:
-    """The scheduler half of vLLM's engine for this path (what drives the plugin's forward with `kv_caches` +
-    `attn_metadata`, vllm_file/mixtral.py:1130-1186), over `MixtralEngine.seq_*`:
-
-      add(request_id, embeds, max_tokens, eos)   queue a request (FIFO)
-      step() -> [(request_id, new_token_ids, finished, finish_reason)]   one iteration:
-          1. admit waiting requests while a sequence slot is free and the pool holds the prompt's pages plus one page of
-             headroom per running sequence; the admitted prompts are then prefilled in groups of up to max_prefill rows, a
-             group of two or more in ONE pass over the weights (seq_prefill_batch: vLLM's max_num_batched_tokens), a
-             group of one — or a re-prompt longer than max_prefill, in chunks — by seq_prefill;
-          2. if the running sequences need more new pages than the pool has, preempt the youngest ones (free their pages,
-             re-queue them at the front with prompt + generated tokens as the new prompt: vLLM's recompute preemption);
-          3. `window` greedy decode steps for every running sequence (one C call per step), ONE host synchronisation,
-             then eos / max_tokens per sequence; finished sequences return their pages.
-      abort(request_id)
-
-    A sequence's ids do not depend on what else is scheduled (same kernels, same arithmetic per sequence); tokens decoded
-    past an eos inside a window are discarded, as MixtralEngine's single-request lookahead does.
-
-    prefix_cache=True (or a PrefixCache): vLLM's enable_prefix_caching.  On admission the prompt's 64-row blocks are keyed by content
-    (one vh_hash_row_blocks launch + one small device-to-host copy per admitted request: the only synchronisation the feature adds);
-    the longest cached chain, at most (S - 1) // 64 pages since one row must be prefilled for the first token's logits, is adopted
-    (seq_alloc, seq_adopt) and only emb[64 * hit:] is prefilled, as a member of the admission group like any other prompt (it counts
-    S - 64 * hit rows against max_prefill).  Right after a request's prefill is enqueued its full prompt pages that are not cached yet
-    are held and inserted — everything runs on one stream, so an adopter's kernels are ordered after the writer's; two requests of
-    the SAME admission group therefore do not share.  With an embed_tokens hook, a request that finishes, is aborted or is preempted
-    also registers its pages that lie entirely below its position, the ones filled by generated tokens included (keys continue the
-    chain over cat(open block's prompt rows, embed_tokens(out[:-1]))): a follow-up turn that repeats prompt + response finds them,
-    and a preempted request finds its own pages.  Pool accounting is "free + evictable - promised"; cached pages are evicted
-    (childless first, least recently used first, exactly as many as needed) before any running sequence is preempted.
-    stats: prefix_queries (lookups), prefix_hit_tokens, prefix_evictions, prefill_rows (rows sent to prefill calls, counted with the
-    cache off as well); cached_tokens[request id] is the hit of a request's first admission (the caller pops it)."""
-
-    def __init__(self, engine, embed_tokens=None, max_batch=None, window=1, prefix_cache=False):
-        self.eng, self.embed_tokens = engine, embed_tokens
-        self.cache = prefix_cache if isinstance(prefix_cache, PrefixCache) else (PrefixCache(engine) if prefix_cache else None)
-        self.cached_tokens = {}
-        self.max_batch = int(max_batch or engine.c.max_seqs)
-        if engine.c.max_seqs < 1:
-            raise ValueError("the engine was created without sequence slots (max_seqs = 0)")
-        self.window = int(window)
-        self.waiting = collections.deque()
-        self.running = []                 # admission order
-        self.errors = {}                  # request id -> exception of a request that failed alone (event reason "error")
-        self.stats = {"iterations": 0, "prefills": 0, "prefill_calls": 0, "preemptions": 0, "decode_steps": 0, "failed": 0,
-                      "prefix_queries": 0, "prefix_hit_tokens": 0, "prefix_evictions": 0, "prefill_rows": 0}
-        self.logprobs = {}                # request id -> per-token {id: logprob} of requests with rules["logprobs"] >= 0; the entry of a
-                                          # finished request stays until the caller pops it (a failed or aborted one is dropped here)
-
-    def add(self, request_id, embeds, max_tokens, eos=(), sampling=None, rules=None, prompt_ids=None):
-        """sampling: None (greedy) or the keywords of MixtralEngine.seq_set_sampling without draw0 (see sampling_of).
-        rules: None or the keywords of MixtralEngine.seq_set_logit_rules without the ids (see rules_of); prompt_ids: the prompt set
-        of the penalties.  The rules are re-armed with prompt and output ids after a recompute preemption, and the logprobs of a
-        request (self.logprobs[request_id]) run on across it."""
-        S = int(embeds.shape[0])
-        if S + 2 > self.eng.max_ctx or S > self.eng.max_prefill:
-            raise ValueError(f"prompt of {S} tokens exceeds the engine (max_prefill {self.eng.max_prefill}, pool "
-                             f"{self.eng.max_ctx} tokens)")
-        self.waiting.append(dict(id=request_id, emb=embeds, max_tokens=min(int(max_tokens), self.eng.max_new),
-                                 eos=set(eos), out=[], seq=None, base=0, sampling=sampling, rules=rules,
-                                 prompt_ids=list(prompt_ids or ())))
-        if rules is not None and rules.get("logprobs", -1) >= 0:
-            self.logprobs[request_id] = []
-
-    def abort(self, request_id):
-        self.logprobs.pop(request_id, None)
-        self.cached_tokens.pop(request_id, None)
-        for r in list(self.running):
-            if r["id"] == request_id:
-                self._register_written(r)
-                self.eng.seq_free(r["seq"])
-                self.running.remove(r)
-                return True
-        for r in list(self.waiting):
-            if r["id"] == request_id:
-                self.waiting.remove(r)
-                return True
-        return False
-
-    def has_work(self):
-        return bool(self.waiting or self.running)
-
-    def _pages(self, n_tokens):
-        return -(-int(n_tokens) // 64)
-
-    def _prefill(self, r):
-        """the prompt of a request — or, after a preemption, prompt + generated tokens, which may exceed what one prefill call
-        takes — in chunks of max_prefill (seq_prefill appends at the sequence's position)."""
-        emb, mp = self._suffix(r), int(self.eng.max_prefill)
-        for s0 in range(0, int(emb.shape[0]), mp):
-            if s0 > 0 and s0 + mp >= int(emb.shape[0]):
-                self._arm(r)                 # a chunked re-prompt: only the LAST chunk's token is an output (the table counts it)
-            self.eng.seq_prefill(r["seq"], emb[s0:s0 + mp])
-            self.stats["prefill_calls"] += 1
-            self.stats["prefill_rows"] += int(emb[s0:s0 + mp].shape[0])
-
-    def _suffix(self, r):
-        """the rows of r's prompt that are prefilled: all of them, or what lies behind the pages it adopted."""
-        hit = r.get("hit", 0)
-        return r["emb"][64 * hit:] if hit else r["emb"]
-
-    # ---- prefix cache ----------------------------------------------------------------------------------------------------------
-    def _lookup(self, r):
-        """keys of r's complete prompt blocks (hashed once per prompt; a re-prompt after a preemption only grew) -> the cached pages
-        r may adopt, pinned until the admission pass ends."""
-        c, S = self.cache, int(r["emb"].shape[0])
-        keys = r.setdefault("keys", [])
-        if len(keys) < S // 64:
-            keys += c.keys_after(keys, r["emb"][64 * len(keys):])
-        pages = c.match(keys, (S - 1) // 64)
-        c.pinned.update(pages)
-        return pages
-
-    def _register(self, r, n_full):
-        """hold r's first n_full pages for the cache, as far as their keys are not cached yet (those form the tail of the chain)."""
-        c, keys = self.cache, r["keys"]
-        new = [b for b in range(min(n_full, len(keys))) if keys[b] not in c.entries]
-        if not new:
-            return
-        pages = self.eng.seq_hold_prefix(r["seq"], new[-1] + 1)
-        if new[0] > 0:
-            self.eng.pages_release(pages[:new[0]])             # the hold covers the table's head: the cached part goes back
-        for b in new:
-            c.insert(keys[b], keys[b - 1] if b else None, pages[b])
-
-    def _register_written(self, r, rows=None):
-        """before r's sequence is freed: register its pages that lie entirely below its position, those filled by generated tokens
-        included.  rows: r's prompt + embed_tokens(its output), when the caller has built it anyway (preemption)."""
-        if self.cache is None or self.embed_tokens is None or r.get("seq") is None:
-            return
-        S, keys = int(r["emb"].shape[0]), r.setdefault("keys", [])
-        gen = r["out"][r["base"]:]
-        # K/V of position S + i is the row of generated token i; the last accepted token was never fed (or its row is discarded)
-        valid = min(self.eng.seq_pos(r["seq"]), S + max(len(gen) - 1, 0))
-        if valid // 64 > len(keys):
-            k0 = 64 * len(keys)
-            if rows is None:
-                tail = self.embed_tokens(torch.tensor(gen[:-1], dtype=torch.long, device=r["emb"].device)).to(torch.float32)
-                rows = torch.cat([r["emb"][k0:], tail], dim=0)
-            else:
-                rows = rows[k0:]
-            keys += self.cache.keys_after(keys, rows[:64 * (valid // 64) - k0])
-        self._register(r, valid // 64)
-
-    def _make_room(self, short):
-        """the pool is `short` pages short: evict that many cached pages if the cache can -> True when it could."""
-        if short <= 0:
-            return True
-        if self.cache is None or self.cache.evictable() < short:
-            return False
-        self.stats["prefix_evictions"] += self.cache.evict(short)
-        return True
-
-    def _arm(self, r):
-        """the logit rules of r's slot with its history: the prompt set, and every token generated so far as outputs."""
-        if r.get("rules") is not None:
-            self.eng.seq_set_logit_rules(r["seq"], prompt_ids=r["prompt_ids"], output_ids=r["out"], **r["rules"])
-
-    def _fail(self, r, exc, events):
-        """ONE request failed (its prompt does not fit, its prefill was rejected): it ends with an "error" event, nobody else
-        is touched.  Device-level failures (spin time-outs, launch errors seen at the synchronisation) still propagate."""
-        self.errors[r["id"]] = exc
-        self.logprobs.pop(r["id"], None)
-        self.cached_tokens.pop(r["id"], None)
-        self.stats["failed"] += 1
-        events.append((r["id"], [], True, "error"))
-
-    def _start(self, r, events, prefilled=False):
-        """r holds a slot: prefill it (unless a group call already did) and let it run; a failure ends r alone."""
-        if not prefilled:
-            try:
-                self._prefill(r)
-            except Exception as e:
-                self.eng.seq_free(r["seq"])
-                r["seq"] = None
-                self._fail(r, e, events)
-                return
-        r["fresh"] = True                    # its first token (tokens[0]) is not reported yet
-        self.running.append(r)
-        self.stats["prefills"] += 1
-        if self.cache is not None:           # the prefill is enqueued: its full prompt pages can be shared from here on
-            self._register(r, int(r["emb"].shape[0]) // 64)
-
-    def _prefill_group(self, group, events):
-        """the admitted requests of one group, in admission order: two or more in one pass over the weights.  A group call that
-        raises is retried request by request (a rejected call touched nothing; after a later failure seq_prefill starts again
-        at the sequence's unchanged position), so only the culprit ends with an "error" event."""
-        done = False
-        if len(group) >= 2:
-            try:
-                self.eng.seq_prefill_batch([r["seq"] for r in group], [self._suffix(r) for r in group])
-                self.stats["prefill_calls"] += 1
-                self.stats["prefill_rows"] += sum(int(self._suffix(r).shape[0]) for r in group)
-                done = True
-            except Exception:
-                done = False
-        for r in group:
-            self._start(r, events, prefilled=done)
-        group.clear()
-
-    def _admit(self):
-        events = []
-        mp = int(self.eng.max_prefill)
-        can_batch = hasattr(self.eng, "seq_prefill_batch")
-        group, rows = [], 0       # admitted (slot taken, pages promised), prefill deferred to the group's call
-        while self.waiting and len(self.running) + len(group) < self.max_batch:
-            r = self.waiting[0]
-            # the pool as it will be once the group is prefilled: the pages promised to its prompts are gone, its members run
-            # (pages a member adopted from the prefix cache are in its table already)
-            free = self.eng.pages_free() - sum(self._pages(g["emb"].shape[0]) - g.get("hit", 0) for g in group)
-            n_run = len(self.running) + len(group)
-            need = self._pages(r["emb"].shape[0] + 1) + n_run                   # + one page of headroom per runner
-            hit = []
-            if self.cache is not None:
-                self.cache.tick += 1
-                hit = self._lookup(r)
-                need -= len(hit)
-                if not self._make_room(need - free):        # free + evictable - promised; the pinned pages are not evictable
-                    self.cache.pinned.difference_update(hit)
-                else:
-                    free = max(free, need)
-            if need > free:
-                if n_run == 0:
-                    self.waiting.popleft()
-                    self._fail(r, RuntimeError(f"request {r['id']}: prompt needs {need} KV pages, the pool has "
-                                               f"{free}"), events)
-                    continue
-                break
-            self.waiting.popleft()
-            try:
-                r["seq"] = self.eng.seq_alloc()
-            except Exception as e:
-                self._fail(r, e, events)
-                continue
-            if self.cache is not None:
-                r["hit"] = len(hit)
-                self.stats["prefix_queries"] += 1
-                self.stats["prefix_hit_tokens"] += 64 * len(hit)
-                self.cached_tokens.setdefault(r["id"], 64 * len(hit))
-                if hit:
-                    try:
-                        self.eng.seq_adopt(r["seq"], hit)
-                    except Exception as e:
-                        self.eng.seq_free(r["seq"])
-                        r["seq"] = None
-                        self._fail(r, e, events)
-                        continue
-            if r["sampling"] is not None:
-                # draw index of the next token = tokens already generated (r["base"] after a recompute preemption): the
-                # continued ids are the ones an unpreempted run draws
-                try:
-                    self.eng.seq_set_sampling(r["seq"], draw0=r["base"], **r["sampling"])
-                except Exception as e:
-                    self.eng.seq_free(r["seq"])
-                    r["seq"] = None
-                    self._fail(r, e, events)
-                    continue
-            S = int(r["emb"].shape[0]) - 64 * r.get("hit", 0)     # the rows that are prefilled
-            if S <= mp:                          # (a chunked re-prompt arms its rules in front of its last chunk: _prefill)
-                try:
-                    self._arm(r)
-                except Exception as e:
-                    self.eng.seq_free(r["seq"])
-                    r["seq"] = None
-                    self._fail(r, e, events)
-                    continue
-            if not can_batch or S > mp:          # no batched entry point / a re-prompt that goes in chunks: alone, in order
-                self._prefill_group(group, events)
-                rows = 0
-                self._start(r, events)
-                continue
-            if rows + S > mp:                    # the next prompt would take the group's rows past max_prefill: close it
-                self._prefill_group(group, events)
-                rows = 0
-            group.append(r)
-            rows += S
-        self._prefill_group(group, events)
-        if self.cache is not None:
-            self.cache.pinned.clear()
-        return events
-
-    def _preempt_for(self, steps):
-        """make sure `steps` decode steps of every running sequence find their pages; youngest sequences yield."""
-        while True:
-            new_pages = sum(self._pages(self.eng.seq_pos(r["seq"]) + steps) - len(self.eng.seq_pages(r["seq"]))
-                            for r in self.running)
-            short = new_pages - self.eng.pages_free()
-            if short > 0 and self.cache is not None:              # cached pages yield before a running sequence does
-                self.stats["prefix_evictions"] += self.cache.evict(short)
-                short = new_pages - self.eng.pages_free()
-            if short <= 0 or len(self.running) <= 1:
-                return
-            r = self.running.pop()
-            keep = self.cache is not None and self.embed_tokens is not None   # register its written pages before they are freed
-            if not keep:
-                self.eng.seq_free(r["seq"])
-            if r["out"] and self.embed_tokens is None:
-                raise RuntimeError("KV pool exhausted and no embed_tokens hook to recompute a preempted sequence")
-            emb = r["emb"]
-            if r["out"][r["base"]:]:
-                tail = self.embed_tokens(torch.tensor(r["out"][r["base"]:], dtype=torch.long, device=r["emb"].device))
-                emb = torch.cat([r["emb"], tail.to(torch.float32)], dim=0)
-            if keep:                                              # its written pages stay findable: the re-prompt adopts them
-                self._register_written(r, rows=emb)
-                self.eng.seq_free(r["seq"])
-            r["emb"] = emb
-            r["base"], r["seq"] = len(r["out"]), None
-            self.waiting.appendleft(r)
-            self.stats["preemptions"] += 1
-
-    @torch.no_grad()
-    def step(self):
-        failed = self._admit()
-        if not self.running:
-            return failed
-        # decode window, bounded by every sequence's token buffer and by the pool's addressable context
-        steps = self.window
-        for r in self.running:
-            n_dev = len(r["out"]) - r["base"] + (1 if r.get("fresh") else 0)
-            steps = min(steps, self.eng.max_new - n_dev, self.eng.max_ctx - 2 - self.eng.seq_pos(r["seq"]))
-        steps = max(steps, 0)
-        starved = None
-        if steps > 0:
-            self._preempt_for(steps)
-            if len(self.running) == 1:
-                r = self.running[0]
-                if self._pages(self.eng.seq_pos(r["seq"]) + steps) - len(self.eng.seq_pages(r["seq"])) > self.eng.pages_free():
-                    starved, steps = r, 0                         # alone and the pool is dry: it ends here ("length")
-        if steps > 0:
-            ids = [r["seq"] for r in self.running]
-            for _ in range(steps):
-                self.eng.seq_decode(ids)
-            self.stats["decode_steps"] += steps * len(ids)
-        self.stats["iterations"] += 1
-        torch.cuda.current_stream().synchronize()
-        events = failed
-        for r in list(self.running):
-            cnt = self.eng.check_device_flag(self.eng.seq_counters(r["seq"]).tolist())
-            n_dev = min(cnt[1], self.eng.max_new)                 # tokens of this (re)prefill + its decode steps
-            have = len(r["out"]) - r["base"]
-            new = self.eng.seq_tokens(r["seq"])[have:n_dev].tolist()
-            new_lp = None
-            if r["id"] in self.logprobs and n_dev > have:
-                from .model.vita_mixtral import logprob_dicts
-                views = self.eng.logprobs(r["seq"])
-                new_lp = logprob_dicts(tuple(v[have:n_dev] for v in views), new, r["rules"]["logprobs"])
-            r["fresh"] = False
-            accepted, reason = [], None
-            for tok in new:
-                accepted.append(tok)
-                if tok in r["eos"]:
-                    reason = "stop"
-                elif len(r["out"]) + len(accepted) >= r["max_tokens"]:
-                    reason = "length"
-                if reason:
-                    break
-            r["out"] += accepted
-            if new_lp is not None:
-                self.logprobs[r["id"]] += new_lp[:len(accepted)]
-            if reason is None and (r is starved or self.eng.seq_pos(r["seq"]) + 2 >= self.eng.max_ctx):
-                reason = "length"                                 # the pool cannot hold another token of this sequence
-            if reason:
-                self._register_written(r)
-                self.eng.seq_free(r["seq"])
-                self.running.remove(r)
-            if accepted or reason:
-                events.append((r["id"], accepted, reason is not None, reason or ""))
-        return events
 
 
 @dataclass
@@ -972,10 +492,8 @@ class AsyncLLMEngine:
                 for rid in list(state):
                     self._post(rid, e)
                 state.clear()
-                self.batcher.waiting.clear()
-                self.batcher.logprobs.clear()
-                for r in list(self.batcher.running):
-                    self.batcher.abort(r["id"])
+                for r in (*self.batcher.running, *self.batcher.waiting):      # nothing of this iteration can be trusted
+                    self.batcher.abort(r.id)
                 continue
             for rid, new, finished, reason in events:
                 if rid not in state:
