@@ -106,6 +106,14 @@ int vh_split_planes(const float* x, long ldx, uint16_t* hi, uint16_t* lo, long l
  * resid, act or C_hi, ksplit < 0 without nslab_out, group_off with ngroups > 8, ldw * N >= 2^32. */
 int vh_gemm_ps_i8(const vh_gemm_ps_args* args, const int8_t* W, const float* s, const int8_t* W_up, const float* s_up,
                   long s_group_stride, void* stream);
+/* vh_gemm_ps on MXFP4 weights: args->W / W_up must be null; W (and W_up: GLU) are e2m1 codes, two per byte (element k
+ * of a row in byte k >> 1, low nibble for even k), S (and S_up) one E8M0 scale byte per 32 consecutive elements of a row; the
+ * weight is e2m1(code) * 2^(byte - 127), code 8 (-0) reads as 0.  args->ldw / w_group_stride count WEIGHTS: a code row is ldw / 2
+ * bytes, a scale row ldw / 32 bytes, a group w_group_stride / 2 and w_group_stride / 32 bytes.  The conversion to bf16 is exact, so
+ * the result is vh_gemm_ps's on the dequantised weights.  Always the 12-wave specialised kernel.  Refused with VH_E_SHAPE, before
+ * anything is launched or written: ldw % 64 != 0, w_group_stride % 64 != 0, ldw < K, and what vh_gemm_ps_i8 refuses. */
+int vh_gemm_ps_mxfp4(const vh_gemm_ps_args* args, const uint8_t* W, const uint8_t* S, const uint8_t* W_up, const uint8_t* S_up,
+                     void* stream);
 
 /* vh_attention: softmax(scale * Q K^T [+ (Q+v) P^T]) V with causal / pad / chunk masks.
  * Replaces InternAttention._naive_attn (modeling_intern_vit.py:158-177), Whale
@@ -292,6 +300,30 @@ vh_mixtral_t* vh_mixtral_create_i8(const vh_mixtral_cfg* cfg, const vh_mixtral_l
  * q int8 [rows][ld_dst] holding columns [col0, col0 + ncols) (a TP rank's slice of w2 with the full-row scale). */
 int vh_quant_rows_i8(const uint16_t* w, long rows, int cols, long ld_src, int col0, int ncols, int8_t* q, long ld_dst, float* s,
                      void* stream);
+/* MXFP4 experts (quantization="experts_mxfp4"): OCP MXFP4 along K, the contiguous dimension, in blocks of 32
+ * consecutive elements of a row.  amax = the block's largest |w|; se = max(floor(log2 amax) - 2, -125) (0 for a zero block); the
+ * E8M0 scale byte is se + 127; v = w / 2^se saturates at +-6 and rounds to the nearest of 0, .5, 1, 1.5, 2, 3, 4, 6 (ties to the
+ * even code); code = sign << 3 | index with the sign bit only for a non-zero magnitude.  The engine computes with
+ * w' = e2m1(code) * 2^(byte - 127), which is a bf16 number.  Codes are uint8 [rows][K / 2] (element k in byte k >> 1, low nibble for
+ * even k), scales uint8 [rows][K / 32].  A tensor-parallel rank's w2 column slice starts on a multiple of 32, so it stores the slice
+ * of the codes and of the scales and every TP degree computes the same w'.  Activations stay fp32. */
+typedef struct {
+    const uint8_t* w1; const uint8_t* s1;   /* [n_experts][inter][hidden / 2] codes, [n_experts][inter][hidden / 32] scales */
+    const uint8_t* w3; const uint8_t* s3;   /* as w1 / s1 */
+    const uint8_t* w2; const uint8_t* s2;   /* [n_experts][hidden][inter / 2] codes, [n_experts][hidden][inter / 32] scales (this rank's columns) */
+} vh_mixtral_experts_mxfp4;
+/* vh_mixtral_create with MXFP4 experts: `experts` is a host array of cfg->n_layers entries (copied); layers[l].w1 / w3 / w2 must
+ * be null.  NULL (vh_last_error says why; VH_E_ARG) for a null array, a non-null bf16 expert pointer, a null code or scale pointer,
+ * or hidden / inter not a multiple of 64.  The workspace is vh_mixtral_workspace_bytes(cfg), as for the bf16 engine. */
+vh_mixtral_t* vh_mixtral_create_mxfp4(const vh_mixtral_cfg* cfg, const vh_mixtral_layer* layers,
+                                      const vh_mixtral_experts_mxfp4* experts, const uint16_t* embed, const float* final_norm,
+                                      const uint16_t* lm_head, const float* rope_cos, const float* rope_sin, void* workspace,
+                                      size_t workspace_bytes);
+/* MXFP4 quantisation (the formula above): w bf16 [rows][ld_src], columns [col0, col0 + ncols) (both multiples of 32; ld_src % 8 == 0,
+ * w 16-byte aligned) -> codes [rows][ld_codes_bytes] (ncols / 2 bytes written per row; ld_codes_bytes % 4 == 0) and scales
+ * [rows][ld_scales] (ncols / 32 per row).  Inputs are finite. */
+int vh_quant_mxfp4(const uint16_t* w, long rows, int cols, long ld_src, int col0, int ncols, uint8_t* codes, long ld_codes_bytes,
+                   uint8_t* scales, long ld_scales, void* stream);
 void vh_mixtral_destroy(vh_mixtral_t* m);
 
 /* Tensor-parallel all-reduce hook (sum, fp32, in place).  Either the built-in RCCL path or a
@@ -445,6 +477,10 @@ int vh_moe_decode(const float* x, const float* delta, const float* norm_w, float
 int vh_moe_decode_i8(const float* x, const float* delta, const float* norm_w, float eps, const uint16_t* Wg, const int8_t* W1,
                      const float* s1, const int8_t* W3, const float* s3, const int8_t* W2, const float* s2, int E, int I, int H,
                      float* x_out, float* y, int* route, float* hbuf, void* stream);
+/* vh_moe_decode_mxfp4: the same on MXFP4 experts (vh_mixtral_experts_mxfp4 layout: codes and scale bytes); the router stays bf16. */
+int vh_moe_decode_mxfp4(const float* x, const float* delta, const float* norm_w, float eps, const uint16_t* Wg, const uint8_t* W1,
+                        const uint8_t* s1, const uint8_t* W3, const uint8_t* s3, const uint8_t* W2, const uint8_t* s2, int E, int I, int H,
+                        float* x_out, float* y, int* route, float* hbuf, void* stream);
 /* vh_rope_kv_append (K22): rotate-half RoPE on the q and k heads of S fused-QKV rows and append k, v to the cache at
  *   positions [pos0, pos0 + S) (HF apply_rotary_pos_emb + Cache.update; vLLM rotary_emb + KV write, mixtral.py:477-501).
  *   qkv fp32 [S][ldqkv] = q heads | k heads | v heads (head_dim 128); q_out fp32 [S][nq*128]; caches fp32

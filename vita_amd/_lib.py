@@ -129,6 +129,10 @@ class MixtralExpertsI8(C.Structure):
     _fields_ = [("w1", c_void_p), ("s1", c_void_p), ("w3", c_void_p), ("s3", c_void_p), ("w2", c_void_p), ("s2", c_void_p)]
 
 
+class MixtralExpertsMxfp4(C.Structure):
+    _fields_ = [("w1", c_void_p), ("s1", c_void_p), ("w3", c_void_p), ("s3", c_void_p), ("w2", c_void_p), ("s2", c_void_p)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(c_int, c_void_p, c_void_p, c_long, c_void_p)
 
 # every symbol include/vita_hip.h declares: (restype, argtypes)
@@ -141,6 +145,8 @@ SIGNATURES = {
     "vh_gemm_ps": (c_int, [C.POINTER(GemmPsArgs), c_void_p]),
     "vh_gemm_ps_i8": (c_int, [C.POINTER(GemmPsArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "vh_quant_rows_i8": (c_int, [c_void_p, c_long, c_int, c_long, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p]),
+    "vh_gemm_ps_mxfp4": (c_int, [C.POINTER(GemmPsArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vh_quant_mxfp4": (c_int, [c_void_p, c_long, c_int, c_long, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p]),
     "vh_split_planes": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p]),
     "vh_attention": (c_int, [C.POINTER(AttnArgs), c_void_p]),
     "vh_encoder_layer": (c_int, [C.POINTER(EncoderLayerArgs), c_void_p]),
@@ -166,6 +172,8 @@ SIGNATURES = {
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vh_moe_decode_i8": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vh_moe_decode_mxfp4": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vh_rope_kv_append": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                   c_int, c_void_p, c_void_p]),
     "vh_attn_decode": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p,
@@ -179,6 +187,8 @@ SIGNATURES = {
                                      c_void_p, c_void_p, c_void_p, c_size_t]),
     "vh_mixtral_create_i8": (c_void_p, [C.POINTER(MixtralCfg), C.POINTER(MixtralLayer), C.POINTER(MixtralExpertsI8), c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    "vh_mixtral_create_mxfp4": (c_void_p, [C.POINTER(MixtralCfg), C.POINTER(MixtralLayer), C.POINTER(MixtralExpertsMxfp4), c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
     "vh_mixtral_destroy": (None, [c_void_p]),
     "vh_mixtral_set_allreduce": (c_int, [c_void_p, ALLREDUCE_FN, c_void_p]),
     "vh_rccl_unique_id": (c_int, [c_void_p]),

@@ -176,7 +176,7 @@ def vocab_shard(vocab, rank, world):
     return lo, max(0, min(per, vocab - lo))
 
 
-EXPERT_MODES = ("bf16", "int8")
+EXPERT_MODES = ("bf16", "int8", "mxfp4")
 
 
 def quant_rows_i8(w, col0=0, ncols=None, q=None, s=None):
@@ -221,10 +221,56 @@ def _experts_i8(E, I, H, device, fill_w13, fill_w2, ff):
     return out
 
 
+def quant_mxfp4(w, col0=0, ncols=None, codes=None, scales=None):
+    """MXFP4 quantisation of a bf16 device matrix [rows, cols] on the device (vh_quant_mxfp4) for the columns
+    [col0, col0 + ncols), both multiples of 32: e2m1 codes uint8 [rows, ncols / 2] (element k in byte k >> 1, low nibble for even k)
+    and E8M0 scale bytes uint8 [rows, ncols / 32], one per 32 consecutive elements.  codes / scales may be given as views to fill."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib
+    if w.dtype != torch.bfloat16 or w.ndim != 2 or w.stride(1) != 1:
+        raise ValueError("quant_mxfp4 wants a 2-D bfloat16 matrix contiguous along its last dimension")
+    rows, cols = w.shape
+    ncols = cols - col0 if ncols is None else ncols
+    if col0 % 32 or ncols % 32 or ncols <= 0:
+        raise ValueError("quant_mxfp4: col0 and ncols must be multiples of 32")
+    if codes is None:
+        codes = torch.empty(rows, ncols // 2, dtype=torch.uint8, device=w.device)
+    if scales is None:
+        scales = torch.empty(rows, ncols // 32, dtype=torch.uint8, device=w.device)
+    for t, n, nm in ((codes, ncols // 2, "codes"), (scales, ncols // 32, "scales")):
+        if t.dtype != torch.uint8 or tuple(t.shape) != (rows, n) or t.stride(1) != 1:
+            raise ValueError(f"quant_mxfp4: {nm} must be uint8 [rows, {n}] (last dimension contiguous)")
+    _lib.check(_lib.load().vh_quant_mxfp4(C.c_void_p(w.data_ptr()), rows, cols, w.stride(0), int(col0), int(ncols),
+                                          C.c_void_p(codes.data_ptr()), codes.stride(0), C.c_void_p(scales.data_ptr()),
+                                          scales.stride(0), C.c_void_p(torch.cuda.current_stream().cuda_stream)), "vh_quant_mxfp4")
+    return codes, scales
+
+
+def _experts_mxfp4(E, I, H, device, fill_w13, fill_w2, ff):
+    """MXFP4 experts of one layer, one expert at a time through a bf16 scratch (peak: the fp4 model + one bf16 expert); the fill
+    callables are those of _experts_i8.  A w2 shard is the column slice [ff] of the codes and of the scales."""
+    import torch
+    u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=device)
+    out = {"w1": u8(E, I, H // 2), "s1": u8(E, I, H // 32), "w3": u8(E, I, H // 2), "s3": u8(E, I, H // 32),
+           "w2": u8(E, H, I // 2), "s2": u8(E, H, I // 32)}
+    for e in range(E):
+        for nm, sn in (("w1", "s1"), ("w3", "s3")):
+            quant_mxfp4(fill_w13(e, nm), codes=out[nm][e], scales=out[sn][e])
+        quant_mxfp4(fill_w2(e), col0=ff.start, ncols=I, codes=out["w2"][e], scales=out["s2"][e])
+    return out
+
+
+_EXPERT_PACKERS = {"int8": _experts_i8, "mxfp4": _experts_mxfp4}
+
+
 def pack_mixtral(sd, cfg: VitaConfig, device, rank=0, world=1, shard_vocab=True, experts="bf16"):
     """state dict (reference names) -> dict of device tensors in engine layout for this TP rank.
     experts="int8": w1 / w3 / w2 become int8 with per-row fp32 scales s1 / s3 / s2, quantised on the device one
-    expert at a time; everything else is packed as for "bf16"."""
+    expert at a time; experts="mxfp4": uint8 e2m1 codes with uint8 block scales s1 / s3 / s2, likewise; everything
+    else is packed as for "bf16"."""
     if experts not in EXPERT_MODES:
         raise ValueError(f"experts must be one of {EXPERT_MODES}, got {experts!r}")
     import torch
@@ -252,9 +298,9 @@ def pack_mixtral(sd, cfg: VitaConfig, device, rank=0, world=1, shard_vocab=True,
             "ffn_norm": _t(g(p + "post_attention_layernorm.weight"), device, f32),
             "wrouter": _t(g(p + "block_sparse_moe.gate.weight"), device, bf),
         }
-        if experts == "int8":
+        if experts in _EXPERT_PACKERS:
             ew = lambda e, nm: g(p + f"block_sparse_moe.experts.{e}.{nm}.weight")
-            layer.update(_experts_i8(t.num_local_experts, ff.stop - ff.start, t.hidden_size, device,
+            layer.update(_EXPERT_PACKERS[experts](t.num_local_experts, ff.stop - ff.start, t.hidden_size, device,
                                      lambda e, nm: _t(ew(e, nm)[ff], device, bf), lambda e: _t(ew(e, "w2"), device, bf), ff))
         else:
             layer.update({
@@ -299,7 +345,8 @@ def synth_mixtral_device(cfg: VitaConfig, device, seed=0, rank=0, world=1, shard
     values of its slice of the full tensor, and the CPU oracle regenerates any tensor on the host
     (oracle/hashw.py) — the released geometry can be parity-checked without a checkpoint.
     experts="int8": the experts are generated one at a time into a bf16 scratch and quantised (pack_mixtral); a w2 shard's
-    scratch holds the expert's full [H, I] so that its scales are over full rows."""
+    scratch holds the expert's full [H, I] so that its scales are over full rows.  experts="mxfp4": the same path with the MXFP4
+    quantiser (a shard's w2 blocks are those of the full row)."""
     import torch
     if experts not in EXPERT_MODES:
         raise ValueError(f"experts must be one of {EXPERT_MODES}, got {experts!r}")
@@ -315,7 +362,7 @@ def synth_mixtral_device(cfg: VitaConfig, device, seed=0, rank=0, world=1, shard
     lo, nv = vocab_shard(t.vocab_size, rank, world if shard_vocab else 1)
     out = {"embed": hash_fill(new(t.vocab_size, H), "model.embed_tokens.weight", seed), "final_norm": ones(H),
            "lm_head": hash_fill(new(nv, H), "lm_head.weight", seed, idx0=lo * H), "layers": [], "experts": experts}
-    if experts == "int8":
+    if experts in _EXPERT_PACKERS:
         s13, s2 = new(I, H), new(H, t.intermediate_size)      # one bf16 expert of scratch
 
         def hashed_experts(prefix):
@@ -333,8 +380,8 @@ def synth_mixtral_device(cfg: VitaConfig, device, seed=0, rank=0, world=1, shard
         hash_fill(wqkv[(nq + nkv) * hd:], p + "self_attn.v_proj.weight", seed, idx0=kvs.start * H)
         wo = hash_fill(new(H, nq * hd), p + "self_attn.o_proj.weight", seed, ld_src=t.num_attention_heads * hd,
                        idx0=qs.start)
-        if experts == "int8":
-            ex = _experts_i8(E, I, H, device, *hashed_experts(p), ff)
+        if experts in _EXPERT_PACKERS:
+            ex = _EXPERT_PACKERS[experts](E, I, H, device, *hashed_experts(p), ff)
         else:
             w1, w3, w2 = new(E, I, H), new(E, I, H), new(E, H, I)
             for e in range(E):

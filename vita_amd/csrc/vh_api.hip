@@ -91,9 +91,8 @@ static int gemm_entry(const char* name, const vh_gemm_args* a, const float* ln_w
     return check_launch(name, vhk_gemm(S(stream), g));
 }
 
-int vh_gemm_ps(const vh_gemm_ps_args* a, void* stream) {
-    if (!a || !a->A_hi || !a->A_lo || !a->W) return fail(VH_E_ARG, "vh_gemm_ps: null pointer");
-    VhGemmPsArgs g{};
+// the C ABI's vh_gemm_ps_args as the launchers' record (the quantised entries have checked that a->W / W_up are null)
+static int ps_args(const char* name, const vh_gemm_ps_args* a, VhGemmPsArgs& g) {
     g.A_hi = a->A_hi; g.A_lo = a->A_lo; g.lda = a->lda; g.a_rowidx = a->a_rowidx;
     g.W = a->W; g.W_up = a->W_up; g.ldw = a->ldw; g.w_group_stride = a->w_group_stride;
     g.group_off = a->group_off; g.ngroups = a->ngroups;
@@ -102,7 +101,13 @@ int vh_gemm_ps(const vh_gemm_ps_args* a, void* stream) {
     g.M = a->M; g.N = a->N; g.K = a->K; g.act = a->act;
     g.ksplit = a->ksplit; g.c_split_stride = a->c_split_stride; g.nslab_out = a->nslab_out;
     if ((size_t)a->lda * 2 * (size_t)(a->M > 0 ? a->M : 1) >= (1ull << 32))
-        return fail(VH_E_SHAPE, "vh_gemm_ps: activation plane above the 32-bit offset range");
+        return fail(VH_E_SHAPE, "%s: activation plane above the 32-bit offset range", name);
+    return VH_OK;
+}
+int vh_gemm_ps(const vh_gemm_ps_args* a, void* stream) {
+    if (!a || !a->A_hi || !a->A_lo || !a->W) return fail(VH_E_ARG, "vh_gemm_ps: null pointer");
+    VhGemmPsArgs g{};
+    if (int rc = ps_args("vh_gemm_ps", a, g)) return rc;
     return check_launch("vh_gemm_ps", vhk_gemm_ps(S(stream), g));
 }
 int vh_gemm_ps_i8(const vh_gemm_ps_args* a, const int8_t* W, const float* s, const int8_t* W_up, const float* s_up,
@@ -110,15 +115,7 @@ int vh_gemm_ps_i8(const vh_gemm_ps_args* a, const int8_t* W, const float* s, con
     if (!a || !a->A_hi || !a->A_lo || !W || !s || (W_up != nullptr) != (s_up != nullptr)) return fail(VH_E_ARG, "vh_gemm_ps_i8: null pointer");
     if (a->W || a->W_up) return fail(VH_E_ARG, "vh_gemm_ps_i8: args->W / W_up must be null (the weights are the int8 arguments)");
     VhGemmPsArgs g{};
-    g.A_hi = a->A_hi; g.A_lo = a->A_lo; g.lda = a->lda; g.a_rowidx = a->a_rowidx;
-    g.ldw = a->ldw; g.w_group_stride = a->w_group_stride;
-    g.group_off = a->group_off; g.ngroups = a->ngroups;
-    g.C = a->C; g.ldc = a->ldc; g.C_hi = a->C_hi; g.C_lo = a->C_lo; g.ldc_split = a->ldc_split;
-    g.c_rowidx = a->c_rowidx; g.bias = a->bias; g.scale = a->scale; g.resid = a->resid; g.ldr = a->ldr;
-    g.M = a->M; g.N = a->N; g.K = a->K; g.act = a->act;
-    g.ksplit = a->ksplit; g.c_split_stride = a->c_split_stride; g.nslab_out = a->nslab_out;
-    if ((size_t)a->lda * 2 * (size_t)(a->M > 0 ? a->M : 1) >= (1ull << 32))
-        return fail(VH_E_SHAPE, "vh_gemm_ps_i8: activation plane above the 32-bit offset range");
+    if (int rc = ps_args("vh_gemm_ps_i8", a, g)) return rc;
     const VhPsI8 q{W, W_up, s, s_up, s_group_stride};
     if (const char* why = vhk_gemm_ps_i8_refusal(g, q)) return fail(VH_E_SHAPE, "vh_gemm_ps_i8: %s", why);
     return check_launch("vh_gemm_ps_i8", vhk_gemm_ps_i8(S(stream), g, q));
@@ -127,6 +124,20 @@ int vh_quant_rows_i8(const uint16_t* w, long rows, int cols, long ld_src, int co
                      void* stream) {
     if (!w || !q || !s) return fail(VH_E_ARG, "vh_quant_rows_i8: null pointer");
     return check_launch("vh_quant_rows_i8", vhk_quant_rows_i8(S(stream), w, rows, cols, ld_src, col0, ncols, q, ld_dst, s));
+}
+int vh_gemm_ps_mxfp4(const vh_gemm_ps_args* a, const uint8_t* W, const uint8_t* Sc, const uint8_t* W_up, const uint8_t* Sc_up, void* stream) {
+    if (!a || !a->A_hi || !a->A_lo || !W || !Sc || (W_up != nullptr) != (Sc_up != nullptr)) return fail(VH_E_ARG, "vh_gemm_ps_mxfp4: null pointer");
+    if (a->W || a->W_up) return fail(VH_E_ARG, "vh_gemm_ps_mxfp4: args->W / W_up must be null (the weights are the MXFP4 arguments)");
+    VhGemmPsArgs g{};
+    if (int rc = ps_args("vh_gemm_ps_mxfp4", a, g)) return rc;
+    const VhPsF4 q{W, W_up, Sc, Sc_up};
+    if (const char* why = vhk_gemm_ps_mxfp4_refusal(g, q)) return fail(VH_E_SHAPE, "vh_gemm_ps_mxfp4: %s", why);
+    return check_launch("vh_gemm_ps_mxfp4", vhk_gemm_ps_mxfp4(S(stream), g, q));
+}
+int vh_quant_mxfp4(const uint16_t* w, long rows, int cols, long ld_src, int col0, int ncols, uint8_t* codes, long ld_codes_bytes,
+                   uint8_t* scales, long ld_scales, void* stream) {
+    if (!w || !codes || !scales) return fail(VH_E_ARG, "vh_quant_mxfp4: null pointer");
+    return check_launch("vh_quant_mxfp4", vhk_quant_mxfp4(S(stream), w, rows, cols, ld_src, col0, ncols, codes, ld_codes_bytes, scales, ld_scales));
 }
 int vh_split_planes(const float* x, long ldx, uint16_t* hi, uint16_t* lo, long ldo, int rows, int cols, void* stream) {
     if (!x || !hi || !lo) return fail(VH_E_ARG, "vh_split_planes: null pointer");
@@ -263,6 +274,18 @@ int vh_moe_decode_i8(const float* x, const float* delta, const float* norm_w, fl
     return check_launch("vh_moe_decode_i8 (down)", vhk_dec_down_i8(S(stream), hbuf, route, W2, s2, H, I, H, y));
 }
 
+int vh_moe_decode_mxfp4(const float* x, const float* delta, const float* norm_w, float eps, const uint16_t* Wg, const uint8_t* W1,
+                        const uint8_t* s1, const uint8_t* W3, const uint8_t* s3, const uint8_t* W2, const uint8_t* s2, int E, int I, int H,
+                        float* x_out, float* y, int* route, float* hbuf, void* stream) {
+    if (!x || !norm_w || !Wg || !W1 || !s1 || !W3 || !s3 || !W2 || !s2 || !y || !route || !hbuf)
+        return fail(VH_E_ARG, "vh_moe_decode_mxfp4: null pointer");
+    if (H % 64 || I % 64 || H > 14336 || I > 14336) return fail(VH_E_SHAPE, "vh_moe_decode_mxfp4: H, I must be multiples of 64 and <= 14336");
+    int rc = check_launch("vh_moe_decode_mxfp4 (gate|up)", vhk_dec_gateup_mxfp4(S(stream), x, delta, x_out, norm_w, eps, Wg, E, W1, s1, W3,
+                                                                                s3, I, H, route, hbuf, 0));
+    if (rc != VH_OK) return rc;
+    return check_launch("vh_moe_decode_mxfp4 (down)", vhk_dec_down_mxfp4(S(stream), hbuf, route, W2, s2, H, I, H, y));
+}
+
 int vh_rope_kv_append(const float* qkv, long ldqkv, float* q_out, float* kcache, float* vcache, const float* rope_cos,
                       const float* rope_sin, int Sn, int pos0, int nq, int nkv, int max_ctx, const int* table, void* stream) {
     if (!qkv || !q_out || !kcache || !vcache || !rope_cos || !rope_sin) return fail(VH_E_ARG, "vh_rope_kv_append: null pointer");
@@ -376,6 +399,7 @@ struct Carver {
 struct vh_mixtral {
     vh_mixtral_cfg c;
     std::vector<vh_mixtral_layer> L;
+    std::vector<vh_mixtral_experts_mxfp4> Q4;   // MXFP4 experts (vh_mixtral_create_mxfp4): one entry per layer; empty = not MXFP4
     std::vector<vh_mixtral_experts_i8> Q;   // int8 experts (vh_mixtral_create_i8): one entry per layer; empty = bf16
     const uint16_t* embed; const float* final_norm; const uint16_t* lm_head;
     const float* rope_cos; const float* rope_sin;
@@ -742,6 +766,36 @@ vh_mixtral_t* vh_mixtral_create_i8(const vh_mixtral_cfg* cfg, const vh_mixtral_l
     return m;
 }
 
+vh_mixtral_t* vh_mixtral_create_mxfp4(const vh_mixtral_cfg* cfg, const vh_mixtral_layer* layers,
+                                      const vh_mixtral_experts_mxfp4* experts, const uint16_t* embed, const float* final_norm,
+                                      const uint16_t* lm_head, const float* rope_cos, const float* rope_sin, void* workspace,
+                                      size_t workspace_bytes) {
+    if (cfg_ok(cfg) != VH_OK) return nullptr;
+    if (!layers || !experts) {
+        fail(VH_E_ARG, "vh_mixtral_create_mxfp4: null layers / experts");
+        return nullptr;
+    }
+    if (cfg->hidden % 64 || cfg->inter % 64) {
+        fail(VH_E_ARG, "vh_mixtral_create_mxfp4: hidden (%d) and inter (%d) must be multiples of 64", cfg->hidden, cfg->inter);
+        return nullptr;
+    }
+    for (int l = 0; l < cfg->n_layers; ++l) {
+        const vh_mixtral_layer& w = layers[l];
+        const vh_mixtral_experts_mxfp4& q = experts[l];
+        if (w.w1 || w.w3 || w.w2) {
+            fail(VH_E_ARG, "vh_mixtral_create_mxfp4: layers[%d].w1 / w3 / w2 must be null (the experts are MXFP4)", l);
+            return nullptr;
+        }
+        if (!q.w1 || !q.s1 || !q.w3 || !q.s3 || !q.w2 || !q.s2) {
+            fail(VH_E_ARG, "vh_mixtral_create_mxfp4: null MXFP4 code or scale pointer in experts[%d]", l);
+            return nullptr;
+        }
+    }
+    vh_mixtral_t* m = vh_mixtral_create(cfg, layers, embed, final_norm, lm_head, rope_cos, rope_sin, workspace, workspace_bytes);
+    if (m) m->Q4.assign(experts, experts + cfg->n_layers);
+    return m;
+}
+
 void vh_mixtral_destroy(vh_mixtral_t* m) {
     if (!m) return;
     for (hipEvent_t e : m->prof_ev) (void)hipEventDestroy(e);
@@ -1013,6 +1067,7 @@ static int reduce_rows(vh_mixtral* m, hipStream_t st, int Sn, bool overlap, Prod
 struct MoeGemms {
     VhGemmPsArgs gate_up, down;   // launched by the caller (down: all H columns) through moe_gate_up / moe_down
     const vh_mixtral_experts_i8* q; // int8 experts of the layer (null: bf16): the same arguments with W / W_up null
+    const vh_mixtral_experts_mxfp4* q4;   // MXFP4 experts of the layer (null: not MXFP4), likewise
     int nslab;                    // slabs the combine adds (1 when the kernel picks the split ...
     const int* nslab_dev;         // ... and reports it here; null otherwise)
 };
@@ -1021,6 +1076,7 @@ static int moe_gemms(vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, i
     VH_TRY(vhk_moe_sort(st, m->pids, n, E, m->pgoff, m->pstok, m->psslot), "sort");
     *p = MoeGemms{};
     p->q = m->Q.empty() ? nullptr : &m->Q[&w - m->L.data()];
+    p->q4 = m->Q4.empty() ? nullptr : &m->Q4[&w - m->L.data()];
     VhGemmPsArgs &g = p->gate_up, &d = p->down;
     g.A_hi = m->pxn_hi; g.A_lo = m->pxn_lo; g.lda = H; g.a_rowidx = m->pstok;
     g.W = w.w1; g.W_up = w.w3; g.ldw = H; g.w_group_stride = (long)I * H;
@@ -1042,16 +1098,18 @@ static int moe_gemms(vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, i
 }
 // int8 experts: the specialised streaming GEMM with the int8 stagers (vhk_gemm_ps_i8), the same arguments with W / W_up null
 static int moe_gate_up(hipStream_t st, const MoeGemms& p) {
-    if (!p.q) return vhk_gemm_ps(st, p.gate_up);
+    if (!p.q && !p.q4) return vhk_gemm_ps(st, p.gate_up);
     VhGemmPsArgs g = p.gate_up;
     g.W = nullptr; g.W_up = nullptr;
+    if (p.q4) return vhk_gemm_ps_mxfp4(st, g, VhPsF4{p.q4->w1, p.q4->w3, p.q4->s1, p.q4->s3});
     return vhk_gemm_ps_i8(st, g, VhPsI8{p.q->w1, p.q->w3, p.q->s1, p.q->s3, (long)g.N});
 }
 // down projection of output columns [c0, c0 + d.N) (d: p.down with N / C narrowed by the caller)
 static int moe_down_gemm(hipStream_t st, const MoeGemms& p, const VhGemmPsArgs& d, int c0, int H) {
-    if (!p.q) return vhk_gemm_ps(st, d);
+    if (!p.q && !p.q4) return vhk_gemm_ps(st, d);
     VhGemmPsArgs a = d;
     a.W = nullptr;
+    if (p.q4) return vhk_gemm_ps_mxfp4(st, a, VhPsF4{p.q4->w2 + (size_t)c0 * (a.ldw >> 1), nullptr, p.q4->s2 + (size_t)c0 * (a.ldw >> 5), nullptr});
     return vhk_gemm_ps_i8(st, a, VhPsI8{p.q->w2 + (size_t)c0 * a.ldw, nullptr, p.q->s2 + c0, nullptr, (long)H});
 }
 // the down projection of output columns [h * ncols, (h + 1) * ncols) into the slabs from py_half(h), then their
@@ -1536,16 +1594,30 @@ static bool fused_wanted(const vh_mixtral* m) {
     return vhk_dec_ablk_supported(m->H, m->nq, m->nkv) != 0;
 }
 
-// gate|up and down GEMVs of one sequence's MoE in layer w, on its bf16 experts or (q8 set) its int8 ones; cx / px: the fused exchange
+// gate|up and down GEMVs of one sequence's MoE in layer w, on its bf16, int8 or MXFP4 experts; cx / px: the fused exchange
 // the launch consumes / produces (nullable)
-static int dec_gateup(const vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, const vh_mixtral_experts_i8* q8, const float* x_in,
+struct DecExperts {
+    const vh_mixtral_experts_i8* q8;       // int8 experts of the layer, or null
+    const vh_mixtral_experts_mxfp4* q4;    // MXFP4 experts of the layer, or null (both null: bf16)
+    int consumer() const { return q4 ? 5 : q8 ? 4 : 1; }   // vhk_dec_consumer_blocks' id of the gate|up launch
+};
+static DecExperts dec_experts(const vh_mixtral* m, int l) {
+    return DecExperts{m->Q.empty() ? nullptr : &m->Q[l], m->Q4.empty() ? nullptr : &m->Q4[l]};
+}
+static int dec_gateup(const vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, const DecExperts& x, const float* x_in,
                       const float* delta, float* x_out, int* route, float* hbuf, const VhXchg* cx) {
+    const vh_mixtral_experts_i8* q8 = x.q8;
+    if (x.q4)
+        return vhk_dec_gateup_mxfp4(st, x_in, delta, x_out, w.ffn_norm, m->c.rms_eps, w.wrouter, m->E, x.q4->w1, x.q4->s1, x.q4->w3,
+                                    x.q4->s3, m->I, m->H, route, hbuf, 0, cx);
     return q8 ? vhk_dec_gateup_i8(st, x_in, delta, x_out, w.ffn_norm, m->c.rms_eps, w.wrouter, m->E, q8->w1, q8->s1, q8->w3, q8->s3, m->I,
                                   m->H, route, hbuf, 0, cx)
               : vhk_dec_gateup(st, x_in, delta, x_out, w.ffn_norm, m->c.rms_eps, w.wrouter, m->E, w.w1, w.w3, m->I, m->H, route, hbuf, 0, cx);
 }
-static int dec_down(const vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, const vh_mixtral_experts_i8* q8, const float* hbuf,
+static int dec_down(const vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, const DecExperts& x, const float* hbuf,
                     const int* route, float* out, const VhXchg* px) {
+    const vh_mixtral_experts_i8* q8 = x.q8;
+    if (x.q4) return vhk_dec_down_mxfp4(st, hbuf, route, x.q4->w2, x.q4->s2, m->H, m->I, m->H, out, px);
     return q8 ? vhk_dec_down_i8(st, hbuf, route, q8->w2, q8->s2, m->H, m->I, m->H, out, px)
               : vhk_dec_down(st, hbuf, route, w.w2, m->H, m->I, out, px);
 }
@@ -1580,11 +1652,11 @@ static int decode_one_step(vh_mixtral* m, vh_mixtral::Unit& u, hipStream_t st) {
     bool have_xm = false;
     for (int l = 0; l < m->c.n_layers; ++l) {
         const vh_mixtral_layer& w = m->L[l];
-        const vh_mixtral_experts_i8* q8 = m->Q.empty() ? nullptr : &m->Q[l];
+        const DecExperts ex = dec_experts(m, l);
         float* kc = m->kcache + (size_t)l * nkv * m->c.max_ctx * hd;
         float* vc = m->vcache + (size_t)l * nkv * m->c.max_ctx * hd;
         const bool prof = m->prof_stride > 0 && (l % m->prof_stride) == 0 && m->prof_used + 2 <= m->prof_ev.size();
-        if (fuse && vh_comm_xchg_next(m->comm, H, 0, vhk_dec_consumer_blocks(q8 ? 4 : 1, 0, H, I), &xa, st) != VH_OK)
+        if (fuse && vh_comm_xchg_next(m->comm, H, 0, vhk_dec_consumer_blocks(ex.consumer(), 0, H, I), &xa, st) != VH_OK)
             return fail(VH_E_COMM, "fused exchange failed: %s", vh_comm_last_error());
         if (fused_attn) {
             VhDecAblk a{};
@@ -1611,13 +1683,13 @@ static int decode_one_step(vh_mixtral* m, vh_mixtral::Unit& u, hipStream_t st) {
         const int xm_blocks = l + 1 < m->c.n_layers ? (fused_attn ? vhk_dec_ablk_qkv_blocks(m->nqkv, H) : vhk_dec_consumer_blocks(0, m->nqkv, H, I))
                                                      : m->lm_grid;
         if (prof) (void)hipEventRecord(m->prof_ev[m->prof_used], st);
-        VH_TRY(dec_gateup(m, st, w, q8, u.xb, u.da, u.xa, m->route, m->hbuf, fuse ? &xa : nullptr), "dec gateup");
+        VH_TRY(dec_gateup(m, st, w, ex, u.xb, u.da, u.xa, m->route, m->hbuf, fuse ? &xa : nullptr), "dec gateup");
         if (prof) { (void)hipEventRecord(m->prof_ev[m->prof_used + 1], st); m->prof_used += 2; }
         if (fuse) {
             if (vh_comm_xchg_next(m->comm, H, 1, xm_blocks, &xm, st) != VH_OK) return fail(VH_E_COMM, "fused exchange failed: %s", vh_comm_last_error());
             have_xm = true;
         }
-        VH_TRY(dec_down(m, st, w, q8, m->hbuf, m->route, u.dm, fuse ? &xm : nullptr), "dec down");
+        VH_TRY(dec_down(m, st, w, ex, m->hbuf, m->route, u.dm, fuse ? &xm : nullptr), "dec down");
         if (!fuse && m->allreduce(u.dm, H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
     }
     const int rc = head_one(m, st, u, u.xa, u.dm, /*mode=*/1, /*set_pos=*/0, have_xm ? &xm : nullptr);
@@ -1870,7 +1942,7 @@ static int decode_iteration(vh_mixtral* m, hipStream_t st, const int* ids, int n
     }
     for (int l = 0; l < m->c.n_layers; ++l) {
         const vh_mixtral_layer& w = m->L[l];
-        const vh_mixtral_experts_i8* q8 = m->Q.empty() ? nullptr : &m->Q[l];
+        const DecExperts ex = dec_experts(m, l);
         float* kc = m->kcache + (size_t)l * nkv * m->c.max_ctx * hd;
         float* vc = m->vcache + (size_t)l * nkv * m->c.max_ctx * hd;
         for (int g0 = 0; g0 < n; g0 += VH_BMAX) {
@@ -1910,8 +1982,8 @@ static int decode_iteration(vh_mixtral* m, hipStream_t st, const int* ids, int n
             for (int b = 0; b < n; ++b) {
                 const vh_mixtral::Unit& u = *us[b];
                 const int lane = b % VH_BMAX;   // the scratch lane the sequence had in its attention group
-                VH_TRY(dec_gateup(m, st, w, q8, u.xb, u.da, u.xa, m->l_route[lane], m->l_hbuf[lane], nullptr), "dec gateup");
-                VH_TRY(dec_down(m, st, w, q8, m->l_hbuf[lane], m->l_route[lane], dm[b], nullptr), "dec down");
+                VH_TRY(dec_gateup(m, st, w, ex, u.xb, u.da, u.xa, m->l_route[lane], m->l_hbuf[lane], nullptr), "dec gateup");
+                VH_TRY(dec_down(m, st, w, ex, m->l_hbuf[lane], m->l_route[lane], dm[b], nullptr), "dec down");
             }
             for (int b = 0; b < n; ++b)
                 if (m->allreduce(dm[b], H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");

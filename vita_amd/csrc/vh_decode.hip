@@ -926,6 +926,225 @@ __global__ __launch_bounds__(256) void k_dec_down_i8(const float* __restrict__ h
     }
 }
 
+// ---- MXFP4 experts: e2m1 codes [rows][K / 2] with one E8M0 scale byte per 32 weights [rows][K / 32] ------------
+// A thread's chunk is one SCALE BLOCK: 32 weights = 16 bytes of codes (one 16-byte load, the width of the bf16 kernels) plus the
+// block's scale byte.  A row of K = 4096 is then only 128 chunks, so a row is spread over P = 64 WPR threads (WPR = 1, 2 or 4
+// waves, by K) and the G = 4 / WPR thread groups of a block take different rows; the conversion (one v_cvt_scalef32_pk_f32_fp4
+// per two weights) applies the block scale, so there is no per-row scale in the epilogue.  Rows per group are chosen so that a
+// thread has at least the int8 kernels' bytes in flight, except the down kernel with two chunk slots (measured).
+template <int NJ, int R, int WPR>
+__device__ __forceinline__ void gemv_issue_f4(const uint8_t* const (&rows)[R], const uint8_t* const (&srows)[R], int K,
+                                              uint4 (&w)[R][NJ], uint32_t (&s)[R][NJ]) {
+    const int tl = threadIdx.x & (64 * WPR - 1);
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int c = tl + j * 64 * WPR;
+            if (c * 32 < K) {
+                w[r][j] = ld_weight16(rows[r] + (size_t)c * 16);
+                s[r][j] = srows[r][c];
+            } else {
+                w[r][j] = make_uint4(0, 0, 0, 0);
+                s[r][j] = 127u;
+            }
+        }
+}
+// 32 weights of one scale block against 32 activations; the scale byte becomes the fp32 2^(byte - 127) the conversion takes
+__device__ __forceinline__ float dot32_f4_f32(const uint4& w, const uint32_t sbyte, const float* x) {
+    const float sc = __uint_as_float(sbyte << 23);
+    const uint32_t wd[4] = {w.x, w.y, w.z, w.w};
+    float a = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#define VH_F4_PAIR(B)                                                                        \
+    {                                                                                        \
+        const vh_f32x2 v = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(wd[i], sc, B);           \
+        a = fmaf(v.x, x[i * 8 + 2 * B], a);                                                  \
+        a = fmaf(v.y, x[i * 8 + 2 * B + 1], a);                                              \
+    }
+        VH_F4_PAIR(0) VH_F4_PAIR(1) VH_F4_PAIR(2) VH_F4_PAIR(3)
+#undef VH_F4_PAIR
+    }
+    return a;
+}
+template <int NJ, int R>
+__device__ __forceinline__ void gemv_fma_f4(const uint4 (&w)[R][NJ], const uint32_t (&s)[R][NJ], const float (&x)[NJ][32],
+                                            float (&acc)[R]) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        float a = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) a += dot32_f4_f32(w[r][j], s[r][j], x[j]);
+        acc[r] = a;
+    }
+}
+
+// router (bf16, dec_route: its activation registers are in the bf16 kernels' 8-wide chunk layout) + gate|up of the two chosen
+// experts.  The normed activations go through LDS once per block into the 32-wide chunk layout (16-byte pieces, swizzled by
+// the chunk index so that neither side has bank conflicts).  Group g of the block takes RP gate + RP up rows of an iteration's
+// G RP rows: h = silu(g inv) * (u inv), inv the deferred RMSNorm factor.
+template <int NJ8, int NJ, int WPR>
+__global__ __launch_bounds__(256) void k_dec_gateup_mxfp4(const float* __restrict__ x_in, const float* __restrict__ delta,
+                                                          float* __restrict__ x_out, const float* __restrict__ norm_w,
+                                                          float eps, const uint16_t* __restrict__ Wg, int E,
+                                                          const uint8_t* __restrict__ W1, const uint8_t* __restrict__ S1,
+                                                          const uint8_t* __restrict__ W3, const uint8_t* __restrict__ S3,
+                                                          int I, int K, int* __restrict__ route_out,
+                                                          float* __restrict__ hbuf, const VhXchg cx) {
+    constexpr int G = 4 / WPR, P = 64 * WPR, RP = (G == 4 || NJ == 2) ? 4 : 8, NV = 2 * RP;
+    static_assert(NJ * P * 32 >= NJ8 * 2048, "the 32-wide chunks cover what the 8-wide ones do");
+    __shared__ float red[4 * (NV > 9 ? NV : 9)];
+    __shared__ f32x4 xs[NJ8 * 512];
+    xchg_reduce(cx);
+    const int bi = blockIdx.x, gn = gridDim.x;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int g = threadIdx.x / P, tl = threadIdx.x & (P - 1);
+    float inv;
+    int e0 = 0, e1 = 0;
+    float x[NJ][32];
+    {
+        float xr[NJ8][8];
+        dec_route<NJ8>(bi, x_in, delta, x_out, norm_w, eps, Wg, E, K, route_out, cx, red, xr, inv, e0, e1);
+#pragma unroll
+        for (int j = 0; j < NJ8; ++j) {
+            const int c = threadIdx.x + j * 256;
+            if (c * 8 < K) {
+                const int sw = (c >> 2) & 7;
+                xs[(2 * c) ^ sw] = f32x4{xr[j][0], xr[j][1], xr[j][2], xr[j][3]};
+                xs[(2 * c + 1) ^ sw] = f32x4{xr[j][4], xr[j][5], xr[j][6], xr[j][7]};
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int c = tl + j * P;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (c * 32 < K) v = xs[(c * 8 + i) ^ (c & 7)];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) x[j][i * 4 + q] = v[q];
+            }
+        }
+    }
+    const int rows_it = G * RP;
+    const int per_slot = I / rows_it;
+    const int n_iter = 2 * per_slot;
+    const size_t ldc = (size_t)(K >> 1), lds = (size_t)(K >> 5);
+    for (int it = bi; it < n_iter; it += gn) {
+        const int slot = it / per_slot;
+        const int i0 = (it - slot * per_slot) * rows_it;
+        const size_t r0 = (size_t)(slot ? e1 : e0) * I + i0 + g * RP;
+        const uint8_t* rows[NV];
+        const uint8_t* srows[NV];
+#pragma unroll
+        for (int r = 0; r < RP; ++r) {
+            rows[r] = W1 + (r0 + r) * ldc;
+            rows[RP + r] = W3 + (r0 + r) * ldc;
+            srows[r] = S1 + (r0 + r) * lds;
+            srows[RP + r] = S3 + (r0 + r) * lds;
+        }
+        uint4 w[NV][NJ];
+        uint32_t s[NV][NJ];
+        gemv_issue_f4<NJ, NV, WPR>(rows, srows, K, w, s);
+        float acc[NV];
+        gemv_fma_f4<NJ, NV>(w, s, x, acc);
+        const float wv = MultiReduce<NV, 0>::run(acc, lane);
+        const int idx = multi_idx<NV>(lane);
+        if (idx < NV) red[wid * NV + idx] = wv;
+        __syncthreads();
+        if ((int)threadIdx.x < rows_it) {
+            const int gg = threadIdx.x / RP, r = threadIdx.x - gg * RP;
+            float gs = 0.f, us = 0.f;
+#pragma unroll
+            for (int k = 0; k < WPR; ++k) {
+                gs += red[(gg * WPR + k) * NV + r];
+                us += red[(gg * WPR + k) * NV + RP + r];
+            }
+            hbuf[(size_t)slot * I + i0 + threadIdx.x] = silu_f(gs * inv) * (us * inv);
+        }
+        __syncthreads();
+    }
+}
+
+// down GEMV of both experts on MXFP4 rows: out[n] = w0 (w'_e0[n] . h0) + w1 (w'_e1[n] . h1).  A block takes RB = G R output rows,
+// R per thread group: 8 / G, or 4 with two chunk slots (I > 8192; measured at I = 14336: 6 rows, 252 VGPRs, cost 3 us more per layer).  W2 / S2 point at row 0 of this call's rows; rstride = rows per expert
+template <int NJ, int WPR>
+__global__ __launch_bounds__(256) void k_dec_down_mxfp4(const float* __restrict__ hbuf, const int* __restrict__ route,
+                                                        const uint8_t* __restrict__ W2, const uint8_t* __restrict__ S2, int N, int I,
+                                                        long rstride, float* __restrict__ out, const VhXchg px) {
+    constexpr int G = 4 / WPR, P = 64 * WPR, R = NJ == 2 ? 4 : 8 / G, RB = G * R;
+    __shared__ float red[4 * R];
+    const int e0 = route[0], e1 = route[1];
+    const float w0 = __int_as_float(route[2]), w1 = __int_as_float(route[3]);
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int g = threadIdx.x / P, tl = threadIdx.x & (P - 1);
+    const int n0 = blockIdx.x * RB + g * R;
+    const size_t ldc = (size_t)(I >> 1), lds = (size_t)(I >> 5);
+    const uint8_t* rows0[R];
+    const uint8_t* rows1[R];
+    const uint8_t* srows0[R];
+    const uint8_t* srows1[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const size_t a = (size_t)e0 * rstride + min(n0 + r, N - 1), b = (size_t)e1 * rstride + min(n0 + r, N - 1);
+        rows0[r] = W2 + a * ldc; srows0[r] = S2 + a * lds;
+        rows1[r] = W2 + b * ldc; srows1[r] = S2 + b * lds;
+    }
+    uint4 wa[R][NJ], wb[R][NJ];
+    uint32_t sa[R][NJ], sb[R][NJ];
+    gemv_issue_f4<NJ, R, WPR>(rows0, srows0, I, wa, sa);
+    gemv_issue_f4<NJ, R, WPR>(rows1, srows1, I, wb, sb);
+    // one chunk slot of activations at a time (32 registers, not 32 NJ): acc[r] += w'[r][slot] . h[slot]
+    auto fma_slots = [&](const float* __restrict__ h, const uint4 (&w)[R][NJ], const uint32_t (&s)[R][NJ], float (&acc)[R])
+                         __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) acc[r] = 0.f;
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            const int c = tl + j * P;
+            float x[32];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (c * 32 < I) v = reinterpret_cast<const f32x4*>(h)[c * 8 + i];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) x[i * 4 + q] = v[q];
+            }
+#pragma unroll
+            for (int r = 0; r < R; ++r) acc[r] += dot32_f4_f32(w[r][j], s[r][j], x);
+        }
+    };
+    float tot[R];
+    {
+        float acc[R];
+        fma_slots(hbuf, wa, sa, acc);
+#pragma unroll
+        for (int r = 0; r < R; ++r) tot[r] = w0 * acc[r];
+    }
+    {
+        float acc[R];
+        fma_slots(hbuf + (size_t)I, wb, sb, acc);
+#pragma unroll
+        for (int r = 0; r < R; ++r) tot[r] = fmaf(w1, acc[r], tot[r]);
+    }
+    // the thread sum is linear, so the routing weights were applied per thread above
+    const float wv = MultiReduce<R, 0>::run(tot, lane);
+    const int idx = multi_idx<R>(lane);
+    if (idx < R) red[wid * R + idx] = wv;
+    __syncthreads();
+    const int n = blockIdx.x * RB + threadIdx.x;
+    if ((int)threadIdx.x < RB && n < N) {
+        const int gg = threadIdx.x / R, r = threadIdx.x - gg * R;
+        float v = 0.f;
+#pragma unroll
+        for (int k = 0; k < WPR; ++k) v += red[(gg * WPR + k) * R + r];
+        if (px.world) xchg_put(px, n, v);
+        else out[n] = v;
+    }
+}
+
 // (r06 experiment, removed: gate|up and down of a tensor-parallel shard as ONE launch — down blocks behind the gate|up blocks of one grid,
 // W2 rows requested once block 0 had published the route as granules, h read as tagged granules.  Bit-identical, and SLOWER: one rank's
 // TP = 8 shard 1.369 against 1.313 ms per token, TP = 4 2.233 against 1.808 — 512-1024 resident down blocks poll the route and then h for
@@ -1355,6 +1574,9 @@ constexpr int DEC_GEMV_R = 8;
 // measured SLOWER at every degree: one rank's TP = 8 / 4 / 2 shard 1.316 / 1.831 / 2.871 against 1.287 / 1.788 / 2.790 ms per token; removed)
 // int8 experts: 8 + 8 rows per gate|up group and 4 rows per expert in the down blocks (the bf16 kernels' bytes in flight)
 constexpr int DEC_I8_RP = 8, DEC_I8_R = 4;
+// MXFP4 experts: gate (= up) rows per iteration of k_dec_gateup_mxfp4 (G groups of RP rows): K <= 2048 one wave per row and
+// 4 x 4 rows, K <= 4096 two waves and 2 x 8, K <= 8192 four waves and 8, above that 4 (two chunk slots per thread)
+static int dec_f4_rows_it(int K) { return K <= 4096 ? 16 : K <= 8192 ? 8 : 4; }
 static int dec_gateup_grid(int I, int rp = 4) {   // rp: gate (= up) rows per group of the kernel (4 bf16, 8 int8)
     // 1.5 persistent blocks per CU: every block pays the router prologue (96 KB of L2 reads), so fewer, longer-lived
     // blocks win — r01: 79 us at 512 blocks vs 83 at 1024 and 82 at 1280; r02 (cheaper block reductions): whole-token rate
@@ -1370,12 +1592,21 @@ static int dec_gateup_grid(int I, int rp = 4) {   // rp: gate (= up) rows per gr
     }
     return grid > n_iter ? n_iter : grid;
 }
+// MXFP4 gate|up: 3 persistent blocks per CU when there are more than 6 row groups per CU (measured at TP = 1, 1792 groups: a decode
+// step 3.79 / 3.54 / 3.28 / 3.45 ms at 384 / 512 / 768 / 1024 blocks: the conversion makes a group's FMA phase longer than the bf16 and
+// int8 kernels', and more resident blocks cover it with loads); a tensor-parallel shard's few groups as for the other formats
+static int dec_gateup_grid_f4(int I, int K) {
+    const int rows_it = dec_f4_rows_it(K);
+    const int n_iter = 2 * (I / rows_it), cus = vh_num_cus();
+    if (vh_tuning()->dec_gateup_grid <= 0 && n_iter > 6 * cus) return 3 * cus;
+    return dec_gateup_grid(I, rows_it);
+}
 // blocks of a consumer launch: the fused exchange's reducers are its first min(16, blocks) blocks
 int vhk_dec_consumer_blocks(int which, int N, int K, int I) {
-    (void)K;
     if (which == 0) return (N + DEC_GEMV_R - 1) / DEC_GEMV_R;
     if (which == 1) return dec_gateup_grid(I);
     if (which == 4) return dec_gateup_grid(I, DEC_I8_RP);   // gate|up on int8 experts
+    if (which == 5) return dec_gateup_grid_f4(I, K);   // gate|up on MXFP4 experts
     if (which == 3) return N;   // fused attention block: at least the fused-QKV blocks (N = their count) come first
     return N;   // LM head: the caller's grid
 }
@@ -1486,6 +1717,44 @@ int vhk_dec_down_i8(hipStream_t st, const float* hbuf, const int* route, const i
     return pick_nj(I, [&](auto nj) {
         hipLaunchKernelGGL((k_dec_down_i8<decltype(nj)::value, DEC_I8_R>), dim3((N + DEC_I8_R - 1) / DEC_I8_R), dim3(256), 0, st,
                            hbuf, route, W2, s2, N, I, row_stride, out, px);
+        return 0;
+    });
+}
+
+// MXFP4 experts: (NJ8 of the router prologue, chunk slots NJ, waves per row WPR) by K
+template <typename F>
+static int pick_f4(int K, F&& f) {
+    using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
+    using I4 = std::integral_constant<int, 4>; using I7 = std::integral_constant<int, 7>;
+    if (K <= 2048) return f(I1{}, I1{}, I1{});
+    if (K <= 4096) return f(I2{}, I1{}, I2{});
+    if (K <= 8192) return f(I4{}, I1{}, I4{});
+    if (K <= 14336) return f(I7{}, I2{}, I4{});
+    return -1;
+}
+int vhk_dec_gateup_mxfp4(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
+                         const uint16_t* Wg, int E, const uint8_t* W1, const uint8_t* S1, const uint8_t* W3, const uint8_t* S3, int I,
+                         int K, int* route_out, float* hbuf, int grid, const VhXchg* cxp) {
+    const int rows_it = dec_f4_rows_it(K);
+    if (E > 8 || E < 2 || I % rows_it != 0 || K % 32 != 0) return -1;
+    const int n_iter = 2 * (I / rows_it);
+    const VhXchg cx = xchg_or_none(cxp);
+    if (grid <= 0) grid = dec_gateup_grid_f4(I, K);
+    if (grid > n_iter) grid = n_iter;
+    return pick_f4(K, [&](auto nj8, auto nj, auto wpr) {
+        hipLaunchKernelGGL((k_dec_gateup_mxfp4<decltype(nj8)::value, decltype(nj)::value, decltype(wpr)::value>), dim3(grid), dim3(256),
+                           0, st, x_in, delta, x_out, norm_w, eps, Wg, E, W1, S1, W3, S3, I, K, route_out, hbuf, cx);
+        return 0;
+    });
+}
+int vhk_dec_down_mxfp4(hipStream_t st, const float* hbuf, const int* route, const uint8_t* W2, const uint8_t* S2, int N, int I,
+                       long row_stride, float* out, const VhXchg* pxp) {
+    if (I % 32 != 0 || N < 1 || row_stride < N) return -1;
+    const VhXchg px = xchg_or_none(pxp);
+    return pick_f4(I, [&](auto, auto nj, auto wpr) {
+        constexpr int RB = decltype(nj)::value == 2 ? 4 : 8;     // output rows per block (k_dec_down_mxfp4)
+        hipLaunchKernelGGL((k_dec_down_mxfp4<decltype(nj)::value, decltype(wpr)::value>), dim3((N + RB - 1) / RB), dim3(256), 0, st, hbuf,
+                           route, W2, S2, N, I, row_stride, out, px);
         return 0;
     });
 }

@@ -728,6 +728,49 @@ __global__ __launch_bounds__(256) void k_quant_rows_i8(const uint16_t* __restric
     }
 }
 
+// ---- MXFP4 expert weights: e2m1 codes with one E8M0 scale byte per 32 consecutive elements of a row ------------
+// amax over the block, se = max(floor(log2 amax) - 2, -125) from the exponent field (0 for a zero block), byte = se + 127,
+// v = |w| 2^-se (exact) saturated at 6 and rounded to the nearest e2m1 magnitude, ties to the even code; the sign bit only with
+// a non-zero magnitude (tests/q4_ref.py is matched bit for bit).  A thread takes 8 elements (16 bytes in, 4 bytes out), the four
+// lanes of a block share the amax; only the columns [col0, col0 + ncols) are read and written.
+__global__ __launch_bounds__(256) void k_quant_mxfp4(const uint16_t* __restrict__ w, long ld_src, int col0, int pieces, long total,
+                                                     uint8_t* __restrict__ codes, long ld_codes, uint8_t* __restrict__ scales,
+                                                     long ld_scales) {
+    // grid-stride; total % 4 == 0 and the stride is a multiple of 256: the four lanes of a block stay together
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long r = idx / pieces;
+        const int p = (int)(idx - r * pieces);
+        const uint4 raw = *reinterpret_cast<const uint4*>(w + r * ld_src + col0 + p * 8);
+        const uint32_t wd[4] = {raw.x, raw.y, raw.z, raw.w};
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            v[2 * i] = __uint_as_float(wd[i] << 16);
+            v[2 * i + 1] = __uint_as_float(wd[i] & 0xffff0000u);
+        }
+        float mx = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) mx = fmaxf(mx, fabsf(v[i]));
+        mx = fmaxf(mx, __shfl_xor(mx, 1));
+        mx = fmaxf(mx, __shfl_xor(mx, 2));
+        const int ef = (int)((__float_as_uint(mx) >> 23) & 0xffu);
+        int se = ef - 127 - 2;
+        if (se < -125) se = -125;                      // (a bf16 denormal amax included: its floor(log2) is below -126)
+        if (mx == 0.f) se = 0;
+        const float inv = __uint_as_float((uint32_t)(127 - se) << 23);   // 2^-se, a normal number for se in [-125, 125]
+        uint32_t out = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float a = fminf(fabsf(v[i]) * inv, 6.0f);
+            const uint32_t m = (a > 0.25f) + (a >= 0.75f) + (a > 1.25f) + (a >= 1.75f) + (a > 2.5f) + (a >= 3.5f) + (a > 5.0f);
+            const uint32_t sg = (v[i] < 0.f && m != 0) ? 8u : 0u;
+            out |= (sg | m) << (4 * i);
+        }
+        *reinterpret_cast<uint32_t*>(codes + r * ld_codes + p * 4) = out;
+        if ((p & 3) == 0) scales[r * ld_scales + (p >> 2)] = (uint8_t)(se + 127);
+    }
+}
+
 }  // namespace
 
 int vhk_layernorm(hipStream_t st, const float* x, long ldx, float* y, long ldy, const float* w, const float* b,
@@ -775,6 +818,19 @@ int vhk_quant_rows_i8(hipStream_t st, const uint16_t* w, long rows, int cols, lo
         return -1;
     if (rows == 0) return 0;
     hipLaunchKernelGGL(k_quant_rows_i8, dim3((unsigned)rows), dim3(256), 0, st, w, cols, ld_src, col0, ncols, q, ld_dst, s);
+    return 0;
+}
+int vhk_quant_mxfp4(hipStream_t st, const uint16_t* w, long rows, int cols, long ld_src, int col0, int ncols, uint8_t* codes,
+                    long ld_codes, uint8_t* scales, long ld_scales) {
+    if (rows < 0 || rows > 0x7fffffffL || cols < 1 || ld_src < cols || (ld_src % 8) != 0 || col0 < 0 || ncols < 1 || col0 + ncols > cols ||
+        (col0 % 32) != 0 || (ncols % 32) != 0 || ld_codes < ncols / 2 || (ld_codes % 4) != 0 || ld_scales < ncols / 32 ||
+        (reinterpret_cast<uintptr_t>(w) & 15) != 0 || (reinterpret_cast<uintptr_t>(codes) & 3) != 0)
+        return -1;
+    if (rows == 0) return 0;
+    const int pieces = ncols / 8;
+    const long total = rows * pieces;
+    hipLaunchKernelGGL(k_quant_mxfp4, dim3(grid_for(total, 256)), dim3(256), 0, st, w, ld_src, col0, pieces, total, codes, ld_codes,
+                       scales, ld_scales);
     return 0;
 }
 int vhk_cast_bf16_f32(hipStream_t st, const uint16_t* in, float* out, long n) {

@@ -42,9 +42,11 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;   // 8 int8 weig
 
 // I8: int8 weights (q) — the stagers load 8 bytes per piece and convert them to bf16 (exact: |q| <= 127) as they store
 // the SAME LDS image; the epilogue applies the group's column scales.  Everything else is the bf16 kernel's.
-template <bool GLU, int RTMAX, int RTW, int RTA, bool NTW, bool I8 = false>
+// F4: MXFP4 weights — the stagers load 4 bytes of codes per piece plus the piece's scale byte and convert them to 8 bf16
+// (exact: an e2m1 value times a power of two) as they store the same LDS image; the epilogue is the bf16 one.
+template <bool GLU, int RTMAX, int RTW, int RTA, bool NTW, bool I8 = false, bool F4 = false>
 __device__ __forceinline__ void run_tile_sp(const VhGemmPsArgs& p, const TileCtx& t, unsigned char* lds, const int lane,
-                                            const int wid, const VhPsI8* q8 = nullptr) {
+                                            const int wid, const VhPsI8* q8 = nullptr, const VhPsF4* q4 = nullptr) {
     constexpr int A_BUF = RTMAX * 2 * MG_SUB;    // one activation stage: hi sub-tiles then lo sub-tiles
     constexpr int W_BASE = 2 * A_BUF;
     constexpr int LDS_BYTES = 2 * A_BUF + SP_NSLOT * MG_SLOT;
@@ -129,7 +131,114 @@ __device__ __forceinline__ void run_tile_sp(const VhGemmPsArgs& p, const TileCtx
         return;
     }
 
-    if (I8 && wid < 10) {
+    if (F4 && wid < 10) {
+        // ================================ MXFP4 weight stagers: the schedule of the bf16 stagers below ==================
+        // piece q = 2 * s16 + u as there; its 16-byte bf16 chunk ch = (lane & 7) ^ (row >> 1) is 4 BYTES of the code row, and the scale
+        // block of the chunk is (stage, ch >> 2): a 64-wide K stage holds two blocks per row.  The 32 pieces are held as loaded
+        // (32 code + 32 scale VGPRs) and converted one at a time as they are stored (v_cvt_scalef32_pk_bf16_fp4: 4 per piece).
+        const int g = wid - 8;
+        const size_t goff = (size_t)t.e * (size_t)p.w_group_stride;
+        const unsigned char* w_gate = q4->W + (goff >> 1);
+        const unsigned char* w_up = (GLU ? q4->W_up : q4->W) + (goff >> 1);
+        const unsigned char* s_gate = q4->S + (goff >> 5);
+        const unsigned char* s_up = (GLU ? q4->S_up : q4->S) + (goff >> 5);
+        const uint32_t ldc1 = (uint32_t)(p.ldw >> 1), lds1 = (uint32_t)(p.ldw >> 5);
+        uint32_t wcol[2], scol[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const uint32_t ch = (uint32_t)((lane & 7) ^ (((u * 8 + lrow) >> 1) & 7));
+            wcol[u] = ch * 4;
+            scol[u] = ch >> 2;
+        }
+        uint32_t wreg[32], sreg[32];
+#pragma unroll
+        for (int q = 0; q < 32; ++q) { wreg[q] = 0u; sreg[q] = 0u; }
+        auto row_of = [&](int s16, int u, int lr) __attribute__((always_inline)) {
+            int n = GLU ? t.n0 + (s16 >> 2) * 32 + (s16 & 1) * 16 + u * 8 + lr : t.n0 + s16 * 16 + u * 8 + lr;
+            if (n > p.N - 1) n = p.N - 1;                                // clamped rows: products never stored
+            return (uint32_t)n;
+        };
+        auto ld4 = [&](const unsigned char* base, uint32_t n, int u) __attribute__((always_inline)) {
+            const uint32_t o = n * ldc1 + wcol[u];
+            if (NTW) return __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(base + o));
+            return *reinterpret_cast<const uint32_t*>(base + o);
+        };
+        auto cvt = [](const uint32_t wd, const uint32_t sb) __attribute__((always_inline)) {   // 8 codes -> 8 bf16 (exact)
+            const float sc = __uint_as_float(sb << 23);
+            u32x4 o;
+            o[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wd, sc, 0));
+            o[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wd, sc, 1));
+            o[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wd, sc, 2));
+            o[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(wd, sc, 3));
+            return o;
+        };
+        auto w_load = [&](int kt) __attribute__((always_inline)) {
+            const int kc = kt < t.nk ? kt : t.nk - 1;
+            const size_t kb = (size_t)(t.k0 + kc) * 32, ksb = (size_t)(t.k0 + kc) * 2;
+            int lr = lrow;
+            asm volatile("" : "+v"(lr));
+#pragma unroll
+            for (int q = 0; q < 32; ++q) {
+                const int s16 = q >> 1, u = q & 1;
+                const bool up = GLU && (s16 & 2);
+                const uint32_t n = row_of(s16, u, lr);
+                wreg[q] = ld4((up ? w_up : w_gate) + kb, n, u);
+                sreg[q] = ((up ? s_up : s_gate) + ksb)[n * lds1 + scol[u]];
+            }
+        };
+        unsigned char* const wr_dst0 = lds + W_BASE + lane * 16;
+        auto w_store = [&](int kt) __attribute__((always_inline)) {
+#pragma unroll
+            for (int q = 0; q < 32; ++q) {
+                const int s16 = q >> 1, u = q & 1;
+                *reinterpret_cast<u32x4*>(wr_dst0 + (((2 * kt) & 3) + (s16 >> 3)) * MG_SLOT + (s16 & 7) * MG_SUB + u * 1024) =
+                    cvt(wreg[q], sreg[q]);
+            }
+        };
+        {
+            const size_t kb = (size_t)t.k0 * 32, ksb = (size_t)t.k0 * 2;
+            int lr = lrow;
+            asm volatile("" : "+v"(lr));
+#pragma unroll
+            for (int qq = 0; qq < 16; ++qq) {
+                const int s16 = 8 * g + (qq >> 1), u = qq & 1;
+                const bool up = GLU && (s16 & 2);
+                const uint32_t n = row_of(s16, u, lr);
+                wreg[qq] = ld4((up ? w_up : w_gate) + kb, n, u);
+                sreg[qq] = ((up ? s_up : s_gate) + ksb)[n * lds1 + scol[u]];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int qq = 0; qq < 16; ++qq) {
+                const int s16 = qq >> 1, u = qq & 1;
+                *reinterpret_cast<u32x4*>(wr_dst0 + g * MG_SLOT + s16 * MG_SUB + u * 1024) = cvt(wreg[qq], sreg[qq]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        w_load(1 + g);
+        __builtin_amdgcn_sched_barrier(0);
+        int k = g;
+        if (g == 1) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+        }
+        for (; k < t.nk; k += 2) {
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            if (k + 1 < t.nk) {
+                w_store(k + 1);
+                __builtin_amdgcn_sched_barrier(0);
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                __builtin_amdgcn_sched_barrier(0);
+                w_load(k + 3);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+    } else if (I8 && wid < 10) {
         // ================================ int8 weight stagers: the schedule of the bf16 stagers below ===================
         // piece q = 2 * s16 + u as there; its 16-byte bf16 chunk (lane & 7) ^ (row >> 1) is 8 BYTES of the int8 row.  The 32 pieces
         // are held as loaded (64 VGPRs) and converted one at a time as they are stored.
@@ -408,16 +517,40 @@ void k_gemm_sp_i8(const VhGemmPsArgs p, const VhPsI8 q8) {
     });
 }
 
+// MXFP4 weights: the same kernel with the fp4 stagers (the bf16 epilogue)
+template <bool GLU, int RTMAX, bool NTW>
+__global__ __launch_bounds__(64 * SP_WAVES) __attribute__((amdgpu_waves_per_eu(3, 3)))
+void k_gemm_sp_mxfp4(const VhGemmPsArgs p, const VhPsF4 q4) {
+    constexpr int A_BUF = RTMAX * 2 * MG_SUB;
+    static_assert(2 * A_BUF + SP_NSLOT * MG_SLOT <= MG_LDS && (RTMAX % 2) == 0, "LDS budget / ring geometry");
+    __shared__ __attribute__((aligned(1024))) unsigned char lds[2 * A_BUF + SP_NSLOT * MG_SLOT];
+    const int lane = threadIdx.x & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    for_each_tile<GLU, RTMAX>(p, [&](const TileCtx& t) __attribute__((always_inline)) {
+        switch (t.rt) {
+#define SP_CASE(RT)                                                                                                                  \
+    case RT:                                                                                                                         \
+        if constexpr (RTMAX >= RT) run_tile_sp<GLU, RTMAX, (RT + 1) / 2, RT / 2, NTW, false, true>(p, t, lds, lane, wid, nullptr, &q4); \
+        break;
+            SP_CASE(1) SP_CASE(2) SP_CASE(3) SP_CASE(4) SP_CASE(5) SP_CASE(6)
+            SP_CASE(7) SP_CASE(8) SP_CASE(9) SP_CASE(10) SP_CASE(11) SP_CASE(12)
+#undef SP_CASE
+            default: break;
+        }
+    });
+}
+
 }  // namespace
 
-// why vhk_gemm_ps_i8 refuses these arguments (nullptr: it takes them).  Every check runs before anything is launched or written.
-const char* vhk_gemm_ps_i8_refusal(const VhGemmPsArgs& a, const VhPsI8& q) {
+// What the int8 and the MXFP4 form refuse alike, in two parts so that each form's own checks (alignment, weight and scale pointers)
+// keep their place in the order: the shape first, everything after the weights last.
+static const char* ps_q_refusal_shape(const VhGemmPsArgs& a) {
     if (a.K <= 0 || a.K % 64 != 0) return "K must be a positive multiple of 64";
     if (a.M < 0 || a.N <= 0) return "M < 0 or N <= 0";
-    if ((a.lda % 8) != 0 || (a.ldw % 8) != 0) return "lda % 8 / ldw % 8 alignment";
-    if (a.W || a.W_up || !q.W || !q.s || (q.W_up != nullptr) != (q.s_up != nullptr)) return "weight / scale pointers";
+    return nullptr;
+}
+static const char* ps_q_refusal_rest(const VhGemmPsArgs& a, bool glu) {
     if (!a.A_hi || !a.A_lo || (!a.C && !a.C_hi) || (a.C_hi && !a.C_lo)) return "activation / output pointers";
-    const bool glu = q.W_up != nullptr;
     const int ksplit = a.ksplit == 0 ? 1 : a.ksplit;
     if (ksplit < -8) return "ksplit below -8";
     if ((ksplit > 1 || ksplit < 0) && (glu || a.bias || a.scale || a.resid || a.act != VH_ACT_NONE || a.C_hi || !a.C))
@@ -428,11 +561,12 @@ const char* vhk_gemm_ps_i8_refusal(const VhGemmPsArgs& a, const VhPsI8& q) {
     if ((size_t)a.ldw * (size_t)a.N >= (1ull << 32)) return "ldw * N reaches 2^32";      // 32-bit per-lane byte offsets inside one group
     return nullptr;
 }
-
-int vhk_gemm_ps_i8(hipStream_t st, const VhGemmPsArgs& a0, const VhPsI8& q) {
+// The launch both forms share, for arguments that passed the form's refusal: the default K split, the grid, the row-tile cap of an
+// ungrouped call, the XCD grouping and the non-temporal weight loads; launch(GLU, NT, grid, args) starts the form's kernel.
+template <typename L>
+static int ps_q_launch(const VhGemmPsArgs& a0, bool glu, L&& launch) {
+    using T = std::true_type; using F = std::false_type;
     VhGemmPsArgs a = a0;
-    if (vhk_gemm_ps_i8_refusal(a, q)) return -1;
-    const bool glu = q.W_up != nullptr;
     if (a.ksplit == 0) a.ksplit = 1;
     if (a.M == 0) return 0;
     int grid = vh_num_cus() & ~7;
@@ -446,13 +580,45 @@ int vhk_gemm_ps_i8(hipStream_t st, const VhGemmPsArgs& a0, const VhPsI8& q) {
     a.xcd_group = a.group_off ? ((glu ? (px >> 1) : px) & 1) : 0;
     const bool nt = vh_tuning()->ps_nt > 0;
     if (glu) {
-        if (nt) hipLaunchKernelGGL((k_gemm_sp_i8<true, 12, true>), dim3(grid), dim3(64 * SP_WAVES), 0, st, a, q);
-        else hipLaunchKernelGGL((k_gemm_sp_i8<true, 12, false>), dim3(grid), dim3(64 * SP_WAVES), 0, st, a, q);
+        if (nt) launch(T{}, T{}, grid, a);
+        else launch(T{}, F{}, grid, a);
     } else {
-        if (nt) hipLaunchKernelGGL((k_gemm_sp_i8<false, 12, true>), dim3(grid), dim3(64 * SP_WAVES), 0, st, a, q);
-        else hipLaunchKernelGGL((k_gemm_sp_i8<false, 12, false>), dim3(grid), dim3(64 * SP_WAVES), 0, st, a, q);
+        if (nt) launch(F{}, T{}, grid, a);
+        else launch(F{}, F{}, grid, a);
     }
     return 0;
+}
+
+// why vhk_gemm_ps_mxfp4 refuses these arguments (nullptr: it takes them): the rules of vhk_gemm_ps_i8_refusal, and ldw % 64 == 0 (code
+// rows are multiples of 32 bytes, scale rows hold whole stages).  Every check runs before anything is launched or written.
+const char* vhk_gemm_ps_mxfp4_refusal(const VhGemmPsArgs& a, const VhPsF4& q) {
+    if (const char* why = ps_q_refusal_shape(a)) return why;
+    if ((a.lda % 8) != 0 || (a.ldw % 64) != 0 || (a.w_group_stride % 64) != 0) return "lda % 8 / ldw % 64 / w_group_stride % 64 alignment";
+    if (a.ldw < a.K) return "ldw below K";
+    if (a.W || a.W_up || !q.W || !q.S || (q.W_up != nullptr) != (q.S_up != nullptr)) return "weight / scale pointers";
+    return ps_q_refusal_rest(a, q.W_up != nullptr);
+}
+
+int vhk_gemm_ps_mxfp4(hipStream_t st, const VhGemmPsArgs& a0, const VhPsF4& q) {
+    if (vhk_gemm_ps_mxfp4_refusal(a0, q)) return -1;
+    return ps_q_launch(a0, q.W_up != nullptr, [&](auto glu, auto nt, int grid, const VhGemmPsArgs& a) {
+        hipLaunchKernelGGL((k_gemm_sp_mxfp4<decltype(glu)::value, 12, decltype(nt)::value>), dim3(grid), dim3(64 * SP_WAVES), 0, st, a, q);
+    });
+}
+
+// why vhk_gemm_ps_i8 refuses these arguments (nullptr: it takes them).  Every check runs before anything is launched or written.
+const char* vhk_gemm_ps_i8_refusal(const VhGemmPsArgs& a, const VhPsI8& q) {
+    if (const char* why = ps_q_refusal_shape(a)) return why;
+    if ((a.lda % 8) != 0 || (a.ldw % 8) != 0) return "lda % 8 / ldw % 8 alignment";
+    if (a.W || a.W_up || !q.W || !q.s || (q.W_up != nullptr) != (q.s_up != nullptr)) return "weight / scale pointers";
+    return ps_q_refusal_rest(a, q.W_up != nullptr);
+}
+
+int vhk_gemm_ps_i8(hipStream_t st, const VhGemmPsArgs& a0, const VhPsI8& q) {
+    if (vhk_gemm_ps_i8_refusal(a0, q)) return -1;
+    return ps_q_launch(a0, q.W_up != nullptr, [&](auto glu, auto nt, int grid, const VhGemmPsArgs& a) {
+        hipLaunchKernelGGL((k_gemm_sp_i8<decltype(glu)::value, 12, decltype(nt)::value>), dim3(grid), dim3(64 * SP_WAVES), 0, st, a, q);
+    });
 }
 
 // arguments already checked by vhk_gemm_ps (vh_gemm_ps.hip)

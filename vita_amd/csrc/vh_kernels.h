@@ -101,7 +101,7 @@ int vh_comm_is_loopback(const vh_comm* c);        // a single-rank communicator 
 // cx (nullable): the delta is the result of a fused exchange (then `delta` is ignored); px (nullable): push the outputs
 int vhk_dec_qkv(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
                 const uint16_t* W, int N, int K, float* out, const VhXchg* cx = nullptr);
-int vhk_dec_consumer_blocks(int which, int N, int K, int I);   // grid of a consumer launch (0 qkv, 1 gate|up, 2 lm head, 3 fused attention block, 4 int8 gate|up): bounds nred
+int vhk_dec_consumer_blocks(int which, int N, int K, int I);   // grid of a consumer launch (0 qkv, 1 gate|up, 2 lm head, 3 fused attention block, 4 int8 gate|up, 5 MXFP4 gate|up: K = hidden): bounds nred
 int vhk_dec_attn(hipStream_t st, const float* qkv, float* kcache, float* vcache, const int* pos_ptr,
                  const float* rope_cos, const float* rope_sin, float* part_o, float* part_ml, int* cnt,
                  float* attn_out, int nq, int nkv, int max_ctx, int max_splits, int ctx_host, float scale,
@@ -185,6 +185,13 @@ int vhk_dec_gateup_i8(hipStream_t st, const float* x_in, const float* delta, flo
 // W2 / s2: the first of the N rows this call computes (a column slice of the experts' [Ntot][I]); row_stride = rows per expert (Ntot)
 int vhk_dec_down_i8(hipStream_t st, const float* hbuf, const int* route, const int8_t* W2, const float* s2, int N, int I,
                     long row_stride, float* out, const VhXchg* px = nullptr);
+// MXFP4 experts: e2m1 codes W [rows][K / 2] (element k in byte k >> 1, low nibble for even k) and E8M0 scale bytes
+// S [rows][K / 32]; w' = e2m1(code) * 2^(byte - 127) is formed where the weights are converted, so there is no epilogue scale
+int vhk_dec_gateup_mxfp4(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
+                         const uint16_t* Wg, int E, const uint8_t* W1, const uint8_t* S1, const uint8_t* W3, const uint8_t* S3, int I,
+                         int K, int* route_out, float* hbuf, int grid, const VhXchg* cx = nullptr);
+int vhk_dec_down_mxfp4(hipStream_t st, const float* hbuf, const int* route, const uint8_t* W2, const uint8_t* S2, int N, int I,
+                       long row_stride, float* out, const VhXchg* px = nullptr);
 int vhk_dec_lmhead(hipStream_t st, const float* x_in, const float* delta, const float* norm_w, float eps,
                    const uint16_t* W, int V, int K, float* logits, float* blk_val, int* blk_idx, int grid,
                    const int* ngen_ptr, int hist_rows, int v0, int Vfull, const VhXchg* cx = nullptr,
@@ -259,6 +266,18 @@ const char* vhk_gemm_ps_i8_refusal(const VhGemmPsArgs& a, const VhPsI8& q);   //
 // w[rows][ld_src] bf16 -> q[rows][ld_dst] int8 (columns [col0, col0 + ncols)) + s[rows] fp32, the scale over all `cols`
 int vhk_quant_rows_i8(hipStream_t st, const uint16_t* w, long rows, int cols, long ld_src, int col0, int ncols, int8_t* q,
                       long ld_dst, float* s);
+// MXFP4 expert weights: a.W / a.W_up are null, a.ldw / a.w_group_stride count WEIGHTS (a code row is ldw / 2 bytes, a
+// scale row ldw / 32 bytes, a group w_group_stride / 2 and / 32 bytes); the stager converts 8 codes and their block's scale byte to
+// 8 bf16 (exact) into the same LDS image; the epilogue is the bf16 kernel's.  Always the specialised form.
+struct VhPsF4 {
+    const uint8_t* W; const uint8_t* W_up;   // codes
+    const uint8_t* S; const uint8_t* S_up;   // scale bytes
+};
+int vhk_gemm_ps_mxfp4(hipStream_t st, const VhGemmPsArgs& a, const VhPsF4& q);
+const char* vhk_gemm_ps_mxfp4_refusal(const VhGemmPsArgs& a, const VhPsF4& q);   // nullptr, or why vhk_gemm_ps_mxfp4 returns -1
+// w[rows][ld_src] bf16, columns [col0, col0 + ncols) (multiples of 32) -> codes[rows][ld_codes bytes], scales[rows][ld_scales]
+int vhk_quant_mxfp4(hipStream_t st, const uint16_t* w, long rows, int cols, long ld_src, int col0, int ncols, uint8_t* codes,
+                    long ld_codes, uint8_t* scales, long ld_scales);
 int vhk_split_planes(hipStream_t st, const float* x, long ldx, uint16_t* hi, uint16_t* lo, long ldo, int rows,
                      int cols);
 

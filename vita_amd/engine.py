@@ -8,7 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MixtralCfg, MixtralExpertsI8, MixtralLayer, check
+from ._lib import MixtralCfg, MixtralExpertsI8, MixtralExpertsMxfp4, MixtralLayer, check
 from .config import VitaConfig
 
 
@@ -60,26 +60,29 @@ class MixtralEngine:
         self.rope_cos = torch.from_numpy(cos).to(device)
         self.rope_sin = torch.from_numpy(sin).to(device)
         # int8 experts (pack_mixtral / synth_mixtral_device with experts="int8"): the layers' w1 / w3 / w2 are int8 with scales
-        self.experts = "int8" if lay0["w1"].dtype == torch.int8 else "bf16"
+        # MXFP4 experts (experts="mxfp4"): uint8 e2m1 codes with uint8 block scales
+        self.experts = {torch.int8: "int8", torch.uint8: "mxfp4"}.get(lay0["w1"].dtype, "bf16")
         layers = (MixtralLayer * t.num_hidden_layers)()
-        q8 = (MixtralExpertsI8 * t.num_hidden_layers)() if self.experts == "int8" else None
+        qstruct = {"int8": MixtralExpertsI8, "mxfp4": MixtralExpertsMxfp4}.get(self.experts)
+        q8 = (qstruct * t.num_hidden_layers)() if qstruct else None
         for i, L in enumerate(packed["layers"]):
             for f, _ in MixtralLayer._fields_:
                 if q8 is not None and f in ("w1", "w3", "w2"):
                     continue
                 setattr(layers[i], f, L[f].data_ptr())
             if q8 is not None:
-                for f, _ in MixtralExpertsI8._fields_:
+                for f, _ in qstruct._fields_:
                     setattr(q8[i], f, L[f].data_ptr())
-        self._layers, self._experts_i8 = layers, q8
+        self._layers, self._experts_q = layers, q8
         args = (packed["embed"].data_ptr(), packed["final_norm"].data_ptr(), packed["lm_head"].data_ptr(),
                 self.rope_cos.data_ptr(), self.rope_sin.data_ptr(), self.workspace.data_ptr(), nbytes)
+        create = {"int8": "vh_mixtral_create_i8", "mxfp4": "vh_mixtral_create_mxfp4"}.get(self.experts, "vh_mixtral_create")
         if q8 is not None:
-            self.h = self.lib.vh_mixtral_create_i8(C.byref(c), layers, q8, *args)
+            self.h = getattr(self.lib, create)(C.byref(c), layers, q8, *args)
         else:
             self.h = self.lib.vh_mixtral_create(C.byref(c), layers, *args)
         if not self.h:
-            check(-1, "vh_mixtral_create_i8" if q8 is not None else "vh_mixtral_create")
+            check(-1, create)
         self._ar_cb = None
         self._comm = None
         self.decode_exchange = "kernel"     # form of the batch-1 TP exchange under the IPC transport (vita_amd.parallel votes)

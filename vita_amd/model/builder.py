@@ -81,11 +81,16 @@ def load_pretrained_model(model_path, model_base, model_name, model_type, load_8
     if model_type not in {"mixtral-8x7b"}:
         raise ValueError(f"Unknown Model Type {model_type}")          # builder.py:25-26
     if load_4bit:
-        raise NotImplementedError("4-bit quantisation is not part of the HIP path")
+        # the reference's load_4bit is bitsandbytes NF4, another format; the 4-bit mode of this path is OCP MXFP4 on the experts
+        raise NotImplementedError("load_4bit (bitsandbytes NF4) is not part of the HIP path; the 4-bit expert mode is "
+                                  "experts_mxfp4=True (LLM(quantization='experts_mxfp4'), DESIGN 5.8)")
     # load_8bit: the MoE experts (88 % of a token's weight bytes) as int8 with per-output-row scales, quantised on the device
     # (DESIGN 5.5).  Not bitsandbytes' LLM.int8(): activations stay fp32 and there is no outlier split.
     if load_8bit:
         kwargs["experts_int8"] = True
+    # experts_mxfp4=True (a keyword, passed through): the experts as OCP MXFP4, 4.25 bits per weight
+    if kwargs.get("experts_int8") and kwargs.get("experts_mxfp4"):
+        raise ValueError("experts_int8 (load_8bit) and experts_mxfp4 are two expert formats: ask for one")
     if model_base is not None or "lora" in (model_name or "").lower():
         warnings.warn("LoRA merge is a training-side feature and is not reproduced; loading merged weights only")
     from transformers import AutoTokenizer

@@ -51,7 +51,7 @@ class _Backbone(_HipModule):
 class VITAMixtralForCausalLM(_HipModule):
     def __init__(self, cfg: VitaConfig, state_dict, device="cuda:0", packed_llm=None, max_new_tokens=1024,
                  max_prefill=None, rank=0, world=1, keep_scores=True, max_seqs=0, kv_pool_tokens=None,
-                 gpu_memory_utilization=None, experts_int8=False, penalty_tables=False, max_logprobs=0):
+                 gpu_memory_utilization=None, experts_int8=False, penalty_tables=False, max_logprobs=0, experts_mxfp4=False):
         super().__init__()
         from ..checkpoint import pack_mixtral
         self.vcfg_all = cfg
@@ -74,8 +74,10 @@ class VITAMixtralForCausalLM(_HipModule):
                 proj.load(state_dict, device)
             if any(k.startswith("model.audio_encoder.") for k in state_dict):
                 audio.load(state_dict, device)
+        if experts_int8 and experts_mxfp4:
+            raise ValueError("experts_int8 and experts_mxfp4 are two expert formats: ask for one")
         self.packed = packed_llm if packed_llm is not None else pack_mixtral(
-            state_dict, cfg, device, rank, world, experts="int8" if experts_int8 else "bf16")
+            state_dict, cfg, device, rank, world, experts="int8" if experts_int8 else "mxfp4" if experts_mxfp4 else "bf16")
         self.model = _Backbone(tower, proj, audio, self.packed["embed"])
         self.max_new_tokens = max_new_tokens
         self.max_prefill = max_prefill or cfg.tokenizer_model_max_length

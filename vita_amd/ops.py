@@ -462,6 +462,31 @@ def gemm_ps_i8(a_hi, a_lo, w, s, *, w_up=None, s_up=None, s_group_stride=0, bias
     return planes if out_split else out
 
 
+def gemm_ps_mxfp4(a_hi, a_lo, w, s, *, w_up=None, s_up=None, bias=None, act=None, scale=None, resid=None, out=None, out_split=False,
+                  a_rowidx=None, m=None, c_rowidx=None, group_off=None, ngroups=0, w_group_stride=0, ksplit=1, nslab_out=None,
+                  out_planes=None):
+    """gemm_ps on MXFP4 weights (vh_gemm_ps_mxfp4): w / w_up uint8 e2m1 codes [.., N, K / 2] (element k in byte k >> 1, low
+    nibble for even k), s / s_up uint8 E8M0 scale bytes [.., N, K / 32].  The row strides are taken from the tensors (a column range
+    of a wider matrix is a legal operand when the scales are the same range: s.stride(-2) * 16 == w.stride(-2)); w_group_stride
+    counts WEIGHTS.  The keywords are gemm_ps's without `wide`."""
+    _dev(a_hi, a_lo, w, s, w_up, s_up)
+    _bf16(a_hi, "a_hi"); _bf16(a_lo, "a_lo")
+    for t, nm in ((w, "w"), (w_up, "w_up"), (s, "s"), (s_up, "s_up")):
+        if t is not None and (t.dtype != torch.uint8 or t.stride(-1) != 1):
+            raise TypeError(f"{nm} must be uint8 with contiguous rows, got {t.dtype} strides {t.stride()}")
+    for cw, cs, nm in ((w, s, "s"), (w_up, s_up, "s_up")):
+        if (cw is None) != (cs is None):
+            raise ValueError("w_up and s_up go together")
+        if cw is not None and (cs.shape[-2] != cw.shape[-2] or cs.shape[-1] * 16 != cw.shape[-1] or cs.stride(-2) * 16 != cw.stride(-2)):
+            raise ValueError(f"{nm} must be [.., N, K / 32] with 1 / 16 of the codes' row stride, got {tuple(cs.shape)} strides {cs.stride()}")
+    g, planes, out = _gemm_ps_args(a_hi, a_lo, w, bias=bias, act=act, scale=scale, resid=resid, out=out, out_split=out_split,
+                                   a_rowidx=a_rowidx, m=m, c_rowidx=c_rowidx, group_off=group_off, ngroups=ngroups,
+                                   w_group_stride=w_group_stride, ksplit=ksplit, nslab_out=nslab_out, out_planes=out_planes)
+    g.K, g.ldw = 2 * int(w.shape[-1]), 2 * int(w.stride(-2))          # counted in weights, two per code byte
+    check(_lib.load().vh_gemm_ps_mxfp4(C.byref(g), _p(w), _p(s), _p(w_up), _p(s_up), _stream()), "vh_gemm_ps_mxfp4")
+    return planes if out_split else out
+
+
 # ---- batch-1 decode operators, one by one (include/vita_hip.h: "batch-1 decode operators") --------------------------------
 def router_top2(x, wg, want_probs=False):
     """MixtralSparseMoeBlock's gate on normed rows x [rows, H] fp32, wg bf16 [E, H] -> (ids int32 [rows, 2], weights fp32

@@ -184,8 +184,9 @@ class LLM:
         # holds pages (its error names reset_prefix_cache)
         self.enable_prefix_caching = bool(enable_prefix_caching)
         # vLLM's quantization="experts_int8": the MoE experts as int8 with per-output-row scales
-        if quantization not in (None, "experts_int8"):
-            raise ValueError(f"quantization={quantization!r}: vita_amd supports None and 'experts_int8'")
+        # "experts_mxfp4": the experts as OCP MXFP4 (e2m1 codes, one power-of-two scale per 32 weights)
+        if quantization not in (None, "experts_int8", "experts_mxfp4"):
+            raise ValueError(f"quantization={quantization!r}: vita_amd supports None, 'experts_int8' and 'experts_mxfp4'")
         world = int(os.environ.get("WORLD_SIZE", "1"))
         if tensor_parallel_size != 1 and tensor_parallel_size != world:
             raise RuntimeError(
@@ -201,6 +202,7 @@ class LLM:
             model, None, os.path.basename(str(model).rstrip("/")), "mixtral-8x7b", device=device,
             max_new_tokens=max_new_tokens, max_seqs=int(max_num_seqs), kv_pool_tokens=kv_pool_tokens,
             gpu_memory_utilization=gpu_memory_utilization, load_8bit=quantization == "experts_int8",
+            experts_mxfp4=quantization == "experts_mxfp4",
             # max_logprobs > 0 (vLLM's name): logprob buffers AND token tables for the engine and every sequence slot, so that
             # SamplingParams' penalties and logprobs run on the device; penalty_tables=True alone: the tables only
             max_logprobs=int(max_logprobs), penalty_tables=bool(max_logprobs) if penalty_tables is None else bool(penalty_tables), **kw)
@@ -395,7 +397,7 @@ class AsyncEngineArgs:
     kv_pool_tokens: Optional[int] = None     # size of the paged KV pool; default: max_num_seqs x (<= 1024-token prompt + max_new_tokens),
                                              # bounded by gpu_memory_utilization of the free memory (VITAMixtralForCausalLM.default_kv_pool_tokens)
     device: str = "cuda"
-    quantization: Optional[str] = None       # None or "experts_int8" (LLM)
+    quantization: Optional[str] = None       # None, "experts_int8" or "experts_mxfp4" (LLM)
     max_logprobs: int = 0                    # > 0 (<= 20): SamplingParams' penalties and logprobs on the device (LLM)
     enable_prefix_caching: bool = False      # reuse the KV pages of earlier prompts with the same leading rows (ContinuousBatcher)
 
