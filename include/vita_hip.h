@@ -110,8 +110,12 @@ int vh_gemm_ps_i8(const vh_gemm_ps_args* args, const int8_t* W, const float* s, 
  * of a row in byte k >> 1, low nibble for even k), S (and S_up) one E8M0 scale byte per 32 consecutive elements of a row; the
  * weight is e2m1(code) * 2^(byte - 127), code 8 (-0) reads as 0.  args->ldw / w_group_stride count WEIGHTS: a code row is ldw / 2
  * bytes, a scale row ldw / 32 bytes, a group w_group_stride / 2 and w_group_stride / 32 bytes.  The conversion to bf16 is exact, so
- * the result is vh_gemm_ps's on the dequantised weights.  Always the 12-wave specialised kernel.  Refused with VH_E_SHAPE, before
- * anything is launched or written: ldw % 64 != 0, w_group_stride % 64 != 0, ldw < K, and what vh_gemm_ps_i8 refuses. */
+ * the result is vh_gemm_ps's on the dequantised weights.  The contract covers scale bytes 2 to 252, which is what the quantiser
+ * emits plus the range in which every w' is a normal bf16 number; other bytes are outside it (the kernel builds the scale as
+ * byte << 23: byte 0 reads as 0.0 and 255 as Inf, byte 1 with code 1 is the bf16 denormal 2^-127, byte 253 with codes 6 and 7 and
+ * byte 254 from code 4 upward exceed the bf16 range).  Always the 12-wave specialised kernel.  Refused with VH_E_SHAPE, before
+ * anything is launched or written: ldw % 64 != 0, w_group_stride % 64 != 0, ldw < K, and what vh_gemm_ps_i8 refuses.  M == 0 is
+ * accepted and writes nothing. */
 int vh_gemm_ps_mxfp4(const vh_gemm_ps_args* args, const uint8_t* W, const uint8_t* S, const uint8_t* W_up, const uint8_t* S_up,
                      void* stream);
 
@@ -306,7 +310,9 @@ int vh_quant_rows_i8(const uint16_t* w, long rows, int cols, long ld_src, int co
  * even code); code = sign << 3 | index with the sign bit only for a non-zero magnitude.  The engine computes with
  * w' = e2m1(code) * 2^(byte - 127), which is a bf16 number.  Codes are uint8 [rows][K / 2] (element k in byte k >> 1, low nibble for
  * even k), scales uint8 [rows][K / 32].  A tensor-parallel rank's w2 column slice starts on a multiple of 32, so it stores the slice
- * of the codes and of the scales and every TP degree computes the same w'.  Activations stay fp32. */
+ * of the codes and of the scales and every TP degree computes the same w'.  Activations stay fp32.  The contract covers scale
+ * bytes 2 to 252, which is what the quantiser emits plus the range in which every w' is a normal bf16 number; other bytes are
+ * outside it. */
 typedef struct {
     const uint8_t* w1; const uint8_t* s1;   /* [n_experts][inter][hidden / 2] codes, [n_experts][inter][hidden / 32] scales */
     const uint8_t* w3; const uint8_t* s3;   /* as w1 / s1 */

@@ -45,7 +45,8 @@ CASES = {c.name: c for c in [
 # group) reach the specialised kernel's schedule only through the forced ps_cfg 2.
 TP_CASES = ("uniform", "skew")             # the TP shard widths and the overlap halves run on these two
 
-# ---- the int8 form's extra cases (tests/test_moe_gemm_i8_gpu.py; int8 ALWAYS runs the specialised kernel, at any row count) --------
+# ---- the int8 and MXFP4 forms' extra cases (tests/test_moe_gemm_i8_gpu.py, tests/test_moe_gemm_mxfp4_gpu.py; both ALWAYS run the
+# specialised kernel, at any row count) ---------------------------------------------------------------------------------------------
 # an iteration of a few concurrent sequences at the released widths: rows per expert (tests/test_ops_gpu.py:
 # test_gemm_ps_device_chosen_ksplit_few_rows)
 DECODE_CNTS = ((2, 0, 1, 0, 0, 2, 0, 1), (1, 1, 1, 0, 1, 1, 0, 1), (3, 2, 4, 1, 2, 1, 2, 1), (6, 0, 0, 0, 0, 0, 0, 0))
@@ -71,15 +72,19 @@ def small_cases():
     return out
 
 
-def i8_rt_cap(M, N, glu, ksplit, cus=256):
-    """vhk_gemm_ps_i8's row-tile cap of an UNGROUPED call with a fixed split: the smallest cap 3 .. 11 whose tiles still fit one round
-    (more, shorter m-tiles while blocks would idle); 0 = none (12)."""
+def ps_q_rt_cap(M, N, glu, ksplit, cus=256):
+    """the row-tile cap of an UNGROUPED call with a fixed split in the launcher the int8 and the MXFP4 form share (ps_q_launch in
+    vh_gemm_sp.hip): the smallest cap 3 .. 11 whose tiles still fit one round (more, shorter m-tiles while blocks would idle);
+    0 = none (12)."""
     grid = max(cus & ~7, 8)
     nrt, NT = (M + 15) >> 4, (N + (127 if glu else 255)) // (128 if glu else 256)
     for c in range(3, 12):
         if ((nrt + c - 1) // c) * NT * ksplit <= grid:
             return c
     return 0
+
+
+i8_rt_cap = ps_q_rt_cap      # the int8 tests' name of it
 
 
 def k_slices(K, KS):

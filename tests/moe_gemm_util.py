@@ -1,7 +1,8 @@
 """Machinery shared by the streaming MoE GEMM tests at the released widths (tests/test_moe_gemm_gpu.py: bf16 weights through
-ops.gemm_ps; tests/test_moe_gemm_i8_gpu.py: int8 weights through ops.gemm_ps_i8): tolerances, the vh_tune knob context, the seeded
-weight recipe, per-case operands with float64 references, and the gate|up / down runners with their checks.  What differs between
-the two forms — how the GEMM is called and which weights the reference sees — is passed in as callables."""
+ops.gemm_ps; tests/test_moe_gemm_i8_gpu.py: int8 weights through ops.gemm_ps_i8; tests/test_moe_gemm_mxfp4_gpu.py: MXFP4 weights
+through ops.gemm_ps_mxfp4): tolerances, the vh_tune knob context, the seeded weight recipe, per-case operands with float64
+references, and the gate|up / down runners with their checks.  What differs between the forms — how the GEMM is called and which
+weights the reference sees — is passed in as callables."""
 import math
 
 import torch
@@ -76,6 +77,30 @@ def glu_tol(g, u, gemm_tol):
     return gemm_tol * (dsilu.abs() * u.abs() + silu(g).abs()) + 2.0 ** -16 * (silu(g) * u).abs()
 
 
+E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def dq_mxfp4(codes, scales):
+    """w' = e2m1(code) 2^(byte - 127) in float64 on the tensors' device: packed codes uint8 [.., K / 2] (element k in byte k >> 1, low
+    nibble for even k), E8M0 scale bytes uint8 [.., K / 32] -> [.., K].  Code 8 (-0) is 0."""
+    lut = torch.tensor(E2M1 + tuple(-v for v in E2M1), dtype=torch.float64, device=codes.device)
+    c = torch.stack([codes & 15, codes >> 4], -1).reshape(*codes.shape[:-1], -1).long()
+    X = torch.pow(torch.tensor(2.0, dtype=torch.float64, device=codes.device), scales.double() - 127)
+    return (lut[c].reshape(*scales.shape, 32) * X.unsqueeze(-1)).reshape(c.shape)
+
+
+def mxfp4_probe(dev, N, K, shift, ring):
+    """the conversion probes' operand: codes [N, K / 2] with code (n + k + shift) % 16 at element k of row n, scale bytes [N, K / 32]
+    with ring[(block + n) % len(ring)]"""
+    k = torch.arange(K, device=dev)
+    n = torch.arange(N, device=dev)
+    code = ((n[:, None] + k[None, :] + shift) % 16).to(torch.uint8)
+    codes = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    ring = torch.tensor(ring, dtype=torch.uint8, device=dev)
+    scales = ring[(torch.arange(K // 32, device=dev)[None, :] + n[:, None]) % len(ring)].contiguous()
+    return codes, scales
+
+
 def make_weights(dev, plain=True):
     """w1, w3 [E, I, H] and w2 [E, H, I] bf16 (~2.8 GB) and, with plain, qkv [6144, H] and o [H, H] (drawn after the experts):
     N(0, 0.02^2) from one seeded generator."""
@@ -96,8 +121,9 @@ class CaseData:
     pass
 
 
-def build_case(dev, rows, seed, gate_up_w):
-    """operands and float64 gate|up reference of one routing (rows per expert).  gate_up_w(e) -> (w1[e], w3[e]) as float64 [I, H]."""
+def build_case(dev, rows, seed, gate_up_w, gemm_tol=None):
+    """operands and float64 gate|up reference of one routing (rows per expert).  gate_up_w(e) -> (w1[e], w3[e]) as float64 [I, H].
+    gemm_tol: the GEMM bound of g and u (atol(H) on the seeded recipe's rms unless the caller has its own weights' rms)."""
     from vita_amd import ops
     gen = torch.Generator(device=dev).manual_seed(seed)
     cg = torch.Generator().manual_seed(seed)
@@ -128,7 +154,7 @@ def build_case(dev, rows, seed, gate_up_w):
             u[goff[e]:goff[e + 1]] = xe @ w3.T
             del w3
     c.h_ref = silu(g) * u
-    c.h_tol = glu_tol(g, u, atol(H))
+    c.h_tol = glu_tol(g, u, atol(H) if gemm_tol is None else gemm_tol)
     del g, u
     # down: its own N(0, 1) input rows, scattered to (token, slot) rows of an output with guard rows no index targets
     hin = randn(gen, (M, I), dev)
@@ -174,9 +200,10 @@ def run_gateup(c, what, gemm, n0=0, n1=I):
         guard(f"{what} {nm} guard columns", b[:, N:])
 
 
-def run_down(c, what, ksplit, K, ref, gemm, n0=0, n1=H):
+def run_down(c, what, ksplit, K, ref, gemm, n0=0, n1=H, tol=None):
     """down projection (a K range of w2 of K columns, output columns [n0, n1)) scattered through c_rowidx into guarded slabs.
-    gemm(out, nslab) runs it (nslab: the device int of a device-chosen split, else None); ref: float64 [R, H] of that K range."""
+    gemm(out, nslab) runs it (nslab: the device int of a device-chosen split, else None); ref: float64 [R, H] of that K range;
+    tol: the bound (atol(K) on the seeded recipe's rms unless the caller has its own weights' rms)."""
     dev = c.hin.device
     N = n1 - n0
     nsl = abs(ksplit)
@@ -192,7 +219,8 @@ def run_down(c, what, ksplit, K, ref, gemm, n0=0, n1=H):
         guard(f"{what} slabs {ks}.. above the reported count", buf[ks:])
     elif ksplit <= 1:
         ks = 1
-    close(f"{what} down (ksplit {ksplit} -> {ks} slabs)", buf[:ks, :, :N].double().sum(0)[c.live], ref[:, n0:n1][c.live], atol(K))
+    close(f"{what} down (ksplit {ksplit} -> {ks} slabs)", buf[:ks, :, :N].double().sum(0)[c.live], ref[:, n0:n1][c.live],
+          atol(K) if tol is None else tol)
     guard(f"{what} guard rows", buf[:ks, ~c.live])
     guard(f"{what} guard columns", buf[:ks, :, N:])
     return ks

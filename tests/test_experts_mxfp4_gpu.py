@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import moe_gemm_cases as mc
+from tests import moe_gemm_util as mu
 from tests import mxfp4_cases as mx
 from tests import q4_ref
 from tests.util import assert_close, to_np
@@ -31,15 +32,7 @@ def _bf16(dev, shape, seed, std=0.02):
     return (torch.randn(shape, generator=g) * std).to(torch.bfloat16).to(dev)
 
 
-_E2M1 = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
-
-
-def _dq(codes, scales):
-    """w' in fp64 on the device: packed codes [.., K / 2], scale bytes [.., K / 32] -> [.., K]"""
-    lut = torch.tensor(_E2M1 + tuple(-v for v in _E2M1), dtype=torch.float64, device=codes.device)
-    c = torch.stack([codes & 15, codes >> 4], -1).reshape(*codes.shape[:-1], -1).long()
-    X = torch.pow(torch.tensor(2.0, dtype=torch.float64, device=codes.device), scales.double() - 127)
-    return (lut[c].reshape(*scales.shape, 32) * X.unsqueeze(-1)).reshape(c.shape)
+_dq = mu.dq_mxfp4              # w' in fp64 on the device: packed codes [.., K / 2], scale bytes [.., K / 32] -> [.., K]
 
 
 def _planted(dev, rows, cols):
@@ -101,11 +94,20 @@ def _experts(dev, E, I, H, seed, I_full=None, col0=0):
     return out
 
 
-@pytest.mark.parametrize("H,I", [(4096, 14336), (4096, 1792)])
+# (H, I) by the form pick_f4 takes.  Down by I: 1792 <1,1>, 3584 <1,2> (the TP = 4 shard: 112 chunks on 128 threads), 7168 <1,4> (TP = 2:
+# 224 on 256), 14336 <2,4>.  Gate|up by H: 2048 <1,1,1> at its upper edge, 4096 <2,1,2>, 8192 <4,1,4>, 14336 <7,2,4>; I = 128 is the
+# smallest with I % rows_it == 0 for every form and I % 64 == 0.
+DECODE_SHAPES = [(4096, 14336), (4096, 1792), (4096, 3584), (4096, 7168), (2048, 128), (8192, 128), (14336, 128)]
+
+
+@pytest.mark.parametrize("H,I", DECODE_SHAPES)
 @pytest.mark.parametrize("with_delta", [False, True])
 def test_moe_decode_mxfp4(dev, H, I, with_delta):
     E = 8
-    ex = _experts(dev, E, I, H, seed=I + with_delta, I_full=14336, col0=14336 - I)
+    # w2 is a column slice of wider rows where that is what the engine has: the released rows' last I columns for the two shapes
+    # this test began with, the upper half of [H, 2 I] rows for the other shard widths (the bf16 rows are drawn on the host)
+    I_full = I if H != 4096 else 14336 if I in (14336, 1792) else 2 * I
+    ex = _experts(dev, E, I, H, seed=I + with_delta, I_full=I_full, col0=I_full - I)
     wg = _bf16(dev, (E, H), 7)
     g = torch.Generator(device="cpu").manual_seed(5)
     x = torch.randn(H, generator=g).to(dev)
@@ -130,6 +132,10 @@ def _check_moe_decode(dev, ex, wg, x, delta, nw, E, I, H, what):
     xn = xs * torch.rsqrt((xs * xs).mean() + 1e-5) * nw.double()
     p = torch.softmax(wg.double() @ xn, 0)
     top = torch.topk(p, 2).indices.tolist()
+    p3 = torch.topk(p, 3).values.tolist()
+    gaps = [(p3[i] - p3[i + 1]) / p3[i] for i in range(2)]
+    print(f"{what}: relative gaps of the reference's router probabilities, first / second and second / third: {gaps[0]:.3g} {gaps[1]:.3g}")
+    assert min(gaps) >= 1e-6, f"{what}: the reference's own top-2 is not separated ({gaps}): `route ==` would say nothing; pick another seed"
     assert route[:2].tolist() == top
     wts = p[top] / p[top].sum()
     ref = torch.zeros(H, dtype=torch.float64, device=dev)
@@ -146,7 +152,7 @@ def _check_moe_decode(dev, ex, wg, x, delta, nw, E, I, H, what):
     return ref
 
 
-@pytest.mark.parametrize("I", [1792, 14336])
+@pytest.mark.parametrize("I", [1792, 3584, 7168, 14336])
 def test_moe_decode_mxfp4_hand_packed(dev, I):
     """The decode GEMVs convert with the f32 form of the instruction, and the quantiser never gives them code 8 (-0) or a scale
     byte far from 127.  Hand-packed experts do: every one of the 16 codes, drawn uniformly, and the scale bytes 2, 127 and 252 in
@@ -229,25 +235,27 @@ def test_gemm_ps_mxfp4_glu_and_down(dev, case):
 def test_conversion_probe_bit_exact(dev):
     """C = I W'^T through the plain MXFP4 GEMM: with one-hot activation planes every output is ONE product 1 * w', so C must equal
     the dequantised weights exactly.  K = 192 is three stages; row n holds code (n + k) % 16 at element k, so over 16 rows every code
-    sits at every nibble position of a stage; the scale bytes 2, 127 and 252 alternate over neighbouring blocks of every row."""
-    K, N, G = 192, 40, 3
-    k = torch.arange(K, device=dev)
-    n = torch.arange(N, device=dev)
-    code = ((n[:, None] + k[None, :]) % 16).to(torch.uint8)
-    codes = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
-    ring = torch.tensor([2, 127, 252, 127, 2, 252, 252, 2], dtype=torch.uint8, device=dev)
-    scales = ring[(torch.arange(K // 32, device=dev)[None, :] + n[:, None]) % 8].contiguous()
+    sits at every nibble position of a stage; the scale bytes 2, 127 and 252 alternate over neighbouring blocks of every row.  N is a
+    full 256-row n-tile plus a tail of 8, under both load forms (ps_nt).  The GLU form of the probe: tests/test_moe_gemm_mxfp4_gpu.py."""
+    K, N, G = 192, 256 + 8, 3
+    codes, scales = mu.mxfp4_probe(dev, N, K, 0, (2, 127, 252, 127, 2, 252, 252, 2))
     assert {int(v) for v in scales[0].tolist()} == {2, 127, 252}
     a_hi = torch.eye(K, device=dev).to(torch.bfloat16)
     a_lo = torch.zeros_like(a_hi)
-    big = torch.full((K + 2 * G, N + 8), 123.0, device=dev)
-    out = big[G:G + K, :N]
-    ops.gemm_ps_mxfp4(a_hi, a_lo, codes, scales, out=out)
-    torch.cuda.synchronize()
     ref = torch.from_numpy(q4_ref.dequant(to_np(codes), to_np(scales))).to(dev)     # fp32 [N, K]
     assert torch.isfinite(ref).all() and float(ref.abs().max()) == 6 * 2.0 ** 125 and float(ref[ref != 0].abs().min()) == 2.0 ** -126
-    assert torch.equal(out, ref.T), (out - ref.T).abs().max()
-    assert (big[:G] == 123.0).all() and (big[G + K:] == 123.0).all() and (big[:, N:] == 123.0).all(), "guard rows / columns"
+    for nt in (-1, 1):
+        big = torch.full((K + 2 * G, N + 8), 123.0, device=dev)
+        out = big[G:G + K, :N]
+        with mu.Knobs(-1, -1, nt):
+            ops.gemm_ps_mxfp4(a_hi, a_lo, codes, scales, out=out)
+            torch.cuda.synchronize()
+        bad = out != ref.T
+        if bool(bad.any()):
+            m, n = (int(v) for v in torch.nonzero(bad)[0])
+            raise AssertionError(f"conversion probe [nt {nt}]: {int(bad.sum())} of {bad.numel()} differ; first at n {n}, k {m} (stage "
+                                 f"{m // 64}, block {m // 32}): got {float(out[m, n]):.9g}, want {float(ref[n, m]):.9g}")
+        assert (big[:G] == 123.0).all() and (big[G + K:] == 123.0).all() and (big[:, N:] == 123.0).all(), f"guard rows / columns [nt {nt}]"
 
 
 def _engine(dev, cfg, packed, **kw):

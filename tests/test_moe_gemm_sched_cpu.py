@@ -115,3 +115,62 @@ def test_i8_small_cases_reach_the_rt_cap_selection():
     assert (200, 3) in caps                                                               # 13 row tiles -> 5 m-tiles of <= 3
     s = mc.schedule((200,), 390, 320, False, ksplit=5, cap=3)
     assert s.KS == 5 and [nk for _, nk in mc.k_slices(320, 5)] == [1] * 5 and max(t.mi for t in s.tiles) == 4
+
+
+# ---- the MXFP4 form (tests/test_moe_gemm_mxfp4_gpu.py): the int8 form's launcher and schedule with the fp4 stagers -------------------
+def _f4_runs():
+    """(projection, Schedule, K) of every launch shape of the MXFP4 module's sections a - d on a 256-CU part.  A knob set changes the
+    load form and the placement, not the tiles, and the dense and the strided (ldw = I) form of a shard's down run the same tiles."""
+    runs = []
+    for case in mc.CASES.values():                                                        # a. released widths
+        runs.append(("gateup", mc.gateup_schedule(case.rows), mc.H))
+        runs += [("down", mc.down_schedule(case.rows, ksplit=ks), mc.I) for ks in (mc.MOE_KSPLIT, 1, 2, 3)]
+    for name in mc.TP_CASES:                                                              # b. TP shards and the overlap halves
+        for it in mc.TP_WIDTHS:
+            runs.append(("gateup", mc.gateup_schedule(mc.CASES[name].rows, N=it), mc.H))
+            runs += [("down", mc.down_schedule(mc.CASES[name].rows, K=it, N=n), it) for n in (mc.H, mc.H // 2)]
+    for cnt in mc.DECODE_CNTS:                                                            # c. batched-decode shapes
+        runs += [("gateup", mc.gateup_schedule(cnt), mc.H), ("down", mc.down_schedule(cnt), mc.I)]
+    for (M, N, K, glu, grouped, ksplit) in mc.small_cases():                              # d. short and odd K
+        rows = mc.SMALL_ROWS[M] if grouped else (M,)
+        cap = 0 if grouped else mc.ps_q_rt_cap(M, N, glu, ksplit)
+        runs.append(("gateup" if glu else "down", mc.schedule(rows, N, K, glu, ksplit=ksplit, cap=cap), K))
+    return runs
+
+
+def _stager_ends(nk):
+    """how each fp4 stager wave g leaves a K slice of nk stages (run_tile_sp: after the shared stage 0, wave g runs k = g, g + 2, ..
+    < nk and stores stage k + 1 when there is one): 'idle' (no iteration), 'store' or 'skip' in its last iteration."""
+    out = []
+    for g in (0, 1):
+        ks = list(range(g, nk, 2))
+        out.append((g, "idle" if not ks else "store" if ks[-1] + 1 < nk else "skip"))
+    return out
+
+
+@pytest.mark.parametrize("proj", ["gateup", "down"])
+def test_f4_runs_reach_every_schedule_path(proj):
+    runs = [(s, K) for p, s, K in _f4_runs() if p == proj]
+    rts = {t.rt for s, _ in runs for t in s.tiles}
+    halves = {t.half for s, _ in runs for t in s.tiles if t.half >= 0}
+    assert rts == set(range(1, mc.RTMAX + 1)), f"{proj}: row-tile counts never run: {sorted(set(range(1, 13)) - rts)}"
+    assert halves == {0, 1}, f"{proj}: M-split tail halves reached: {sorted(halves)}"
+    assert any(s.empty_halves for s, _ in runs), f"{proj}: no run has an M-split tail whose second half is empty"
+    assert any(s.R == 0 for s, _ in runs), f"{proj}: no run has fewer tiles than blocks (R = 0)"
+    assert any(s.r > 0 and not s.split_tail for s, _ in runs), f"{proj}: no run has a partial last round that is not M-split"
+    nks = {mc.k_slices(K, s.KS)[t.ks][1] for s, K in runs for t in s.tiles}
+    assert {1, 2, 3, 4, 5} <= nks, f"{proj}: short slices reached: {sorted(n for n in nks if n <= 5)}"
+    # both stage parities for each stager wave: either wave ends a slice on a store and on a skipped one, wave 1 also idles (nk = 1)
+    ends = {e for n in nks for e in _stager_ends(n)}
+    assert ends == {(0, "store"), (0, "skip"), (1, "store"), (1, "skip"), (1, "idle")}, f"{proj}: stager endings reached: {sorted(ends)}"
+    if proj == "down":                                                                    # tiles the stagers address with k0 != 0
+        assert any(mc.k_slices(K, s.KS)[t.ks][0] > 0 for s, K in runs for t in s.tiles)
+
+
+def test_f4_small_cases_reach_the_rt_cap_selection():
+    """the ungrouped short-K calls take the shared launcher's rt_cap branch: a cap below 12 that changes the m-tiling is reached, and
+    the largest fixed split has one stage per slab (every slab but the first starts at k0 != 0)."""
+    caps = {(M, mc.ps_q_rt_cap(M, N, glu, ks)) for (M, N, K, glu, grouped, ks) in mc.small_cases() if not grouped}
+    assert any(0 < c < mc.RTMAX for _, c in caps) and (200, 3) in caps                    # 13 row tiles -> 5 m-tiles of <= 3
+    s = mc.schedule((200,), 390, 320, False, ksplit=5, cap=3)
+    assert s.KS == 5 and mc.k_slices(320, 5) == [(i, 1) for i in range(5)] and max(t.mi for t in s.tiles) == 4
