@@ -281,7 +281,8 @@ typedef struct {
 typedef struct vh_mixtral vh_mixtral_t;
 
 size_t vh_mixtral_workspace_bytes(const vh_mixtral_cfg* cfg);
-/* `layers` is a host array of cfg->n_layers entries (copied). rope tables: fp32 [max_ctx][head_dim/2]. */
+/* `layers` is a host array of cfg->n_layers entries (copied); a null w1 / w3 / w2 in layers[l] is refused (VH_E_ARG). rope tables:
+ * fp32 [max_ctx][head_dim/2]. */
 vh_mixtral_t* vh_mixtral_create(const vh_mixtral_cfg* cfg, const vh_mixtral_layer* layers, const uint16_t* embed,
                                 const float* final_norm, const uint16_t* lm_head, const float* rope_cos,
                                 const float* rope_sin, void* workspace, size_t workspace_bytes);

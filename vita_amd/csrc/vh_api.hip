@@ -253,37 +253,38 @@ int vh_router_top2(const float* x, long ldx, const uint16_t* Wg, int E, int H, i
     return check_launch("vh_router_top2", vhk_router_top2(S(stream), x, ldx, Wg, E, H, rows, ids, wts, probs));
 }
 
+// a layer's experts are complete: the three weights, and for the quantised formats their scales
+static bool experts_complete(const VhExperts& x) {
+    return x.w1 && x.w3 && x.w2 && (x.fmt == VH_EXPERTS_BF16 || (x.s1 && x.s3 && x.s2));
+}
+static int moe_decode(const char* name, const VhExperts& ex, const float* x, const float* delta, const float* norm_w, float eps,
+                      const uint16_t* Wg, int E, int I, int H, float* x_out, float* y, int* route, float* hbuf, void* stream) {
+    if (!x || !norm_w || !Wg || !experts_complete(ex) || !y || !route || !hbuf) return fail(VH_E_ARG, "%s: null pointer", name);
+    if (H % 64 || I % 64 || H > 14336 || I > 14336) return fail(VH_E_SHAPE, "%s: H, I must be multiples of 64 and <= 14336", name);
+    char what[64];
+    snprintf(what, sizeof(what), "%s (gate|up)", name);
+    int rc = check_launch(what, vhk_dec_gateup(S(stream), x, delta, x_out, norm_w, eps, Wg, E, ex, I, H, route, hbuf, 0));
+    if (rc != VH_OK) return rc;
+    snprintf(what, sizeof(what), "%s (down)", name);
+    return check_launch(what, vhk_dec_down(S(stream), hbuf, route, ex, H, I, y));
+}
 int vh_moe_decode(const float* x, const float* delta, const float* norm_w, float eps, const uint16_t* Wg, const uint16_t* W1,
                   const uint16_t* W3, const uint16_t* W2, int E, int I, int H, float* x_out, float* y, int* route, float* hbuf,
                   void* stream) {
-    if (!x || !norm_w || !Wg || !W1 || !W3 || !W2 || !y || !route || !hbuf) return fail(VH_E_ARG, "vh_moe_decode: null pointer");
-    if (H % 64 || I % 64 || H > 14336 || I > 14336) return fail(VH_E_SHAPE, "vh_moe_decode: H, I must be multiples of 64 and <= 14336");
-    int rc = check_launch("vh_moe_decode (gate|up)", vhk_dec_gateup(S(stream), x, delta, x_out, norm_w, eps, Wg, E, W1, W3, I, H, route, hbuf, 0));
-    if (rc != VH_OK) return rc;
-    return check_launch("vh_moe_decode (down)", vhk_dec_down(S(stream), hbuf, route, W2, H, I, y));
+    const VhExperts ex{VH_EXPERTS_BF16, W1, W3, W2, nullptr, nullptr, nullptr};
+    return moe_decode("vh_moe_decode", ex, x, delta, norm_w, eps, Wg, E, I, H, x_out, y, route, hbuf, stream);
 }
 int vh_moe_decode_i8(const float* x, const float* delta, const float* norm_w, float eps, const uint16_t* Wg, const int8_t* W1,
                      const float* s1, const int8_t* W3, const float* s3, const int8_t* W2, const float* s2, int E, int I, int H,
                      float* x_out, float* y, int* route, float* hbuf, void* stream) {
-    if (!x || !norm_w || !Wg || !W1 || !s1 || !W3 || !s3 || !W2 || !s2 || !y || !route || !hbuf)
-        return fail(VH_E_ARG, "vh_moe_decode_i8: null pointer");
-    if (H % 64 || I % 64 || H > 14336 || I > 14336) return fail(VH_E_SHAPE, "vh_moe_decode_i8: H, I must be multiples of 64 and <= 14336");
-    int rc = check_launch("vh_moe_decode_i8 (gate|up)", vhk_dec_gateup_i8(S(stream), x, delta, x_out, norm_w, eps, Wg, E, W1, s1, W3, s3,
-                                                                          I, H, route, hbuf, 0));
-    if (rc != VH_OK) return rc;
-    return check_launch("vh_moe_decode_i8 (down)", vhk_dec_down_i8(S(stream), hbuf, route, W2, s2, H, I, H, y));
+    const VhExperts ex{VH_EXPERTS_I8, W1, W3, W2, s1, s3, s2};
+    return moe_decode("vh_moe_decode_i8", ex, x, delta, norm_w, eps, Wg, E, I, H, x_out, y, route, hbuf, stream);
 }
-
 int vh_moe_decode_mxfp4(const float* x, const float* delta, const float* norm_w, float eps, const uint16_t* Wg, const uint8_t* W1,
                         const uint8_t* s1, const uint8_t* W3, const uint8_t* s3, const uint8_t* W2, const uint8_t* s2, int E, int I, int H,
                         float* x_out, float* y, int* route, float* hbuf, void* stream) {
-    if (!x || !norm_w || !Wg || !W1 || !s1 || !W3 || !s3 || !W2 || !s2 || !y || !route || !hbuf)
-        return fail(VH_E_ARG, "vh_moe_decode_mxfp4: null pointer");
-    if (H % 64 || I % 64 || H > 14336 || I > 14336) return fail(VH_E_SHAPE, "vh_moe_decode_mxfp4: H, I must be multiples of 64 and <= 14336");
-    int rc = check_launch("vh_moe_decode_mxfp4 (gate|up)", vhk_dec_gateup_mxfp4(S(stream), x, delta, x_out, norm_w, eps, Wg, E, W1, s1, W3,
-                                                                                s3, I, H, route, hbuf, 0));
-    if (rc != VH_OK) return rc;
-    return check_launch("vh_moe_decode_mxfp4 (down)", vhk_dec_down_mxfp4(S(stream), hbuf, route, W2, s2, H, I, H, y));
+    const VhExperts ex{VH_EXPERTS_MXFP4, W1, W3, W2, s1, s3, s2};
+    return moe_decode("vh_moe_decode_mxfp4", ex, x, delta, norm_w, eps, Wg, E, I, H, x_out, y, route, hbuf, stream);
 }
 
 int vh_rope_kv_append(const float* qkv, long ldqkv, float* q_out, float* kcache, float* vcache, const float* rope_cos,
@@ -399,8 +400,7 @@ struct Carver {
 struct vh_mixtral {
     vh_mixtral_cfg c;
     std::vector<vh_mixtral_layer> L;
-    std::vector<vh_mixtral_experts_mxfp4> Q4;   // MXFP4 experts (vh_mixtral_create_mxfp4): one entry per layer; empty = not MXFP4
-    std::vector<vh_mixtral_experts_i8> Q;   // int8 experts (vh_mixtral_create_i8): one entry per layer; empty = bf16
+    std::vector<VhExperts> X;   // the experts of every layer in the engine's format (vh_kernels.h): L[l].w1 / w3 / w2 are read through it only
     const uint16_t* embed; const float* final_norm; const uint16_t* lm_head;
     const float* rope_cos; const float* rope_sin;
     int nq, nkv, hd, H, I, E, V, nqkv, max_splits, lm_grid;
@@ -700,6 +700,51 @@ int rccl_allreduce_cb(void* user, float* buf, long count, void* stream) {
                                     reinterpret_cast<hipStream_t>(stream));
     return rc == 0 ? 0 : -1;
 }
+// The three creates: `record(l)` is layer l's experts as the entry was given them (bf16: the pointers of layers[l]; quantised: its
+// experts[l], and then layers[l] must not name bf16 experts as well); `experts` is the entry's per-layer array, refused when null
+int experts_ok(const char* name, int l, const vh_mixtral_layer& w, const VhExperts& x) {
+    const bool quantised = x.fmt != VH_EXPERTS_BF16;
+    if (quantised && (w.w1 || w.w3 || w.w2))
+        return fail(VH_E_ARG, "%s: layers[%d].w1 / w3 / w2 must be null (the experts are quantised: experts[%d])", name, l, l);
+    if (!experts_complete(x))
+        return fail(VH_E_ARG, "%s: null expert weight or scale pointer in %s[%d]", name, quantised ? "experts" : "layers", l);
+    return VH_OK;
+}
+template <class Record>
+vh_mixtral_t* create_engine(const char* name, const vh_mixtral_cfg* cfg, const vh_mixtral_layer* layers, const void* experts,
+                            Record&& record, const uint16_t* embed, const float* final_norm, const uint16_t* lm_head,
+                            const float* rope_cos, const float* rope_sin, void* workspace, size_t workspace_bytes) {
+    if (cfg_ok(cfg) != VH_OK) return nullptr;
+    if (!layers || !experts || !embed || !final_norm || !lm_head || !rope_cos || !rope_sin || !workspace) {
+        fail(VH_E_ARG, "%s: null pointer (layers / experts / tables / workspace)", name);
+        return nullptr;
+    }
+    std::vector<VhExperts> X(cfg->n_layers);
+    for (int l = 0; l < cfg->n_layers; ++l) {
+        X[l] = record(l);
+        if (experts_ok(name, l, layers[l], X[l]) != VH_OK) return nullptr;
+    }
+    vh_mixtral* m = new vh_mixtral{};
+    m->c = *cfg;
+    m->derive();
+    m->L.assign(layers, layers + cfg->n_layers);
+    m->X = std::move(X);
+    m->embed = embed; m->final_norm = final_norm; m->lm_head = lm_head;
+    m->rope_cos = rope_cos; m->rope_sin = rope_sin;
+    m->ar_fn = nullptr; m->ar_user = nullptr; m->rccl_comm = nullptr;
+    const size_t need = m->carve(workspace);
+    if (need > workspace_bytes) {
+        fail(VH_E_ARG, "%s: workspace too small (%zu < %zu)", name, workspace_bytes, need);
+        delete m;
+        return nullptr;
+    }
+    m->init_seqs();
+    m->init_units();
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, workspace) == hipSuccess) m->device = at.device;
+    else (void)hipGetLastError();      // a host pointer (argument tests without a GPU): the current device is used
+    return m;
+}
 }  // namespace
 
 extern "C" {
@@ -715,85 +760,26 @@ size_t vh_mixtral_workspace_bytes(const vh_mixtral_cfg* cfg) {
 vh_mixtral_t* vh_mixtral_create(const vh_mixtral_cfg* cfg, const vh_mixtral_layer* layers, const uint16_t* embed,
                                 const float* final_norm, const uint16_t* lm_head, const float* rope_cos,
                                 const float* rope_sin, void* workspace, size_t workspace_bytes) {
-    if (cfg_ok(cfg) != VH_OK) return nullptr;
-    if (!layers || !embed || !final_norm || !lm_head || !rope_cos || !rope_sin || !workspace) {
-        fail(VH_E_ARG, "vh_mixtral_create: null pointer");
-        return nullptr;
-    }
-    vh_mixtral* m = new vh_mixtral{};
-    m->c = *cfg;
-    m->derive();
-    m->L.assign(layers, layers + cfg->n_layers);
-    m->embed = embed; m->final_norm = final_norm; m->lm_head = lm_head;
-    m->rope_cos = rope_cos; m->rope_sin = rope_sin;
-    m->ar_fn = nullptr; m->ar_user = nullptr; m->rccl_comm = nullptr;
-    const size_t need = m->carve(workspace);
-    if (need > workspace_bytes) {
-        fail(VH_E_ARG, "vh_mixtral_create: workspace too small (%zu < %zu)", workspace_bytes, need);
-        delete m;
-        return nullptr;
-    }
-    m->init_seqs();
-    m->init_units();
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, workspace) == hipSuccess) m->device = at.device;
-    else (void)hipGetLastError();      // a host pointer (argument tests without a GPU): the current device is used
-    return m;
+    auto record = [&](int l) { return VhExperts{VH_EXPERTS_BF16, layers[l].w1, layers[l].w3, layers[l].w2, nullptr, nullptr, nullptr}; };
+    return create_engine("vh_mixtral_create", cfg, layers, layers, record, embed, final_norm, lm_head, rope_cos, rope_sin, workspace,
+                         workspace_bytes);
 }
 
 vh_mixtral_t* vh_mixtral_create_i8(const vh_mixtral_cfg* cfg, const vh_mixtral_layer* layers, const vh_mixtral_experts_i8* experts,
                                    const uint16_t* embed, const float* final_norm, const uint16_t* lm_head, const float* rope_cos,
                                    const float* rope_sin, void* workspace, size_t workspace_bytes) {
-    if (cfg_ok(cfg) != VH_OK) return nullptr;
-    if (!layers || !experts) {
-        fail(VH_E_ARG, "vh_mixtral_create_i8: null layers / experts");
-        return nullptr;
-    }
-    for (int l = 0; l < cfg->n_layers; ++l) {
-        const vh_mixtral_layer& w = layers[l];
-        const vh_mixtral_experts_i8& q = experts[l];
-        if (w.w1 || w.w3 || w.w2) {
-            fail(VH_E_ARG, "vh_mixtral_create_i8: layers[%d].w1 / w3 / w2 must be null (the experts are int8)", l);
-            return nullptr;
-        }
-        if (!q.w1 || !q.s1 || !q.w3 || !q.s3 || !q.w2 || !q.s2) {
-            fail(VH_E_ARG, "vh_mixtral_create_i8: null int8 weight or scale in experts[%d]", l);
-            return nullptr;
-        }
-    }
-    vh_mixtral_t* m = vh_mixtral_create(cfg, layers, embed, final_norm, lm_head, rope_cos, rope_sin, workspace, workspace_bytes);
-    if (m) m->Q.assign(experts, experts + cfg->n_layers);
-    return m;
+    auto record = [&](int l) { const auto& q = experts[l]; return VhExperts{VH_EXPERTS_I8, q.w1, q.w3, q.w2, q.s1, q.s3, q.s2}; };
+    return create_engine("vh_mixtral_create_i8", cfg, layers, experts, record, embed, final_norm, lm_head, rope_cos, rope_sin, workspace,
+                         workspace_bytes);
 }
 
 vh_mixtral_t* vh_mixtral_create_mxfp4(const vh_mixtral_cfg* cfg, const vh_mixtral_layer* layers,
                                       const vh_mixtral_experts_mxfp4* experts, const uint16_t* embed, const float* final_norm,
                                       const uint16_t* lm_head, const float* rope_cos, const float* rope_sin, void* workspace,
                                       size_t workspace_bytes) {
-    if (cfg_ok(cfg) != VH_OK) return nullptr;
-    if (!layers || !experts) {
-        fail(VH_E_ARG, "vh_mixtral_create_mxfp4: null layers / experts");
-        return nullptr;
-    }
-    if (cfg->hidden % 64 || cfg->inter % 64) {
-        fail(VH_E_ARG, "vh_mixtral_create_mxfp4: hidden (%d) and inter (%d) must be multiples of 64", cfg->hidden, cfg->inter);
-        return nullptr;
-    }
-    for (int l = 0; l < cfg->n_layers; ++l) {
-        const vh_mixtral_layer& w = layers[l];
-        const vh_mixtral_experts_mxfp4& q = experts[l];
-        if (w.w1 || w.w3 || w.w2) {
-            fail(VH_E_ARG, "vh_mixtral_create_mxfp4: layers[%d].w1 / w3 / w2 must be null (the experts are MXFP4)", l);
-            return nullptr;
-        }
-        if (!q.w1 || !q.s1 || !q.w3 || !q.s3 || !q.w2 || !q.s2) {
-            fail(VH_E_ARG, "vh_mixtral_create_mxfp4: null MXFP4 code or scale pointer in experts[%d]", l);
-            return nullptr;
-        }
-    }
-    vh_mixtral_t* m = vh_mixtral_create(cfg, layers, embed, final_norm, lm_head, rope_cos, rope_sin, workspace, workspace_bytes);
-    if (m) m->Q4.assign(experts, experts + cfg->n_layers);
-    return m;
+    auto record = [&](int l) { const auto& q = experts[l]; return VhExperts{VH_EXPERTS_MXFP4, q.w1, q.w3, q.w2, q.s1, q.s3, q.s2}; };
+    return create_engine("vh_mixtral_create_mxfp4", cfg, layers, experts, record, embed, final_norm, lm_head, rope_cos, rope_sin, workspace,
+                         workspace_bytes);
 }
 
 void vh_mixtral_destroy(vh_mixtral_t* m) {
@@ -1065,9 +1051,8 @@ static int reduce_rows(vh_mixtral* m, hipStream_t st, int Sn, bool overlap, Prod
 // left: the rows are sorted by expert, gate|up runs one tall m-tile per expert (weights cross the fabric once) and emits the
 // planes of h (ph_hi / lo), the down projection is K-split into `nslab` partial slabs of py that the combine adds.
 struct MoeGemms {
-    VhGemmPsArgs gate_up, down;   // launched by the caller (down: all H columns) through moe_gate_up / moe_down
-    const vh_mixtral_experts_i8* q; // int8 experts of the layer (null: bf16): the same arguments with W / W_up null
-    const vh_mixtral_experts_mxfp4* q4;   // MXFP4 experts of the layer (null: not MXFP4), likewise
+    VhGemmPsArgs gate_up, down;   // launched by the caller (down: all H columns) through moe_gate_up / moe_down; W / W_up stay null:
+    const VhExperts* x;           // the weights are the layer's experts, handed to the format's GEMM by moe_gate_up / moe_down_gemm
     int nslab;                    // slabs the combine adds (1 when the kernel picks the split ...
     const int* nslab_dev;         // ... and reports it here; null otherwise)
 };
@@ -1075,11 +1060,10 @@ static int moe_gemms(vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, i
     const int H = m->H, I = m->I, E = m->E;
     VH_TRY(vhk_moe_sort(st, m->pids, n, E, m->pgoff, m->pstok, m->psslot), "sort");
     *p = MoeGemms{};
-    p->q = m->Q.empty() ? nullptr : &m->Q[&w - m->L.data()];
-    p->q4 = m->Q4.empty() ? nullptr : &m->Q4[&w - m->L.data()];
+    p->x = &m->X[&w - m->L.data()];
     VhGemmPsArgs &g = p->gate_up, &d = p->down;
     g.A_hi = m->pxn_hi; g.A_lo = m->pxn_lo; g.lda = H; g.a_rowidx = m->pstok;
-    g.W = w.w1; g.W_up = w.w3; g.ldw = H; g.w_group_stride = (long)I * H;
+    g.ldw = H; g.w_group_stride = (long)I * H;
     g.group_off = m->pgoff; g.ngroups = E;
     g.C_hi = m->ph_hi; g.C_lo = m->ph_lo; g.ldc_split = I; g.M = 2 * n; g.N = I; g.K = H; g.ksplit = 1;
     int ks = vh_tuning()->moe_ksplit;   // 1 .. 4 slabs, or -n: chosen by the kernel from the expert sizes (up to n)
@@ -1088,7 +1072,7 @@ static int moe_gemms(vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, i
     if (ks < -4) ks = -4;
     if (ks > (I >> 6)) ks = 1;
     d.A_hi = m->ph_hi; d.A_lo = m->ph_lo; d.lda = I;
-    d.W = w.w2; d.ldw = I; d.w_group_stride = (long)H * I;
+    d.ldw = I; d.w_group_stride = (long)H * I;
     d.group_off = m->pgoff; d.ngroups = E;
     d.C = m->py; d.ldc = H; d.c_rowidx = m->psslot; d.M = 2 * n; d.N = H; d.K = I;
     d.ksplit = ks; d.c_split_stride = m->down_slab(H); d.nslab_out = m->pnslab;
@@ -1096,28 +1080,45 @@ static int moe_gemms(vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, i
     p->nslab_dev = ks < 0 ? m->pnslab : nullptr;
     return VH_OK;
 }
-// int8 experts: the specialised streaming GEMM with the int8 stagers (vhk_gemm_ps_i8), the same arguments with W / W_up null
+// The format's streaming GEMM on the layer's experts.  bf16: the weights go into the arguments; int8 / MXFP4: the specialised GEMM
+// with that format's stagers (vhk_gemm_ps_i8 / _mxfp4), W / W_up null.  int8 scale groups are I (gate|up) and H (down) floats apart
 static int moe_gate_up(hipStream_t st, const MoeGemms& p) {
-    if (!p.q && !p.q4) return vhk_gemm_ps(st, p.gate_up);
+    const VhExperts& x = *p.x;
     VhGemmPsArgs g = p.gate_up;
-    g.W = nullptr; g.W_up = nullptr;
-    if (p.q4) return vhk_gemm_ps_mxfp4(st, g, VhPsF4{p.q4->w1, p.q4->w3, p.q4->s1, p.q4->s3});
-    return vhk_gemm_ps_i8(st, g, VhPsI8{p.q->w1, p.q->w3, p.q->s1, p.q->s3, (long)g.N});
+    switch (x.fmt) {
+        case VH_EXPERTS_BF16: g.W = vh_as<uint16_t>(x.w1); g.W_up = vh_as<uint16_t>(x.w3); return vhk_gemm_ps(st, g);
+        case VH_EXPERTS_I8: return vhk_gemm_ps_i8(st, g, VhPsI8{vh_as<int8_t>(x.w1), vh_as<int8_t>(x.w3), vh_as<float>(x.s1), vh_as<float>(x.s3), (long)g.N});
+        case VH_EXPERTS_MXFP4: return vhk_gemm_ps_mxfp4(st, g, VhPsF4{vh_as<uint8_t>(x.w1), vh_as<uint8_t>(x.w3), vh_as<uint8_t>(x.s1), vh_as<uint8_t>(x.s3)});
+    }
+    return -1;
+}
+// the experts with w2 / s2 starting at row c0 of every expert's [H][I] down matrix (output column c0: a tensor-parallel half).  bf16 and
+// int8 code rows are I elements, MXFP4 code rows I / 2 bytes; int8 has one scale per row, MXFP4 I / 32 scale bytes
+static VhExperts w2_from_row(VhExperts x, int c0, long I) {
+    switch (x.fmt) {
+        case VH_EXPERTS_BF16: x.w2 = vh_as<uint16_t>(x.w2) + (size_t)c0 * I; break;
+        case VH_EXPERTS_I8: x.w2 = vh_as<int8_t>(x.w2) + (size_t)c0 * I; x.s2 = vh_as<float>(x.s2) + c0; break;
+        case VH_EXPERTS_MXFP4: x.w2 = vh_as<uint8_t>(x.w2) + (size_t)c0 * (I >> 1); x.s2 = vh_as<uint8_t>(x.s2) + (size_t)c0 * (I >> 5); break;
+    }
+    return x;
 }
 // down projection of output columns [c0, c0 + d.N) (d: p.down with N / C narrowed by the caller)
 static int moe_down_gemm(hipStream_t st, const MoeGemms& p, const VhGemmPsArgs& d, int c0, int H) {
-    if (!p.q && !p.q4) return vhk_gemm_ps(st, d);
+    const VhExperts x = w2_from_row(*p.x, c0, d.ldw);
     VhGemmPsArgs a = d;
-    a.W = nullptr;
-    if (p.q4) return vhk_gemm_ps_mxfp4(st, a, VhPsF4{p.q4->w2 + (size_t)c0 * (a.ldw >> 1), nullptr, p.q4->s2 + (size_t)c0 * (a.ldw >> 5), nullptr});
-    return vhk_gemm_ps_i8(st, a, VhPsI8{p.q->w2 + (size_t)c0 * a.ldw, nullptr, p.q->s2 + c0, nullptr, (long)H});
+    switch (x.fmt) {
+        case VH_EXPERTS_BF16: a.W = vh_as<uint16_t>(x.w2); return vhk_gemm_ps(st, a);
+        case VH_EXPERTS_I8: return vhk_gemm_ps_i8(st, a, VhPsI8{vh_as<int8_t>(x.w2), nullptr, vh_as<float>(x.s2), nullptr, (long)H});
+        case VH_EXPERTS_MXFP4: return vhk_gemm_ps_mxfp4(st, a, VhPsF4{vh_as<uint8_t>(x.w2), nullptr, vh_as<uint8_t>(x.s2), nullptr});
+    }
+    return -1;
 }
 // the down projection of output columns [h * ncols, (h + 1) * ncols) into the slabs from py_half(h), then their
 // routing-weighted sum into part ([n][ncols], zeroed first)
-static int moe_down(vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, const MoeGemms& p, int n, int h, int ncols,
+static int moe_down(vh_mixtral* m, hipStream_t st, const MoeGemms& p, int n, int h, int ncols,
                     float* part) {
     VhGemmPsArgs d = p.down;
-    d.W = w.w2 ? w.w2 + (size_t)h * ncols * m->I : nullptr; d.N = ncols; d.C = m->py_half(h); d.ldc = ncols; d.c_split_stride = m->down_slab(ncols);
+    d.N = ncols; d.C = m->py_half(h); d.ldc = ncols; d.c_split_stride = m->down_slab(ncols);
     VH_TRY(moe_down_gemm(st, p, d, h * ncols, m->H), "down gemm");
     if (hipMemsetAsync(part, 0, (size_t)n * ncols * sizeof(float), st) != hipSuccess) return fail(VH_E_HIP, "memset failed");
     VH_TRY(vhk_moe_combine(st, part, d.C, m->pwts, n, ncols, p.nslab, d.c_split_stride, p.nslab_dev), "combine");
@@ -1424,7 +1425,7 @@ static int prefill_enqueue(vh_mixtral* m, const float* embeds, const PfSeg* sg, 
         if (prof) { (void)hipEventRecord(m->prof_ev[m->prof_used + 1], st); m->prof_used += 2; }
         if (tp) {
             rc = reduce_rows(m, st, Sn, overlap,
-                             [&](int h, float* part, int ncols) { return moe_down(m, st, w, moe, Sn, h, ncols, part); });
+                             [&](int h, float* part, int ncols) { return moe_down(m, st, moe, Sn, h, ncols, part); });
             if (rc != VH_OK) return rc;
         } else {
             VH_TRY(moe_down_gemm(st, moe, moe.down, 0, H), "down gemm");
@@ -1594,34 +1595,6 @@ static bool fused_wanted(const vh_mixtral* m) {
     return vhk_dec_ablk_supported(m->H, m->nq, m->nkv) != 0;
 }
 
-// gate|up and down GEMVs of one sequence's MoE in layer w, on its bf16, int8 or MXFP4 experts; cx / px: the fused exchange
-// the launch consumes / produces (nullable)
-struct DecExperts {
-    const vh_mixtral_experts_i8* q8;       // int8 experts of the layer, or null
-    const vh_mixtral_experts_mxfp4* q4;    // MXFP4 experts of the layer, or null (both null: bf16)
-    int consumer() const { return q4 ? 5 : q8 ? 4 : 1; }   // vhk_dec_consumer_blocks' id of the gate|up launch
-};
-static DecExperts dec_experts(const vh_mixtral* m, int l) {
-    return DecExperts{m->Q.empty() ? nullptr : &m->Q[l], m->Q4.empty() ? nullptr : &m->Q4[l]};
-}
-static int dec_gateup(const vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, const DecExperts& x, const float* x_in,
-                      const float* delta, float* x_out, int* route, float* hbuf, const VhXchg* cx) {
-    const vh_mixtral_experts_i8* q8 = x.q8;
-    if (x.q4)
-        return vhk_dec_gateup_mxfp4(st, x_in, delta, x_out, w.ffn_norm, m->c.rms_eps, w.wrouter, m->E, x.q4->w1, x.q4->s1, x.q4->w3,
-                                    x.q4->s3, m->I, m->H, route, hbuf, 0, cx);
-    return q8 ? vhk_dec_gateup_i8(st, x_in, delta, x_out, w.ffn_norm, m->c.rms_eps, w.wrouter, m->E, q8->w1, q8->s1, q8->w3, q8->s3, m->I,
-                                  m->H, route, hbuf, 0, cx)
-              : vhk_dec_gateup(st, x_in, delta, x_out, w.ffn_norm, m->c.rms_eps, w.wrouter, m->E, w.w1, w.w3, m->I, m->H, route, hbuf, 0, cx);
-}
-static int dec_down(const vh_mixtral* m, hipStream_t st, const vh_mixtral_layer& w, const DecExperts& x, const float* hbuf,
-                    const int* route, float* out, const VhXchg* px) {
-    const vh_mixtral_experts_i8* q8 = x.q8;
-    if (x.q4) return vhk_dec_down_mxfp4(st, hbuf, route, x.q4->w2, x.q4->s2, m->H, m->I, m->H, out, px);
-    return q8 ? vhk_dec_down_i8(st, hbuf, route, q8->w2, q8->s2, m->H, m->I, m->H, out, px)
-              : vhk_dec_down(st, hbuf, route, w.w2, m->H, m->I, out, px);
-}
-
 // One decode step of unit u (all layers + LM head + token select) enqueued on st.  Returns VH_OK or an error code; the host
 // mirrors move in step_unit, only after the step was enqueued without error.
 // Three launches per layer: the attention block (k_dec_ablk: fused QKV -> attention -> O projection; three launches with
@@ -1652,11 +1625,11 @@ static int decode_one_step(vh_mixtral* m, vh_mixtral::Unit& u, hipStream_t st) {
     bool have_xm = false;
     for (int l = 0; l < m->c.n_layers; ++l) {
         const vh_mixtral_layer& w = m->L[l];
-        const DecExperts ex = dec_experts(m, l);
+        const VhExperts& ex = m->X[l];
         float* kc = m->kcache + (size_t)l * nkv * m->c.max_ctx * hd;
         float* vc = m->vcache + (size_t)l * nkv * m->c.max_ctx * hd;
         const bool prof = m->prof_stride > 0 && (l % m->prof_stride) == 0 && m->prof_used + 2 <= m->prof_ev.size();
-        if (fuse && vh_comm_xchg_next(m->comm, H, 0, vhk_dec_consumer_blocks(ex.consumer(), 0, H, I), &xa, st) != VH_OK)
+        if (fuse && vh_comm_xchg_next(m->comm, H, 0, vhk_dec_gateup_blocks(ex.fmt, I, H), &xa, st) != VH_OK)
             return fail(VH_E_COMM, "fused exchange failed: %s", vh_comm_last_error());
         if (fused_attn) {
             VhDecAblk a{};
@@ -1680,16 +1653,16 @@ static int decode_one_step(vh_mixtral* m, vh_mixtral::Unit& u, hipStream_t st) {
         }
         if (!fuse && m->allreduce(u.da, H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
         // the consumer of the MoE exchange is the next layer's attention block (or fused-QKV GEMV), or the LM head after the last layer
-        const int xm_blocks = l + 1 < m->c.n_layers ? (fused_attn ? vhk_dec_ablk_qkv_blocks(m->nqkv, H) : vhk_dec_consumer_blocks(0, m->nqkv, H, I))
+        const int xm_blocks = l + 1 < m->c.n_layers ? (fused_attn ? vhk_dec_ablk_qkv_blocks(m->nqkv, H) : vhk_dec_qkv_blocks(m->nqkv))
                                                      : m->lm_grid;
         if (prof) (void)hipEventRecord(m->prof_ev[m->prof_used], st);
-        VH_TRY(dec_gateup(m, st, w, ex, u.xb, u.da, u.xa, m->route, m->hbuf, fuse ? &xa : nullptr), "dec gateup");
+        VH_TRY(vhk_dec_gateup(st, u.xb, u.da, u.xa, w.ffn_norm, eps, w.wrouter, m->E, ex, I, H, m->route, m->hbuf, 0, fuse ? &xa : nullptr), "dec gateup");
         if (prof) { (void)hipEventRecord(m->prof_ev[m->prof_used + 1], st); m->prof_used += 2; }
         if (fuse) {
             if (vh_comm_xchg_next(m->comm, H, 1, xm_blocks, &xm, st) != VH_OK) return fail(VH_E_COMM, "fused exchange failed: %s", vh_comm_last_error());
             have_xm = true;
         }
-        VH_TRY(dec_down(m, st, w, ex, m->hbuf, m->route, u.dm, fuse ? &xm : nullptr), "dec down");
+        VH_TRY(vhk_dec_down(st, m->hbuf, m->route, ex, H, I, u.dm, fuse ? &xm : nullptr), "dec down");
         if (!fuse && m->allreduce(u.dm, H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
     }
     const int rc = head_one(m, st, u, u.xa, u.dm, /*mode=*/1, /*set_pos=*/0, have_xm ? &xm : nullptr);
@@ -1942,7 +1915,7 @@ static int decode_iteration(vh_mixtral* m, hipStream_t st, const int* ids, int n
     }
     for (int l = 0; l < m->c.n_layers; ++l) {
         const vh_mixtral_layer& w = m->L[l];
-        const DecExperts ex = dec_experts(m, l);
+        const VhExperts& ex = m->X[l];
         float* kc = m->kcache + (size_t)l * nkv * m->c.max_ctx * hd;
         float* vc = m->vcache + (size_t)l * nkv * m->c.max_ctx * hd;
         for (int g0 = 0; g0 < n; g0 += VH_BMAX) {
@@ -1976,14 +1949,14 @@ static int decode_iteration(vh_mixtral* m, hipStream_t st, const int* ids, int n
             int rc = moe_gemms(m, st, w, n, &moe);
             if (rc != VH_OK) return rc;
             VH_TRY(moe_gate_up(st, moe), "gate/up gemm");
-            if ((rc = moe_down(m, st, w, moe, n, 0, H, m->ptmp)) != VH_OK) return rc;
+            if ((rc = moe_down(m, st, moe, n, 0, H, m->ptmp)) != VH_OK) return rc;
             if (tp && m->allreduce(m->ptmp, (long)n * H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");
         } else {
             for (int b = 0; b < n; ++b) {
                 const vh_mixtral::Unit& u = *us[b];
                 const int lane = b % VH_BMAX;   // the scratch lane the sequence had in its attention group
-                VH_TRY(dec_gateup(m, st, w, ex, u.xb, u.da, u.xa, m->l_route[lane], m->l_hbuf[lane], nullptr), "dec gateup");
-                VH_TRY(dec_down(m, st, w, ex, m->l_hbuf[lane], m->l_route[lane], dm[b], nullptr), "dec down");
+                VH_TRY(vhk_dec_gateup(st, u.xb, u.da, u.xa, w.ffn_norm, eps, w.wrouter, E, ex, I, H, m->l_route[lane], m->l_hbuf[lane], 0), "dec gateup");
+                VH_TRY(vhk_dec_down(st, m->l_hbuf[lane], m->l_route[lane], ex, H, I, dm[b]), "dec down");
             }
             for (int b = 0; b < n; ++b)
                 if (m->allreduce(dm[b], H, st) != 0) return fail(VH_E_COMM, "all-reduce failed");

@@ -1574,42 +1574,40 @@ constexpr int DEC_GEMV_R = 8;
 // measured SLOWER at every degree: one rank's TP = 8 / 4 / 2 shard 1.316 / 1.831 / 2.871 against 1.287 / 1.788 / 2.790 ms per token; removed)
 // int8 experts: 8 + 8 rows per gate|up group and 4 rows per expert in the down blocks (the bf16 kernels' bytes in flight)
 constexpr int DEC_I8_RP = 8, DEC_I8_R = 4;
-// MXFP4 experts: gate (= up) rows per iteration of k_dec_gateup_mxfp4 (G groups of RP rows): K <= 2048 one wave per row and
-// 4 x 4 rows, K <= 4096 two waves and 2 x 8, K <= 8192 four waves and 8, above that 4 (two chunk slots per thread)
-static int dec_f4_rows_it(int K) { return K <= 4096 ? 16 : K <= 8192 ? 8 : 4; }
-static int dec_gateup_grid(int I, int rp = 4) {   // rp: gate (= up) rows per group of the kernel (4 bf16, 8 int8)
+// gate (= up) rows per group of the format's gate|up kernel.  MXFP4: rows per iteration of k_dec_gateup_mxfp4 (G groups of RP rows):
+// K <= 2048 one wave per row and 4 x 4 rows, K <= 4096 two waves and 2 x 8, K <= 8192 four waves and 8, above that 4 (two chunk slots
+// per thread)
+static int dec_gateup_rows(VhExpertFmt fmt, int K) {
+    switch (fmt) {
+        case VH_EXPERTS_BF16: return 4;
+        case VH_EXPERTS_I8: return DEC_I8_RP;
+        case VH_EXPERTS_MXFP4: return K <= 4096 ? 16 : K <= 8192 ? 8 : 4;
+    }
+    return 0;
+}
+int vhk_dec_gateup_blocks(VhExpertFmt fmt, int I, int K) {
     // 1.5 persistent blocks per CU: every block pays the router prologue (96 KB of L2 reads), so fewer, longer-lived
     // blocks win — r01: 79 us at 512 blocks vs 83 at 1024 and 82 at 1280; r02 (cheaper block reductions): whole-token rate
     // 196.6 / 205.7 / 210.5 / 207.6 / 207.0 / 208.7 / 207.4 tok/s at 256 / 320 / 384 / 448 / 512 / 768 / 1024 blocks
-    const int n_iter = 2 * (I / rp);
+    const int n_iter = 2 * (I / dec_gateup_rows(fmt, K));
     const int cus = vh_num_cus();
     int grid = 3 * cus / 2;
-    if (vh_tuning()->dec_gateup_grid > 0) grid = vh_tuning()->dec_gateup_grid;
-    else if (n_iter <= 4 * grid) {
+    if (vh_tuning()->dec_gateup_grid > 0) {
+        grid = vh_tuning()->dec_gateup_grid;
+    } else if (fmt == VH_EXPERTS_MXFP4 && n_iter > 6 * cus) {
+        // MXFP4: 3 persistent blocks per CU when there are more than 6 row groups per CU (measured at TP = 1, 1792 groups: a decode
+        // step 3.79 / 3.54 / 3.28 / 3.45 ms at 384 / 512 / 768 / 1024 blocks: the conversion makes a group's FMA phase longer than the
+        // bf16 and int8 kernels', and more resident blocks cover it with loads); a tensor-parallel shard's few groups as for the others
+        grid = 3 * cus;
+    } else if (n_iter <= 4 * grid) {
         // (r06) the few row groups of a tensor-parallel shard: EQUAL shares in as few rounds as 2 blocks per CU allow
         const int rounds = (n_iter + 2 * cus - 1) / (2 * cus);
         grid = (n_iter + rounds - 1) / rounds;
     }
     return grid > n_iter ? n_iter : grid;
 }
-// MXFP4 gate|up: 3 persistent blocks per CU when there are more than 6 row groups per CU (measured at TP = 1, 1792 groups: a decode
-// step 3.79 / 3.54 / 3.28 / 3.45 ms at 384 / 512 / 768 / 1024 blocks: the conversion makes a group's FMA phase longer than the bf16 and
-// int8 kernels', and more resident blocks cover it with loads); a tensor-parallel shard's few groups as for the other formats
-static int dec_gateup_grid_f4(int I, int K) {
-    const int rows_it = dec_f4_rows_it(K);
-    const int n_iter = 2 * (I / rows_it), cus = vh_num_cus();
-    if (vh_tuning()->dec_gateup_grid <= 0 && n_iter > 6 * cus) return 3 * cus;
-    return dec_gateup_grid(I, rows_it);
-}
-// blocks of a consumer launch: the fused exchange's reducers are its first min(16, blocks) blocks
-int vhk_dec_consumer_blocks(int which, int N, int K, int I) {
-    if (which == 0) return (N + DEC_GEMV_R - 1) / DEC_GEMV_R;
-    if (which == 1) return dec_gateup_grid(I);
-    if (which == 4) return dec_gateup_grid(I, DEC_I8_RP);   // gate|up on int8 experts
-    if (which == 5) return dec_gateup_grid_f4(I, K);   // gate|up on MXFP4 experts
-    if (which == 3) return N;   // fused attention block: at least the fused-QKV blocks (N = their count) come first
-    return N;   // LM head: the caller's grid
-}
+// blocks of the fused-QKV GEMV launch over N rows (a fused exchange's reducers are the first min(16, blocks) blocks of its consumer)
+int vhk_dec_qkv_blocks(int N) { return (N + DEC_GEMV_R - 1) / DEC_GEMV_R; }
 
 int vhk_dec_qkv(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
                 const uint16_t* W, int N, int K, float* out, const VhXchg* cx) {
@@ -1666,62 +1664,54 @@ int vhk_dec_oproj(hipStream_t st, const float* attn_out, const uint16_t* W, int 
     return launch_dec_gemv<DEC_GEMV_R, false>(st, attn_out, nullptr, nullptr, nullptr, 0.f, W, N, K, out, px);
 }
 
-int vhk_dec_gateup(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
-                   const uint16_t* Wg, int E, const uint16_t* W1, const uint16_t* W3, int I, int K, int* route_out,
-                   float* hbuf, int grid, const VhXchg* cxp) {
-    if (E > 8 || E < 2 || I % 4 != 0) return -1;
-    const int n_iter = 2 * (I / 4);
-    const VhXchg cx = xchg_or_none(cxp);
-    if (grid <= 0) grid = dec_gateup_grid(I);
-    if (grid > n_iter) grid = n_iter;
-    return pick_nj(K, [&](auto nj) {
-        constexpr int NJ = decltype(nj)::value;
-        hipLaunchKernelGGL((k_dec_gateup<NJ, 4>), dim3(grid), dim3(256), 0, st, x_in, delta, x_out, norm_w, eps, Wg, E, W1, W3, I, K,
-                           route_out, hbuf, cx);
+// gate|up and down per format (file-local: the template selection and the argument rules differ).  x: the layer's experts in that
+// format.  Every format's gate|up kernel takes the same arguments around its weight pointers: vhk_dec_gateup fills them in once
+struct DecGateupCall {
+    hipStream_t st; int grid;
+    const float* x_in; const float* delta; float* x_out; const float* norm_w; float eps; const uint16_t* Wg; int E, I, K;
+    int* route_out; float* hbuf; VhXchg cx;
+    template <class Kernel, class... W>
+    int launch(Kernel kernel, W... weights) const {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, st, x_in, delta, x_out, norm_w, eps, Wg, E, weights..., I, K, route_out, hbuf, cx);
         return 0;
-    });
+    }
+};
+static int dec_gateup_bf16(const DecGateupCall& c, const VhExperts& x) {
+    return pick_nj(c.K, [&](auto nj) { return c.launch(k_dec_gateup<decltype(nj)::value, 4>, vh_as<uint16_t>(x.w1), vh_as<uint16_t>(x.w3)); });
 }
-
-int vhk_dec_down(hipStream_t st, const float* hbuf, const int* route, const uint16_t* W2, int N, int I, float* out,
-                 const VhXchg* pxp) {
+static int dec_down_bf16(hipStream_t st, const float* hbuf, const int* route, const VhExperts& x, int N, int I, float* out,
+                         const VhXchg& px) {
     // one block per row pair (a persistent form that keeps both intermediate vectors in registers measured slower: 204.6-208.8
     // against 211.5 tok/s, r02, git history)
     constexpr int R = 2;
-    const VhXchg px = xchg_or_none(pxp);
     return pick_nj(I, [&](auto nj) {
         hipLaunchKernelGGL((k_dec_down<decltype(nj)::value, R>), dim3((N + R - 1) / R), dim3(256), 0, st, hbuf, route,
-                           W2, N, I, out, px);
+                           vh_as<uint16_t>(x.w2), N, I, out, px);
         return 0;
     });
 }
 
-int vhk_dec_gateup_i8(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
-                      const uint16_t* Wg, int E, const int8_t* W1, const float* s1, const int8_t* W3, const float* s3, int I, int K,
-                      int* route_out, float* hbuf, int grid, const VhXchg* cxp) {
-    if (E > 8 || E < 2 || I % DEC_I8_RP != 0 || K % 8 != 0) return -1;
-    const int n_iter = 2 * (I / DEC_I8_RP);
-    const VhXchg cx = xchg_or_none(cxp);
-    if (grid <= 0) grid = dec_gateup_grid(I, DEC_I8_RP);
-    if (grid > n_iter) grid = n_iter;
-    return pick_nj(K, [&](auto nj) {
-        constexpr int NJ = decltype(nj)::value;
-        hipLaunchKernelGGL((k_dec_gateup_i8<NJ, DEC_I8_RP>), dim3(grid), dim3(256), 0, st, x_in, delta, x_out, norm_w, eps, Wg, E,
-                           W1, s1, W3, s3, I, K, route_out, hbuf, cx);
-        return 0;
+// int8 experts (per-output-row scales s[e][row]): the same launches on int8 weights, (sum_k x_k q_k) * s in fp32
+static int dec_gateup_i8(const DecGateupCall& c, const VhExperts& x) {
+    if (c.K % 8 != 0) return -1;
+    return pick_nj(c.K, [&](auto nj) {
+        return c.launch(k_dec_gateup_i8<decltype(nj)::value, DEC_I8_RP>, vh_as<int8_t>(x.w1), vh_as<float>(x.s1), vh_as<int8_t>(x.w3),
+                        vh_as<float>(x.s3));
     });
 }
-int vhk_dec_down_i8(hipStream_t st, const float* hbuf, const int* route, const int8_t* W2, const float* s2, int N, int I,
-                    long row_stride, float* out, const VhXchg* pxp) {
-    if (I % 8 != 0 || N < 1 || row_stride < N) return -1;
-    const VhXchg px = xchg_or_none(pxp);
+// the kernels' row_stride (rows per expert) is N: w2 / s2 are the first of the N rows of every expert
+static int dec_down_i8(hipStream_t st, const float* hbuf, const int* route, const VhExperts& x, int N, int I, float* out,
+                       const VhXchg& px) {
+    if (I % 8 != 0 || N < 1) return -1;
     return pick_nj(I, [&](auto nj) {
         hipLaunchKernelGGL((k_dec_down_i8<decltype(nj)::value, DEC_I8_R>), dim3((N + DEC_I8_R - 1) / DEC_I8_R), dim3(256), 0, st,
-                           hbuf, route, W2, s2, N, I, row_stride, out, px);
+                           hbuf, route, vh_as<int8_t>(x.w2), vh_as<float>(x.s2), N, I, (long)N, out, px);
         return 0;
     });
 }
 
-// MXFP4 experts: (NJ8 of the router prologue, chunk slots NJ, waves per row WPR) by K
+// MXFP4 experts (w' is formed where the weights are converted, so there is no epilogue scale): (NJ8 of the router
+// prologue, chunk slots NJ, waves per row WPR) by K
 template <typename F>
 static int pick_f4(int K, F&& f) {
     using I1 = std::integral_constant<int, 1>; using I2 = std::integral_constant<int, 2>;
@@ -1732,31 +1722,49 @@ static int pick_f4(int K, F&& f) {
     if (K <= 14336) return f(I7{}, I2{}, I4{});
     return -1;
 }
-int vhk_dec_gateup_mxfp4(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
-                         const uint16_t* Wg, int E, const uint8_t* W1, const uint8_t* S1, const uint8_t* W3, const uint8_t* S3, int I,
-                         int K, int* route_out, float* hbuf, int grid, const VhXchg* cxp) {
-    const int rows_it = dec_f4_rows_it(K);
-    if (E > 8 || E < 2 || I % rows_it != 0 || K % 32 != 0) return -1;
-    const int n_iter = 2 * (I / rows_it);
-    const VhXchg cx = xchg_or_none(cxp);
-    if (grid <= 0) grid = dec_gateup_grid_f4(I, K);
-    if (grid > n_iter) grid = n_iter;
-    return pick_f4(K, [&](auto nj8, auto nj, auto wpr) {
-        hipLaunchKernelGGL((k_dec_gateup_mxfp4<decltype(nj8)::value, decltype(nj)::value, decltype(wpr)::value>), dim3(grid), dim3(256),
-                           0, st, x_in, delta, x_out, norm_w, eps, Wg, E, W1, S1, W3, S3, I, K, route_out, hbuf, cx);
-        return 0;
+static int dec_gateup_mxfp4(const DecGateupCall& c, const VhExperts& x) {
+    if (c.K % 32 != 0) return -1;
+    return pick_f4(c.K, [&](auto nj8, auto nj, auto wpr) {
+        return c.launch(k_dec_gateup_mxfp4<decltype(nj8)::value, decltype(nj)::value, decltype(wpr)::value>, vh_as<uint8_t>(x.w1),
+                        vh_as<uint8_t>(x.s1), vh_as<uint8_t>(x.w3), vh_as<uint8_t>(x.s3));
     });
 }
-int vhk_dec_down_mxfp4(hipStream_t st, const float* hbuf, const int* route, const uint8_t* W2, const uint8_t* S2, int N, int I,
-                       long row_stride, float* out, const VhXchg* pxp) {
-    if (I % 32 != 0 || N < 1 || row_stride < N) return -1;
-    const VhXchg px = xchg_or_none(pxp);
+static int dec_down_mxfp4(hipStream_t st, const float* hbuf, const int* route, const VhExperts& x, int N, int I, float* out,
+                          const VhXchg& px) {
+    if (I % 32 != 0 || N < 1) return -1;
     return pick_f4(I, [&](auto, auto nj, auto wpr) {
         constexpr int RB = decltype(nj)::value == 2 ? 4 : 8;     // output rows per block (k_dec_down_mxfp4)
         hipLaunchKernelGGL((k_dec_down_mxfp4<decltype(nj)::value, decltype(wpr)::value>), dim3((N + RB - 1) / RB), dim3(256), 0, st, hbuf,
-                           route, W2, S2, N, I, row_stride, out, px);
+                           route, vh_as<uint8_t>(x.w2), vh_as<uint8_t>(x.s2), N, I, (long)N, out, px);
         return 0;
     });
+}
+
+int vhk_dec_gateup(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
+                   const uint16_t* Wg, int E, const VhExperts& x, int I, int K, int* route_out, float* hbuf, int grid,
+                   const VhXchg* cxp) {
+    const int rows = dec_gateup_rows(x.fmt, K);
+    if (E > 8 || E < 2 || rows == 0 || I % rows != 0) return -1;
+    const int n_iter = 2 * (I / rows);
+    if (grid <= 0) grid = vhk_dec_gateup_blocks(x.fmt, I, K);
+    if (grid > n_iter) grid = n_iter;
+    const DecGateupCall c{st, grid, x_in, delta, x_out, norm_w, eps, Wg, E, I, K, route_out, hbuf, xchg_or_none(cxp)};
+    switch (x.fmt) {
+        case VH_EXPERTS_BF16: return dec_gateup_bf16(c, x);
+        case VH_EXPERTS_I8: return dec_gateup_i8(c, x);
+        case VH_EXPERTS_MXFP4: return dec_gateup_mxfp4(c, x);
+    }
+    return -1;
+}
+int vhk_dec_down(hipStream_t st, const float* hbuf, const int* route, const VhExperts& x, int N, int I, float* out,
+                 const VhXchg* pxp) {
+    const VhXchg px = xchg_or_none(pxp);
+    switch (x.fmt) {
+        case VH_EXPERTS_BF16: return dec_down_bf16(st, hbuf, route, x, N, I, out, px);
+        case VH_EXPERTS_I8: return dec_down_i8(st, hbuf, route, x, N, I, out, px);
+        case VH_EXPERTS_MXFP4: return dec_down_mxfp4(st, hbuf, route, x, N, I, out, px);
+    }
+    return -1;
 }
 
 int vhk_dec_lmhead(hipStream_t st, const float* x_in, const float* delta, const float* norm_w, float eps,

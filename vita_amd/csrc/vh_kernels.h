@@ -97,11 +97,23 @@ int vh_comm_xchg_next(vh_comm* c, long count, int which, int consumer_blocks, Vh
 int vh_comm_ranks_per_device(const vh_comm* c);   // declared at creation: ranks that drive this rank's device (1 on a node with a GPU per rank)
 int vh_comm_is_loopback(const vh_comm* c);        // a single-rank communicator that plays `world` ranks into its own slots (bench: protocol cost without links)
 
+// ---- one layer's routed experts ---------------------------------------------------------
+// The one place that says which format a layer's expert weights are in: the engine fills a record per layer at create; the decode
+// launchers below and the prefill dispatch (vh_api.hip moe_gate_up / moe_down_gemm) switch on it.  bf16: w [rows][K], no scales; int8:
+// w [rows][K], s fp32 per row; MXFP4: w e2m1 codes [rows][K / 2] bytes, s E8M0 bytes [rows][K / 32]
+enum VhExpertFmt { VH_EXPERTS_BF16, VH_EXPERTS_I8, VH_EXPERTS_MXFP4 };
+struct VhExperts {
+    VhExpertFmt fmt;
+    const void *w1, *w3, *w2;   // gate / up [E][I][H], down [E][H][I]
+    const void *s1, *s3, *s2;   // their scales; null for bf16
+};
+template <class T> inline const T* vh_as(const void* p) { return static_cast<const T*>(p); }   // a record's pointer in its format's type
+
 // ---- decode (vh_decode.hip) ---------------------------------------------------------
 // cx (nullable): the delta is the result of a fused exchange (then `delta` is ignored); px (nullable): push the outputs
 int vhk_dec_qkv(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
                 const uint16_t* W, int N, int K, float* out, const VhXchg* cx = nullptr);
-int vhk_dec_consumer_blocks(int which, int N, int K, int I);   // grid of a consumer launch (0 qkv, 1 gate|up, 2 lm head, 3 fused attention block, 4 int8 gate|up, 5 MXFP4 gate|up: K = hidden): bounds nred
+int vhk_dec_qkv_blocks(int N);   // its grid (bounds the reducers of a fused exchange it consumes)
 int vhk_dec_attn(hipStream_t st, const float* qkv, float* kcache, float* vcache, const int* pos_ptr,
                  const float* rope_cos, const float* rope_sin, float* part_o, float* part_ml, int* cnt,
                  float* attn_out, int nq, int nkv, int max_ctx, int max_splits, int ctx_host, float scale,
@@ -173,25 +185,15 @@ int vhk_decb_attn(hipStream_t st, const VhDecBatchAttn& bt, int n, float* kcache
                   const float* rope_sin, int nq, int nkv, int max_ctx, int max_splits, float scale);
 int vhk_decb_lmhead(hipStream_t st, const VhDecBatchVec& bt, const float* norm_w, float eps, const uint16_t* W, int V, int K,
                     const VhDecBatchHead& hd, int grid, int v0);
+// gate|up and down GEMVs of one token's MoE on the layer's experts x (x.w2 / x.s2: the N rows per expert of this call); -1: an
+// argument the format's kernel does not take.  grid 0: vhk_dec_gateup_blocks
 int vhk_dec_gateup(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
-                   const uint16_t* Wg, int E, const uint16_t* W1, const uint16_t* W3, int I, int K, int* route_out,
-                   float* hbuf, int grid, const VhXchg* cx = nullptr);
-int vhk_dec_down(hipStream_t st, const float* hbuf, const int* route, const uint16_t* W2, int N, int I, float* out,
+                   const uint16_t* Wg, int E, const VhExperts& x, int I, int K, int* route_out, float* hbuf, int grid,
+                   const VhXchg* cx = nullptr);
+int vhk_dec_down(hipStream_t st, const float* hbuf, const int* route, const VhExperts& x, int N, int I, float* out,
                  const VhXchg* px = nullptr);
-// int8 experts (per-output-row scales s[e][row]): the same launches on int8 weights, (sum_k x_k q_k) * s in fp32
-int vhk_dec_gateup_i8(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
-                      const uint16_t* Wg, int E, const int8_t* W1, const float* s1, const int8_t* W3, const float* s3, int I, int K,
-                      int* route_out, float* hbuf, int grid, const VhXchg* cx = nullptr);
-// W2 / s2: the first of the N rows this call computes (a column slice of the experts' [Ntot][I]); row_stride = rows per expert (Ntot)
-int vhk_dec_down_i8(hipStream_t st, const float* hbuf, const int* route, const int8_t* W2, const float* s2, int N, int I,
-                    long row_stride, float* out, const VhXchg* px = nullptr);
-// MXFP4 experts: e2m1 codes W [rows][K / 2] (element k in byte k >> 1, low nibble for even k) and E8M0 scale bytes
-// S [rows][K / 32]; w' = e2m1(code) * 2^(byte - 127) is formed where the weights are converted, so there is no epilogue scale
-int vhk_dec_gateup_mxfp4(hipStream_t st, const float* x_in, const float* delta, float* x_out, const float* norm_w, float eps,
-                         const uint16_t* Wg, int E, const uint8_t* W1, const uint8_t* S1, const uint8_t* W3, const uint8_t* S3, int I,
-                         int K, int* route_out, float* hbuf, int grid, const VhXchg* cx = nullptr);
-int vhk_dec_down_mxfp4(hipStream_t st, const float* hbuf, const int* route, const uint8_t* W2, const uint8_t* S2, int N, int I,
-                       long row_stride, float* out, const VhXchg* px = nullptr);
+// (format, I, K = hidden) -> rows per gate|up group -> blocks of the gate|up launch; also bounds the reducers of a fused exchange
+int vhk_dec_gateup_blocks(VhExpertFmt fmt, int I, int K);
 int vhk_dec_lmhead(hipStream_t st, const float* x_in, const float* delta, const float* norm_w, float eps,
                    const uint16_t* W, int V, int K, float* logits, float* blk_val, int* blk_idx, int grid,
                    const int* ngen_ptr, int hist_rows, int v0, int Vfull, const VhXchg* cx = nullptr,
