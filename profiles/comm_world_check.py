@@ -8,11 +8,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
 def main():
-    import torch.multiprocessing as mp
-    from tests.test_comm_gpu import _free_port, _worker
+    from tests.ranks import run_ranks
+    from tests.test_comm_gpu import _worker
     for world in (4, 8):
-        ret = mp.Manager().dict()
-        mp.spawn(_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
+        ret = run_ranks(_worker, world, deadline_s=120)
         r0 = ret[0]
         bad = [(key, r, ret[r][key][0]) for key in r0 for r in range(world)
                if ret[r][key][0] != 0.0 or ret[r][key][1] != r0[key][1]]

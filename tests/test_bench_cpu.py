@@ -55,42 +55,23 @@ class _FakeEngine:
         self.cancelled = True
 
 
-def _bringup_worker(rank, world, port, fail_rank, ret):
+def _bringup_worker(ctx, fail_rank):
     import torch
     import torch.distributed as dist
     import bench
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        eng = _FakeEngine(fail=(rank == fail_rank))
-        ok = bench.native_rccl_or_fallback(eng, rank, dist, torch.device("cpu"), "gloo", timeout_s=20)
-        ret[rank] = (bool(ok), eng.called, getattr(eng, "cancelled", False))
-    finally:
-        dist.destroy_process_group()
-
-
-def _free_port():
-    import socket
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _run_bringup(fail_rank):
-    import torch.multiprocessing as mp
-    ret = mp.Manager().dict()
-    mp.spawn(_bringup_worker, args=(2, _free_port(), fail_rank, ret), nprocs=2, join=True)
-    return dict(ret)
+    eng = _FakeEngine(fail=(ctx.rank == fail_rank))
+    ok = bench.native_rccl_or_fallback(eng, ctx.rank, dist, torch.device("cpu"), "gloo", timeout_s=20)
+    return (bool(ok), eng.called, getattr(eng, "cancelled", False))
 
 
 def test_rccl_bringup_consensus_world2():
     """One rank failing its native init (or rank 0 being unable to mint an id on a GPU-less host) must send BOTH
     ranks to the torch fallback; nobody may be left believing the native communicator is active alone."""
-    r = _run_bringup(fail_rank=1)
+    from tests.ranks import run_ranks
+    r = run_ranks(_bringup_worker, 2, 1, deadline_s=120, gpu=False)            # fail_rank = 1
     assert r[0][0] is False and r[1][0] is False, r
     assert r[0][2] and r[1][2], r              # ... and every rank cancelled its attempt (a late init must not install)
-    r2 = _run_bringup(fail_rank=-1)
+    r2 = run_ranks(_bringup_worker, 2, -1, deadline_s=120, gpu=False)          # nobody fails
     assert r2[0][0] == r2[1][0], r2            # agree either way (True only where librccl could mint an id)
 
 

@@ -2,87 +2,68 @@
 multi-GPU box is available to this repo's tests): one-shot and two-shot paths against the plain sum, bit-identical
 results on both ranks, several epochs back to back (double-buffer reuse), and the engine's tensor-parallel decode
 through it against the unsharded run."""
-import os
-import time
-import socket
-
 import numpy as np
 import pytest
 import torch
 
+from tests.ranks import greedy_tp_run, require_ipc, run_ranks
+
 pytestmark = pytest.mark.gpu
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _worker(rank, world, port, ret):
+def _worker(ctx):
     import torch.distributed as dist
     from vita_amd.parallel import IpcComm
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda:0")
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        comm = IpcComm(rank, world, 1 << 21, same_device=True)
-        handles = [None] * world
-        dist.all_gather_object(handles, comm.handle)
-        comm.connect(handles)
-        out = {}
-        for it, n in enumerate([4096, 1, 1000, 32768, 40000, 1 << 20, 4096, 4096, 300 * 4096 + 7]):
-            g = torch.Generator(device="cpu").manual_seed(100 * it + rank)
-            x = torch.randn(n, generator=g)
-            parts = [torch.randn(n, generator=torch.Generator(device="cpu").manual_seed(100 * it + r)) for r in range(world)]
-            ref = parts[0].clone()
-            for p in parts[1:]:
-                ref += p                                # rank order, fp32: the kernel's order
-            y = comm.allreduce(x.to(dev))
-            torch.cuda.synchronize()
-            assert comm.status() == 0
-            out[(it, n)] = (float((y.cpu() - ref).abs().max()), y.cpu().numpy().tobytes())
-        # bulk path on a buffer that is NOT 16-byte aligned (a view one element into an allocation): scalar copies
-        base = torch.zeros(50002, device=dev)
-        parts = [torch.randn(50001, generator=torch.Generator(device="cpu").manual_seed(777 + r)) for r in range(world)]
+    rank, world, dev = ctx.rank, ctx.world, ctx.dev
+    comm = IpcComm(rank, world, 1 << 21, same_device=True)
+    ctx.defer(comm.destroy)
+    handles = [None] * world
+    dist.all_gather_object(handles, comm.handle)
+    comm.connect(handles)
+    out = {}
+    for it, n in enumerate([4096, 1, 1000, 32768, 40000, 1 << 20, 4096, 4096, 300 * 4096 + 7]):
+        g = torch.Generator(device="cpu").manual_seed(100 * it + rank)
+        x = torch.randn(n, generator=g)
+        parts = [torch.randn(n, generator=torch.Generator(device="cpu").manual_seed(100 * it + r)) for r in range(world)]
+        ref = parts[0].clone()
+        for p in parts[1:]:
+            ref += p                                # rank order, fp32: the kernel's order
+        y = comm.allreduce(x.to(dev))
+        torch.cuda.synchronize()
+        assert comm.status() == 0
+        out[(it, n)] = (float((y.cpu() - ref).abs().max()), y.cpu().numpy().tobytes())
+    # bulk path on a buffer that is NOT 16-byte aligned (a view one element into an allocation): scalar copies
+    base = torch.zeros(50002, device=dev)
+    parts = [torch.randn(50001, generator=torch.Generator(device="cpu").manual_seed(777 + r)) for r in range(world)]
+    ref = parts[0].clone()
+    for p in parts[1:]:
+        ref += p
+    view = base[1:]
+    view.copy_(parts[rank].to(dev))
+    assert view.data_ptr() % 16 != 0
+    y = comm.allreduce(view)
+    torch.cuda.synchronize()
+    assert comm.status() == 0
+    out[("misaligned", 50001)] = (float((y.cpu() - ref).abs().max()), y.cpu().numpy().tobytes())
+    # the 32-bit granule tag wraps after 2^32 calls: jump every rank to just below it and cross it with mixed sizes
+    # (ADVICE r02: parity tracked separately from the tag, barrier + re-zero + barrier at the wrap)
+    assert comm.lib.vh_comm_debug_set_calls(comm.ptr, (1 << 32) - 3) == 0
+    dist.barrier()
+    for it, n in enumerate([4096, 70000, 4096, 4096, 1000, 4096]):
+        parts = [torch.randn(n, generator=torch.Generator(device="cpu").manual_seed(9000 + 100 * it + r)) for r in range(world)]
         ref = parts[0].clone()
         for p in parts[1:]:
             ref += p
-        view = base[1:]
-        view.copy_(parts[rank].to(dev))
-        assert view.data_ptr() % 16 != 0
-        y = comm.allreduce(view)
+        y = comm.allreduce(parts[rank].to(dev))
         torch.cuda.synchronize()
         assert comm.status() == 0
-        out[("misaligned", 50001)] = (float((y.cpu() - ref).abs().max()), y.cpu().numpy().tobytes())
-        # the 32-bit granule tag wraps after 2^32 calls: jump every rank to just below it and cross it with mixed sizes
-        # (ADVICE r02: parity tracked separately from the tag, barrier + re-zero + barrier at the wrap)
-        assert comm.lib.vh_comm_debug_set_calls(comm.ptr, (1 << 32) - 3) == 0
-        dist.barrier()
-        for it, n in enumerate([4096, 70000, 4096, 4096, 1000, 4096]):
-            parts = [torch.randn(n, generator=torch.Generator(device="cpu").manual_seed(9000 + 100 * it + r)) for r in range(world)]
-            ref = parts[0].clone()
-            for p in parts[1:]:
-                ref += p
-            y = comm.allreduce(parts[rank].to(dev))
-            torch.cuda.synchronize()
-            assert comm.status() == 0
-            out[("wrap", it, n)] = (float((y.cpu() - ref).abs().max()), y.cpu().numpy().tobytes())
-        out[("fine_grained",)] = (0.0, bytes([int(comm.fine_grained)]))
-        ret[rank] = out
-        dist.barrier()
-        time.sleep(0.5)                          # gloo: a rank that leaves the barrier first must not close its sockets under the others
-        comm.destroy()
-    finally:
-        dist.destroy_process_group()
+        out[("wrap", it, n)] = (float((y.cpu() - ref).abs().max()), y.cpu().numpy().tobytes())
+    out[("fine_grained",)] = (0.0, bytes([int(comm.fine_grained)]))
+    return out
 
 
 def test_ipc_allreduce_two_processes_one_gpu():
-    import torch.multiprocessing as mp
-    ret = mp.Manager().dict()
-    mp.spawn(_worker, args=(2, _free_port(), ret), nprocs=2, join=True)
-    r0, r1 = ret[0], ret[1]
+    r0, r1 = run_ranks(_worker, 2, deadline_s=120)
     for key in r0:
         assert r0[key][0] == 0.0 and r1[key][0] == 0.0, (key, r0[key][0], r1[key][0])   # exact: same order of fp32 adds
         assert r0[key][1] == r1[key][1], key                                             # bit-identical across ranks
@@ -101,72 +82,48 @@ def _tp_cfg(world):
     return cfg
 
 
-def _tp_worker(rank, world, port, overlap, ret, fuse=1, collective="ipc"):
+def _tp_oracle(world):
+    """-> cfg, the unsharded fp32 oracle's 10 greedy ids and their logits for _tp_worker's prompt"""
+    from oracle import mixtral as om
+    from vita_amd.checkpoint import synth_state_dict
+    cfg = _tp_cfg(world)
+    sd = synth_state_dict(cfg, seed=3, parts=("text",))
+    ids = np.random.default_rng(5).integers(3, cfg.text.vocab_size, size=37).tolist()
+    return (cfg,) + om.MixtralOracle(sd, cfg.text).greedy(sd["model.embed_tokens.weight"][ids], 10)
+
+
+def _tp_env(fuse):
+    """fuse 1 / 0: force the exchange fused into the decode kernels / one all-reduce kernel per exchange; -1: the ranks choose the
+    exchange form themselves (shared device -> "kernel"); -2: ... after the TIMED trial a real node runs (both forms, 6 steps
+    each), forced here on one device."""
+    if fuse >= 0:
+        return {"VITA_AMD_TP_FUSE": str(int(fuse)), "VITA_AMD_TP_TRIAL": None}
+    return {"VITA_AMD_TP_FUSE": None, "VITA_AMD_TP_TRIAL": "1" if fuse == -2 else None}
+
+
+def _tp_worker(ctx, overlap, collective="ipc"):
     import torch.distributed as dist
     from vita_amd import _lib
     from vita_amd.checkpoint import pack_mixtral, synth_state_dict
-    from vita_amd.config import VitaConfig
     from vita_amd.engine import MixtralEngine
     from vita_amd.parallel import setup_tensor_parallel
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.pop("VITA_AMD_TP_TRIAL", None)
-    if fuse < 0:
-        os.environ.pop("VITA_AMD_TP_FUSE", None)      # the ranks choose the exchange form themselves (shared device -> "kernel")
-        if fuse == -2:
-            os.environ["VITA_AMD_TP_TRIAL"] = "1"     # ... after the TIMED trial a real node runs (both forms, 6 steps each), forced here on one device
-    else:
-        os.environ["VITA_AMD_TP_FUSE"] = str(int(fuse))   # force: 1 = the exchange fused into the decode kernels
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda:0")
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        cfg = _tp_cfg(world)
-        sd = synth_state_dict(cfg, seed=3, parts=("text",))
-        packed = pack_mixtral(sd, cfg, dev, rank=rank, world=world)
-        eng = MixtralEngine(cfg, packed, dev, max_ctx=128, max_prefill=64, max_new=16, rank=rank, world=world, logit_rows=16)
-        t = cfg.text
-        assert eng.c.n_q_heads == t.num_attention_heads // world and eng.c.n_kv_heads == t.num_key_value_heads // world
-        assert eng.c.inter == t.intermediate_size // world
-        _lib.tune("tp_overlap", overlap)
-        name = setup_tensor_parallel(eng, rank, world, dev, backend="gloo", collective=collective)
-        rng = np.random.default_rng(5)
-        ids = rng.integers(3, cfg.text.vocab_size, size=37).tolist()
-        emb = packed["embed"][torch.as_tensor(ids, device=dev)].float()
-        row0, _ = eng.prefill(emb, gather_logits=True)   # sharded head: the full row (collective inside)
-        row0 = row0.cpu()
-        eng.decode(9)
-        torch.cuda.synchronize()
-        lg = eng.logits_all[:10].cpu()
-        dist.all_reduce(lg)                      # vocab-sharded head: rows hold this rank's slice, zeros elsewhere
-        assert eng.vocab_sharded and torch.equal(row0, lg[0]), "prefill() must return the full-vocabulary row under TP"
-        ret[rank] = (name, eng.generated(), lg.numpy(), (eng.c.vocab_lo, eng.c.vocab_n), comm_status(eng), eng.decode_exchange,
-                     eng.decode_schedule())
-        dist.barrier()
-        time.sleep(0.5)                          # gloo: a rank that leaves the barrier first must not close its sockets under the others
-        eng.close()
-    except BaseException:
-        import traceback
-        ret[("error", rank)] = traceback.format_exc()      # mp.spawn reports ONE failing process: keep every rank's own reason
-        raise
-    finally:
-        dist.destroy_process_group()
-
-
-def _require_ipc(names, what):
-    """The sharded-engine tests are ABOUT the library's IPC transport: a run whose ranks agreed on another collective FAILS
-    (VERDICT r04 #1d; it used to xfail, i.e. a box where the IPC bring-up loses kept the suite green).  VITA_ALLOW_GLOO_FALLBACK=1
-    turns the failure back into an xfail for a box that is known not to support same-device IPC mapping."""
-    if names == {"ipc"}:
-        return
-    msg = f"{what}: the ranks agreed on {names} instead of the IPC all-reduce: the IPC transport was NOT exercised"
-    if os.environ.get("VITA_ALLOW_GLOO_FALLBACK", "") == "1":
-        pytest.xfail(msg)
-    pytest.fail(msg)
-
-
-def comm_status(eng):
-    c = getattr(eng, "_comm", None)
-    return c.status() if c is not None else None
+    rank, world, dev = ctx.rank, ctx.world, ctx.dev
+    cfg = _tp_cfg(world)
+    sd = synth_state_dict(cfg, seed=3, parts=("text",))
+    packed = pack_mixtral(sd, cfg, dev, rank=rank, world=world)
+    eng = MixtralEngine(cfg, packed, dev, max_ctx=128, max_prefill=64, max_new=16, rank=rank, world=world, logit_rows=16)
+    ctx.defer(eng.close)
+    t = cfg.text
+    assert eng.c.n_q_heads == t.num_attention_heads // world and eng.c.n_kv_heads == t.num_key_value_heads // world
+    assert eng.c.inter == t.intermediate_size // world
+    _lib.tune("tp_overlap", overlap)
+    name = setup_tensor_parallel(eng, rank, world, dev, backend="gloo", collective=collective)
+    rng = np.random.default_rng(5)
+    ids = rng.integers(3, cfg.text.vocab_size, size=37).tolist()
+    emb = packed["embed"][torch.as_tensor(ids, device=dev)].float()
+    run = greedy_tp_run(eng, emb, 10, dist, name, gather_logits=True)      # sharded head: prefill returns the full row (collective inside)
+    assert eng.vocab_sharded and np.array_equal(run.row0, run.logits[0]), "prefill() must return the full-vocabulary row under TP"
+    return run
 
 
 # world 8 needs 8 engine processes next to this one on a GPU that may hold at most 6: its shard shapes and exchanges run as one
@@ -177,36 +134,23 @@ def test_tp_engine_world_4_and_8_match_oracle(dev, world):
     (q heads 16 / world, KV heads 8 / world: one KV head per rank at 8, every expert's intermediate columns 1024 / world,
     vocabulary rows 1000 / world): greedy ids == the unsharded fp32 oracle, logits within 1e-3, all ranks bit-identical,
     no spin time-out."""
-    import torch.multiprocessing as mp
-    from oracle import mixtral as om
-    from vita_amd.checkpoint import synth_state_dict
-    ret = mp.Manager().dict()
-    try:
-        mp.spawn(_tp_worker, args=(world, _free_port(), 1, ret, -1), nprocs=world, join=True)   # fuse = -1: the ranks choose the exchange form
-    except Exception:
-        for k in sorted(k for k in ret.keys() if isinstance(k, tuple)):
-            print(f"---- rank {k[1]} ----\n{ret[k]}")
-        raise
-    cfg = _tp_cfg(world)
-    sd = synth_state_dict(cfg, seed=3, parts=("text",))
-    rng = np.random.default_rng(5)
-    ids = rng.integers(3, cfg.text.vocab_size, size=37).tolist()
-    ref_ids, ref_lg = om.MixtralOracle(sd, cfg.text).greedy(sd["model.embed_tokens.weight"][ids], 10)
+    ret = run_ranks(_tp_worker, world, 1, env=_tp_env(-1), deadline_s=120)   # fuse = -1: the ranks choose the exchange form
+    cfg, ref_ids, ref_lg = _tp_oracle(world)
     # every rank agreed on ONE collective, and it must be the library's IPC transport: a run that fell back to
     # torch.distributed (gloo) proves nothing about vh_comm under the sharded engine (VERDICT r03 "What's weak" #3)
-    names = {ret[r][0] for r in range(world)}
-    assert len(names) == 1, {r: ret[r][0] for r in range(world)}
-    _require_ipc(names, f"world {world}")
-    assert all(ret[r][4] in (0, None) for r in range(world)), {r: ret[r][4] for r in range(world)}
+    names = {ret[r].collective for r in range(world)}
+    assert len(names) == 1, {r: ret[r].collective for r in range(world)}
+    require_ipc(names, f"world {world}")
+    assert all(ret[r].comm_status in (0, None) for r in range(world)), {r: ret[r].comm_status for r in range(world)}
     print("collective at world", world, ":", names)
-    shards = [ret[r][3] for r in range(world)]
+    shards = [ret[r].vocab_shard for r in range(world)]
     assert shards[0][0] == 0 and sum(n for _, n in shards) == cfg.text.vocab_size
     assert all(shards[r][0] == shards[r - 1][0] + shards[r - 1][1] for r in range(1, world))      # the shards tile the table
     for r in range(world):
-        assert ret[r][1] == ref_ids, f"rank {r} tokens differ from the unsharded oracle: {ret[r][1]} vs {ref_ids}"
-        assert np.array_equal(ret[r][2], ret[0][2]), f"rank {r} logits differ from rank 0's"
-        assert ret[r][6] == "three-launches", ret[r][6]      # ranks that SHARE a device never run launches whose blocks wait for other blocks
-    assert float(np.abs(ret[0][2] - ref_lg).max()) < 1e-3
+        assert ret[r].tokens == ref_ids, f"rank {r} tokens differ from the unsharded oracle: {ret[r].tokens} vs {ref_ids}"
+        assert np.array_equal(ret[r].logits, ret[0].logits), f"rank {r} logits differ from rank 0's"
+        assert ret[r].schedule == "three-launches", ret[r].schedule      # ranks that SHARE a device never run launches whose blocks wait for other blocks
+    assert float(np.abs(ret[0].logits - ref_lg).max()) < 1e-3
 
 
 @pytest.mark.parametrize("overlap,fuse", [(1, 1), (0, 1), (1, 0), (1, -1), (1, -2)])
@@ -217,33 +161,24 @@ def test_tp2_engine_over_ipc_allreduce_matches_oracle(dev, overlap, fuse):
     the other (the default); 0: one all-reduce per sub-block on the compute stream.  fuse = 1: the DECODE exchanges are fused
     into the producer / consumer kernels (VhXchg: pushes from the O / down projections, reduction by the first blocks of the
     next kernel — the form a GPU per rank runs); 0: one all-reduce kernel per exchange (r02, the same-device default)."""
-    import torch.multiprocessing as mp
-    from oracle import mixtral as om
-    from vita_amd.checkpoint import synth_state_dict
-    from vita_amd.config import VitaConfig
-    ret = mp.Manager().dict()
-    mp.spawn(_tp_worker, args=(2, _free_port(), overlap, ret, fuse), nprocs=2, join=True)
-    cfg = VitaConfig.tiny()
-    sd = synth_state_dict(cfg, seed=3, parts=("text",))
-    rng = np.random.default_rng(5)
-    ids = rng.integers(3, cfg.text.vocab_size, size=37).tolist()
-    ref_ids, ref_lg = om.MixtralOracle(sd, cfg.text).greedy(sd["model.embed_tokens.weight"][ids], 10)
-    assert ret[0][0] == ret[1][0] == "ipc"
+    r0, r1 = run_ranks(_tp_worker, 2, overlap, env=_tp_env(fuse), deadline_s=120)
+    cfg, ref_ids, ref_lg = _tp_oracle(2)
+    assert r0.collective == r1.collective == "ipc"
     # forced forms report themselves; left to the vote (fuse = -1) two ranks on ONE device must get the kernel form
     if fuse == -2:      # the timed trial decides (whichever form was faster here); what matters: both ranks agree and the engine is clean after it
-        assert ret[0][5] == ret[1][5] and ret[0][5] in ("fused", "kernel"), (ret[0][5], ret[1][5])
+        assert r0.exchange == r1.exchange and r0.exchange in ("fused", "kernel"), (r0.exchange, r1.exchange)
     else:
-        assert ret[0][5] == ret[1][5] == {1: "fused", 0: "kernel", -1: "kernel"}[fuse]
+        assert r0.exchange == r1.exchange == {1: "fused", 0: "kernel", -1: "kernel"}[fuse]
     # A tensor-parallel rank that OWNS its GPU runs the attention block as ONE launch (k_dec_ablk); ranks that SHARE a device — every
     # multi-process test here — keep its three launches: a launch whose blocks wait for other blocks can be starved by another process's
     # waiting blocks (dispatch is in index order per XCD only: r06 saw it as an intermittent time-out with eight ranks on one GPU).
     # The one-launch form with BOTH exchange forms is covered in one process by test_loopback_* below, at the released shard shapes.
-    assert ret[0][6] == ret[1][6] == "three-launches", (ret[0][5], ret[0][6], ret[1][6])
+    assert r0.schedule == r1.schedule == "three-launches", (r0.exchange, r0.schedule, r1.schedule)
     V = cfg.text.vocab_size
-    assert ret[0][3] == (0, (V + 1) // 2) and ret[1][3] == ((V + 1) // 2, V - (V + 1) // 2)    # the head IS sharded
-    assert ret[0][1] == ret[1][1] == ref_ids
-    assert np.array_equal(ret[0][2], ret[1][2])
-    assert np.abs(ret[0][2] - ref_lg).max() < 1e-3
+    assert r0.vocab_shard == (0, (V + 1) // 2) and r1.vocab_shard == ((V + 1) // 2, V - (V + 1) // 2)    # the head IS sharded
+    assert r0.tokens == r1.tokens == ref_ids
+    assert np.array_equal(r0.logits, r1.logits)
+    assert np.abs(r0.logits - ref_lg).max() < 1e-3
 
 
 def test_tp2_engine_over_torch_allreduce_fallback(dev):
@@ -251,28 +186,20 @@ def test_tp2_engine_over_torch_allreduce_fallback(dev):
     loop through vh_mixtral_set_allreduce — what a job gets when both the IPC transport and native RCCL lose their bring-up):
     two engine processes over gloo, ids == the unsharded fp32 oracle, both ranks bit-identical (no test referenced
     use_torch_allreduce after the r04 prune, yet every failed bring-up lands there)."""
-    import torch.multiprocessing as mp
-    from oracle import mixtral as om
-    from vita_amd.checkpoint import synth_state_dict
-    from vita_amd.config import VitaConfig
-    ret = mp.Manager().dict()
-    mp.spawn(_tp_worker, args=(2, _free_port(), 0, ret, 0, "torch"), nprocs=2, join=True)
-    cfg = VitaConfig.tiny()
-    sd = synth_state_dict(cfg, seed=3, parts=("text",))
-    ids = np.random.default_rng(5).integers(3, cfg.text.vocab_size, size=37).tolist()
-    ref_ids, ref_lg = om.MixtralOracle(sd, cfg.text).greedy(sd["model.embed_tokens.weight"][ids], 10)
-    assert ret[0][0] == ret[1][0] == "torch"
-    assert ret[0][4] is None and ret[1][4] is None            # no IPC communicator was attached
-    assert ret[0][1] == ret[1][1] == ref_ids
-    assert np.array_equal(ret[0][2], ret[1][2])
-    assert np.abs(ret[0][2] - ref_lg).max() < 1e-3
+    r0, r1 = run_ranks(_tp_worker, 2, 0, "torch", env=_tp_env(0), deadline_s=120)
+    _, ref_ids, ref_lg = _tp_oracle(2)
+    assert r0.collective == r1.collective == "torch"
+    assert r0.comm_status is None and r1.comm_status is None            # no IPC communicator was attached
+    assert r0.tokens == r1.tokens == ref_ids
+    assert np.array_equal(r0.logits, r1.logits)
+    assert np.abs(r0.logits - ref_lg).max() < 1e-3
 
 
 # ---- the RELEASED shard shapes at TP = 8 / 4 / 2 (VERDICT r03 missing #2, r05 missing #3) ------------------------------------------
 REAL_TP_S, REAL_TP_NEW = 45, 6
 
 
-def _tp_real_worker(rank, world, port, ret, layers=2):
+def _tp_real_worker(ctx, layers=2):
     """one rank of the released geometry (H 4096, 32 / 8 heads at d = 128 -> 4 q heads + 1 KV head per rank, I 14336 -> 1792
     columns of every expert per rank, V 51760 -> 6470 vocabulary rows per rank), weights from the counter-based generator
     (this rank's slices only: vita_amd.checkpoint.synth_mixtral_device)."""
@@ -281,37 +208,19 @@ def _tp_real_worker(rank, world, port, ret, layers=2):
     from vita_amd.config import VitaConfig
     from vita_amd.engine import MixtralEngine
     from vita_amd.parallel import setup_tensor_parallel
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.pop("VITA_AMD_TP_FUSE", None)
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda:0")
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        cfg = VitaConfig()
-        cfg.text.num_hidden_layers = layers
-        packed = synth_mixtral_device(cfg, dev, seed=0, rank=rank, world=world)
-        eng = MixtralEngine(cfg, packed, dev, max_ctx=128, max_prefill=64, max_new=16, rank=rank, world=world, logit_rows=16)
-        t = cfg.text
-        # the released shard: TP = 8 -> (4, 1, 1792, 6470); TP = 4 -> (8, 2, 3584, 12940); TP = 2 -> (16, 4, 7168, 25880)
-        assert (eng.c.n_q_heads, eng.c.n_kv_heads, eng.c.inter, eng.c.vocab_n) == (32 // world, 8 // world, 14336 // world, 51760 // world)
-        name = setup_tensor_parallel(eng, rank, world, dev, backend="gloo", collective="ipc")
-        ids = np.random.default_rng(11).integers(3, t.vocab_size, size=REAL_TP_S).tolist()
-        emb = packed["embed"][torch.as_tensor(ids, device=dev)].float()
-        eng.prefill(emb)
-        eng.decode(REAL_TP_NEW - 1)
-        torch.cuda.synchronize()
-        lg = eng.logits_all[:REAL_TP_NEW].cpu()
-        dist.all_reduce(lg)                      # vocab-sharded head: rows hold this rank's slice, zeros elsewhere
-        ret[rank] = (name, eng.generated(), lg.numpy(), comm_status(eng), eng.decode_exchange, eng.decode_schedule())
-        dist.barrier()
-        time.sleep(0.5)                          # gloo: a rank that leaves the barrier first must not close its sockets under the others
-        eng.close()
-    except BaseException:
-        import traceback
-        ret[("error", rank)] = traceback.format_exc()
-        raise
-    finally:
-        dist.destroy_process_group()
+    rank, world, dev = ctx.rank, ctx.world, ctx.dev
+    cfg = VitaConfig()
+    cfg.text.num_hidden_layers = layers
+    packed = synth_mixtral_device(cfg, dev, seed=0, rank=rank, world=world)
+    eng = MixtralEngine(cfg, packed, dev, max_ctx=128, max_prefill=64, max_new=16, rank=rank, world=world, logit_rows=16)
+    ctx.defer(eng.close)
+    t = cfg.text
+    # the released shard: TP = 8 -> (4, 1, 1792, 6470); TP = 4 -> (8, 2, 3584, 12940); TP = 2 -> (16, 4, 7168, 25880)
+    assert (eng.c.n_q_heads, eng.c.n_kv_heads, eng.c.inter, eng.c.vocab_n) == (32 // world, 8 // world, 14336 // world, 51760 // world)
+    name = setup_tensor_parallel(eng, rank, world, dev, backend="gloo", collective="ipc")
+    ids = np.random.default_rng(11).integers(3, t.vocab_size, size=REAL_TP_S).tolist()
+    emb = packed["embed"][torch.as_tensor(ids, device=dev)].float()
+    return greedy_tp_run(eng, emb, REAL_TP_NEW, dist, name)
 
 
 @pytest.mark.timeout(1500)
@@ -327,33 +236,26 @@ def test_tp_released_shard_shapes_match_oracle(dev, world, layers):
     TP = 2 is the degree both web demos deploy (web_demo/web_ability_demo.py:340-348), 2 x TP = 4 is BASELINE configs[4].
     Reference partition: web_demo/vllm_tools/vllm_file/mixtral.py:441-470 (QKVParallelLinear / RowParallelLinear head split),
     :375-414 (FusedMoE intermediate split), :939-951 (ParallelLMHead)."""
-    import torch.multiprocessing as mp
     from oracle import stream
     from vita_amd.config import VitaConfig
-    ret = mp.Manager().dict()
-    try:
-        mp.spawn(_tp_real_worker, args=(world, _free_port(), ret, layers), nprocs=world, join=True)
-    except Exception:
-        for k in sorted(k for k in ret.keys() if isinstance(k, tuple)):
-            print(f"---- rank {k[1]} ----\n{ret[k]}")
-        raise
-    names = {ret[r][0] for r in range(world)}
-    assert len(names) == 1, dict((r, ret[r][0]) for r in range(world))
-    _require_ipc(names, f"released-shape TP = {world}")
-    assert all(ret[r][3] == 0 for r in range(world)) and all(ret[r][4] == "kernel" for r in range(world))
-    assert all(ret[r][5] == "three-launches" for r in range(world)), {r: ret[r][5] for r in range(world)}      # (shared device)
+    ret = run_ranks(_tp_real_worker, world, layers, env={"VITA_AMD_TP_FUSE": None}, deadline_s=120)
+    names = {ret[r].collective for r in range(world)}
+    assert len(names) == 1, dict((r, ret[r].collective) for r in range(world))
+    require_ipc(names, f"released-shape TP = {world}")
+    assert all(ret[r].comm_status == 0 for r in range(world)) and all(ret[r].exchange == "kernel" for r in range(world))
+    assert all(ret[r].schedule == "three-launches" for r in range(world)), {r: ret[r].schedule for r in range(world)}      # (shared device)
     cfg = VitaConfig()
     t = cfg.text
     ids = np.random.default_rng(11).integers(3, t.vocab_size, size=REAL_TP_S).tolist()
-    toks = ret[0][1]
+    toks = ret[0].tokens
     assert len(toks) == REAL_TP_NEW
     full = stream.embed_rows(t, ids + toks[:-1], 0)
     ref = stream.forward(t, 0, full, n_layers=layers, logits_from=REAL_TP_S - 1)
     ref_ids = ref["logits"].argmax(-1).tolist()
     for r in range(world):
-        assert ret[r][1] == ref_ids, f"rank {r}: {ret[r][1]} vs oracle {ref_ids}"
-        assert np.array_equal(ret[r][2], ret[0][2]), f"rank {r} logits differ from rank 0's"
-    err = float(np.abs(ret[0][2] - ref["logits"]).max())
+        assert ret[r].tokens == ref_ids, f"rank {r}: {ret[r].tokens} vs oracle {ref_ids}"
+        assert np.array_equal(ret[r].logits, ret[0].logits), f"rank {r} logits differ from rank 0's"
+    err = float(np.abs(ret[0].logits - ref["logits"]).max())
     print(f"TP = {world} released shard shapes, {layers} layers: ids {toks} == oracle, max |logit diff| {err:.2e}")
     assert err < 1e-3
 

@@ -14,6 +14,7 @@ import pytest
 import torch
 
 from oracle import encoders as oe, hashw, stream
+from tests.ranks import TP_UNSET, greedy_tp_run, require_ipc, run_ranks
 from tests.util import assert_close, report, to_np
 from vita_amd.checkpoint import synth_mixtral_device, synth_state_dict
 from vita_amd.config import VitaConfig
@@ -138,14 +139,7 @@ def test_backbone_32_layers_prefill_and_greedy(run, oracle_embeds, oracle_ref):
 TP8_NEW = 8
 
 
-def _free_port():
-    import socket
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _tp8_omni_worker(rank, world, port, layers, enc_path, ret):
+def _tp8_omni_worker(ctx, layers, enc_path):
     """one rank of the released partition at `world` ranks (TP = 8: 4 q heads + 1 KV head, 1792 columns of every expert, 6470
     vocabulary rows; TP = 2, the degree both web demos run — web_demo/web_ability_demo.py:340-348 —: 16 q + 4 KV heads, 7168
     columns, 25880 rows; web_demo/vllm_tools/vllm_file/mixtral.py:375-414,441-476,939-951) running the WHOLE omni request:
@@ -154,57 +148,41 @@ def _tp8_omni_worker(rank, world, port, layers, enc_path, ret):
     import torch.distributed as dist
     from vita_amd.model.vita_mixtral import VITAMixtralForCausalLM
     from vita_amd.parallel import setup_tensor_parallel
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    os.environ.pop("VITA_AMD_TP_FUSE", None)
-    os.environ.pop("VITA_AMD_TP_TRIAL", None)
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda:0")
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        tw = [time.time()]
-        lap = lambda: (tw.append(time.time()), tw[-1] - tw[-2])[1]
-        cfg = VitaConfig()
-        cfg.text.num_hidden_layers = layers
-        packed = synth_mixtral_device(cfg, dev, seed=SEED, rank=rank, world=world)
-        t_w = lap()
-        # the replicated encoder weights: the parent's state dict, memory-mapped (generating 0.7 B values takes ~45 s per process)
-        sd_enc = {k: v.numpy() for k, v in torch.load(enc_path, mmap=True, weights_only=True).items()}
-        model = VITAMixtralForCausalLM(cfg, sd_enc, device=dev, packed_llm=packed, max_new_tokens=TP8_NEW + 8, max_prefill=640,
-                                       rank=rank, world=world, keep_scores=True)
-        eng = model.engine
-        assert (eng.c.n_q_heads, eng.c.n_kv_heads, eng.c.inter) == (32 // world, 8 // world, 14336 // world)
-        assert eng.c.vocab_n in (51760 // world, 51760 // world + 1)
-        t_m = lap()
-        name = setup_tensor_parallel(eng, rank, world, dev, backend="gloo", collective="ipc")
-        t_tp = lap()
-        model.get_vision_tower().load_model()
-        req = make_request(cfg)
-        pix = torch.from_numpy(req["pixel_values"]).to(dev)
-        feats = torch.from_numpy(req["fbank"]).to(dev)
-        ids = torch.tensor([req["input_ids"]], dtype=torch.long, device=dev)
-        audios = {"audios": feats[None], "lengths": torch.tensor([feats.shape[0]], device=dev)}
-        _, _, _, _, emb, _ = model.prepare_inputs_labels_for_multimodal(ids, None, None, None, None, pix, audios)
-        torch.cuda.synchronize()
-        t_enc = lap()
-        eng.prefill(emb[0])
-        torch.cuda.synchronize()
-        t_pf = lap()
-        eng.decode(TP8_NEW - 1)
-        torch.cuda.synchronize()
-        t_dec = lap()
-        if rank == 0:
-            print(f"[realgeom] TP = {world} rank 0: weights {t_w:.1f}s, model {t_m:.1f}s, collective bring-up {t_tp:.1f}s, encoders + splice "
-                  f"{t_enc:.1f}s, prefill {t_pf:.1f}s, {TP8_NEW - 1} decode steps {t_dec:.1f}s", flush=True)
-        lg = eng.logits_all[:TP8_NEW].cpu()
-        dist.all_reduce(lg)                      # vocab-sharded head: rows hold this rank's slice, zeros elsewhere
-        c = getattr(eng, "_comm", None)
-        ret[rank] = (name, eng.generated(), lg.numpy() if rank == 0 else None, c.status() if c is not None else None,
-                     eng.decode_exchange, int(emb.shape[1]), lg.numpy().tobytes() if rank > 0 else None, eng.decode_schedule())
-        dist.barrier()
-        time.sleep(0.5)                          # gloo: a rank that leaves the barrier first must not close its sockets under the others
-        eng.close()
-    finally:
-        dist.destroy_process_group()
+    rank, world, dev = ctx.rank, ctx.world, ctx.dev
+    tw = [time.time()]
+    lap = lambda: (tw.append(time.time()), tw[-1] - tw[-2])[1]
+    cfg = VitaConfig()
+    cfg.text.num_hidden_layers = layers
+    packed = synth_mixtral_device(cfg, dev, seed=SEED, rank=rank, world=world)
+    t_w = lap()
+    # the replicated encoder weights: the parent's state dict, memory-mapped (generating 0.7 B values takes ~45 s per process)
+    sd_enc = {k: v.numpy() for k, v in torch.load(enc_path, mmap=True, weights_only=True).items()}
+    model = VITAMixtralForCausalLM(cfg, sd_enc, device=dev, packed_llm=packed, max_new_tokens=TP8_NEW + 8, max_prefill=640,
+                                   rank=rank, world=world, keep_scores=True)
+    eng = model.engine
+    ctx.defer(eng.close)
+    assert (eng.c.n_q_heads, eng.c.n_kv_heads, eng.c.inter) == (32 // world, 8 // world, 14336 // world)
+    assert eng.c.vocab_n in (51760 // world, 51760 // world + 1)
+    t_m = lap()
+    name = setup_tensor_parallel(eng, rank, world, dev, backend="gloo", collective="ipc")
+    t_tp = lap()
+    model.get_vision_tower().load_model()
+    req = make_request(cfg)
+    pix = torch.from_numpy(req["pixel_values"]).to(dev)
+    feats = torch.from_numpy(req["fbank"]).to(dev)
+    ids = torch.tensor([req["input_ids"]], dtype=torch.long, device=dev)
+    audios = {"audios": feats[None], "lengths": torch.tensor([feats.shape[0]], device=dev)}
+    _, _, _, _, emb, _ = model.prepare_inputs_labels_for_multimodal(ids, None, None, None, None, pix, audios)
+    torch.cuda.synchronize()
+    t_enc = lap()
+    run = greedy_tp_run(eng, emb[0], TP8_NEW, dist, name, timed=True)
+    if rank == 0:
+        print(f"[realgeom] TP = {world} rank 0: weights {t_w:.1f}s, model {t_m:.1f}s, collective bring-up {t_tp:.1f}s, encoders + splice "
+              f"{t_enc:.1f}s, prefill {run.prefill_s:.1f}s, {TP8_NEW - 1} decode steps {run.decode_s:.1f}s", flush=True)
+    run.rows = int(emb.shape[1])
+    if rank > 0:                         # rank 0 sends the array, the others the bytes the parent compares with it
+        run.logits, run.logits_bytes = None, run.logits.tobytes()
+    return run
 
 
 @pytest.mark.timeout(1500)
@@ -219,34 +197,28 @@ def test_tp_full_depth_omni_matches_oracle(run, oracle_ref, tmp_path, world):
     run the decode attention block as three launches; its one-launch form: tests/test_comm_gpu.py test_loopback_*).  Greedy ids == the streamed fp32
     oracle's and logits within 1e-3 (the oracle pass is the one test_backbone_32_layers_prefill_and_greedy paid for: same
     request, and the tokens must agree), every rank bit-identical, no spin time-out."""
-    import torch.multiprocessing as mp
     cfg = run["cfg"]
     L = cfg.text.num_hidden_layers
     t0 = time.time()
     enc_path = str(tmp_path / "encoders.pt")
     torch.save({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in run["sd_enc"].items()}, enc_path)
-    ret = mp.Manager().dict()
-    mp.spawn(_tp8_omni_worker, args=(world, _free_port(), L, enc_path, ret), nprocs=world, join=True)
+    ret = run_ranks(_tp8_omni_worker, world, L, enc_path, env=TP_UNSET, deadline_s=120)
     print(f"[realgeom] TP = {world} ranks done in {time.time() - t0:.1f}s")
-    names = {ret[r][0] for r in range(world)}
-    assert len(names) == 1, {r: ret[r][0] for r in range(world)}
-    if names != {"ipc"}:
-        msg = f"the ranks agreed on {names}, not on the IPC all-reduce: configs[3] ran over gloo on this box"
-        if os.environ.get("VITA_ALLOW_GLOO_FALLBACK", "") == "1":
-            pytest.xfail(msg)
-        pytest.fail(msg)
-    assert all(ret[r][3] == 0 for r in range(world)), {r: ret[r][3] for r in range(world)}
-    assert all(ret[r][5] == 552 for r in range(world))
-    toks = ret[0][1]
-    lg0 = ret[0][2]
+    names = {ret[r].collective for r in range(world)}
+    assert len(names) == 1, {r: ret[r].collective for r in range(world)}
+    require_ipc(names, "configs[3]")
+    assert all(ret[r].comm_status == 0 for r in range(world)), {r: ret[r].comm_status for r in range(world)}
+    assert all(ret[r].rows == 552 for r in range(world))
+    toks = ret[0].tokens
+    lg0 = ret[0].logits
     for r in range(1, world):
-        assert ret[r][1] == toks, f"rank {r}: {ret[r][1]} vs rank 0 {toks}"
-        assert ret[r][6] == lg0.tobytes(), f"rank {r} logits differ from rank 0's"
+        assert ret[r].tokens == toks, f"rank {r}: {ret[r].tokens} vs rank 0 {toks}"
+        assert ret[r].logits_bytes == lg0.tobytes(), f"rank {r} logits differ from rank 0's"
     ref_lg = oracle_ref["logits"][:TP8_NEW]
     ref_ids = ref_lg.argmax(-1).tolist()
     err = float(np.abs(lg0 - ref_lg).max())
     print(f"TP = {world}, {L} layers, S = 552 omni request: ids {toks}, oracle {ref_ids}, TP = 1 device {run['toks'][:TP8_NEW]}, "
-          f"max |logit diff| {err:.2e}, exchange form {ret[0][4]}, decode schedule {ret[0][7]}")
-    assert all(ret[r][7] == "three-launches" for r in range(world)), {r: ret[r][7] for r in range(world)}      # ranks sharing a device (DESIGN 5.1)
+          f"max |logit diff| {err:.2e}, exchange form {ret[0].exchange}, decode schedule {ret[0].schedule}")
+    assert all(ret[r].schedule == "three-launches" for r in range(world)), {r: ret[r].schedule for r in range(world)}      # ranks sharing a device (DESIGN 5.1)
     assert toks == ref_ids
     assert err < 1e-3

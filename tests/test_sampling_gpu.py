@@ -2,15 +2,13 @@
 the RNG pinned to numpy's Philox, every token of the filter kernel equal to the restatement, the draw distribution, degenerate
 rows, the engine's generate() across lookahead windows, and the serving surfaces (LLM, AsyncLLMEngine, recompute preemption)."""
 import asyncio
-import os
-import socket
-import time
 
 import numpy as np
 import pytest
 import torch
 
 from tests import sampling_ref as ref
+from tests.ranks import run_ranks
 from vita_amd import ops
 from vita_amd.checkpoint import synth_state_dict
 from vita_amd.config import VitaConfig
@@ -265,63 +263,37 @@ TP_MODES = {"temperature": dict(temperature=1.2, top_k=0, top_p=1.0, seed=77),
             "top_p": dict(temperature=0.9, top_k=0, top_p=0.8, seed=78)}
 
 
-def _free_port():
-    with socket.socket() as so:
-        so.bind(("127.0.0.1", 0))
-        return so.getsockname()[1]
-
-
-def _tp_sampling_worker(rank, world, port, shard_vocab, ret):
+def _tp_sampling_worker(ctx, shard_vocab):
     import torch.distributed as dist
     from vita_amd._lib import VitaHipError
     from vita_amd.checkpoint import pack_mixtral
     from vita_amd.engine import MixtralEngine
     from vita_amd.parallel import setup_tensor_parallel
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
-    torch.cuda.set_device(0)
-    dev = torch.device("cuda:0")
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        cfg = VitaConfig.tiny()
-        sd = synth_state_dict(cfg, seed=3, parts=("text",))
-        packed = pack_mixtral(sd, cfg, dev, rank=rank, world=world, shard_vocab=shard_vocab)
-        eng = MixtralEngine(cfg, packed, dev, max_ctx=128, max_prefill=64, max_new=16, rank=rank, world=world, logit_rows=16)
-        name = setup_tensor_parallel(eng, rank, world, dev, backend="gloo", collective="ipc")
-        ids = np.random.default_rng(5).integers(3, cfg.text.vocab_size, size=37).tolist()
-        emb = packed["embed"][torch.as_tensor(ids, device=dev)].float()
-        out = {"collective": name, "sharded": eng.vocab_sharded}
-        for mode, kw in TP_MODES.items():
-            try:
-                eng.set_sampling(**kw)
-            except VitaHipError as e:
-                out[mode] = ("raised", str(e))
-                continue
-            eng.prefill(emb)
-            eng.decode(11)
-            torch.cuda.synchronize()
-            lg = eng.logits_all[:12].cpu()
-            if eng.vocab_sharded:
-                dist.all_reduce(lg)              # a kept row holds this rank's slice and zeros elsewhere
-            out[mode] = (eng.generated(), lg.numpy())
-        eng.set_sampling()
-        ret[rank] = out
-        dist.barrier()
-        time.sleep(0.5)
-        eng.close()
-    except BaseException:
-        import traceback
-        ret[("error", rank)] = traceback.format_exc()
-        raise
-    finally:
-        dist.destroy_process_group()
-
-
-def _run_tp(shard_vocab):
-    import torch.multiprocessing as mp
-    ret = mp.Manager().dict()
-    mp.spawn(_tp_sampling_worker, args=(2, _free_port(), shard_vocab, ret), nprocs=2, join=True)
-    assert 0 in ret and 1 in ret, dict(ret)
-    return ret[0], ret[1]
+    rank, world, dev = ctx.rank, ctx.world, ctx.dev
+    cfg = VitaConfig.tiny()
+    sd = synth_state_dict(cfg, seed=3, parts=("text",))
+    packed = pack_mixtral(sd, cfg, dev, rank=rank, world=world, shard_vocab=shard_vocab)
+    eng = MixtralEngine(cfg, packed, dev, max_ctx=128, max_prefill=64, max_new=16, rank=rank, world=world, logit_rows=16)
+    ctx.defer(eng.close)
+    name = setup_tensor_parallel(eng, rank, world, dev, backend="gloo", collective="ipc")
+    ids = np.random.default_rng(5).integers(3, cfg.text.vocab_size, size=37).tolist()
+    emb = packed["embed"][torch.as_tensor(ids, device=dev)].float()
+    out = {"collective": name, "sharded": eng.vocab_sharded}
+    for mode, kw in TP_MODES.items():
+        try:
+            eng.set_sampling(**kw)
+        except VitaHipError as e:
+            out[mode] = ("raised", str(e))
+            continue
+        eng.prefill(emb)
+        eng.decode(11)
+        torch.cuda.synchronize()
+        lg = eng.logits_all[:12].cpu()
+        if eng.vocab_sharded:
+            dist.all_reduce(lg)              # a kept row holds this rank's slice and zeros elsewhere
+        out[mode] = (eng.generated(), lg.numpy())
+    eng.set_sampling()
+    return out
 
 
 def _check_draws(r0, r1, mode):
@@ -337,7 +309,7 @@ def _check_draws(r0, r1, mode):
 def test_tp2_vocab_sharded_head_samples_temperature_only_and_refuses_filters():
     """sharded head: each rank draws over its slice (global vocab indices), the exact candidates travel through the all-reduce,
     both ranks emit the same ids — the restatement's on the gathered rows; top-p is refused (VH_E_ARG)."""
-    r0, r1 = _run_tp(True)
+    r0, r1 = run_ranks(_tp_sampling_worker, 2, True, deadline_s=120)
     assert r0["collective"] == r1["collective"] == "ipc" and r0["sharded"] and r1["sharded"]
     _check_draws(r0, r1, "temperature")
     for r in (r0, r1):
@@ -346,7 +318,7 @@ def test_tp2_vocab_sharded_head_samples_temperature_only_and_refuses_filters():
 
 def test_tp2_unsharded_head_draws_the_same_token_on_every_rank():
     """unsharded head under TP: every rank holds the same logits and draws the same token, temperature-only and top-p."""
-    r0, r1 = _run_tp(False)
+    r0, r1 = run_ranks(_tp_sampling_worker, 2, False, deadline_s=120)
     assert r0["collective"] == r1["collective"] == "ipc" and not r0["sharded"] and not r1["sharded"]
     _check_draws(r0, r1, "temperature")
     _check_draws(r0, r1, "top_p")

@@ -4,7 +4,6 @@ SamplingParams(temperature=0.01) == greedy — must produce the tokens of the OR
 oracle/mixtral.py on the same state dict and inputs), and the same tokens as the HF-flavour boundary."""
 import json
 import os
-import time
 
 import numpy as np
 import pytest
@@ -12,6 +11,7 @@ import torch
 from PIL import Image
 
 from tests import tiny_ckpt
+from tests.ranks import run_ranks
 
 pytestmark = pytest.mark.gpu
 IMG_ID, AUD_ID = 990, 991      # stand-ins for 51000 / 51001 inside the tiny 1000-entry vocabulary
@@ -92,28 +92,18 @@ def test_text_only_and_errors(served, dev):
 
 
 # ---- tensor_parallel_size = 2: two LLM processes (one GPU, gloo bootstrap, the library's IPC all-reduce) -------------
-def _tp_llm_worker(rank, world, port, ckpt, prompts, ret):
-    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), WORLD_SIZE=str(world), RANK=str(rank),
-                      LOCAL_RANK="0", VITA_AMD_DIST_BACKEND="gloo")
-    import torch.distributed as dist
+def _tp_llm_worker(ctx, ckpt, prompts):
     from vita_amd.serving import LLM, SamplingParams
-    llm = LLM(model=ckpt, dtype="float16", tensor_parallel_size=world, max_new_tokens=16)
-    try:
-        outs = llm.generate([{"prompt_token_ids": p} for p in prompts],
-                            sampling_params=SamplingParams(temperature=0.01, max_tokens=8))
-        ret[rank] = (llm.collective, [o.outputs[0].token_ids for o in outs])
-        dist.barrier()
-    finally:
-        llm.model.engine.close()
-        if dist.is_initialized():
-            dist.destroy_process_group()
+    llm = LLM(model=ckpt, dtype="float16", tensor_parallel_size=ctx.world, max_new_tokens=16)
+    ctx.defer(llm.model.engine.close)
+    outs = llm.generate([{"prompt_token_ids": p} for p in prompts],
+                        sampling_params=SamplingParams(temperature=0.01, max_tokens=8))
+    return (llm.collective, [o.outputs[0].token_ids for o in outs])
 
 
 def test_llm_tensor_parallel_two_processes(served, dev):
     """`LLM(..., tensor_parallel_size=2)` under a one-process-per-GPU launch: each process builds its rank's shard, brings up
     the collective itself and serves the same requests; both ranks return the single-process tokens."""
-    import socket
-    import torch.multiprocessing as mp
     from oracle import mixtral as om
     from vita_amd.config import VitaConfig
     from vita_amd.serving import SamplingParams
@@ -124,10 +114,8 @@ def test_llm_tensor_parallel_two_processes(served, dev):
     for p, e in zip(prompts, exp):                      # the single-process tokens are the oracle's
         o, _ = om.MixtralOracle(sd, VitaConfig.tiny().text).greedy(sd["model.embed_tokens.weight"][p], 8)
         assert e == o[:len(e)] and (len(e) == 8 or e[-1] == 2), (e, o)
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
-    ret = mp.Manager().dict()
-    mp.spawn(_tp_llm_worker, args=(2, port, d, prompts, ret), nprocs=2, join=True)
-    assert ret[0][0] == ret[1][0] and ret[0][0] in ("ipc", "torch"), dict(ret)
-    assert ret[0][1] == exp and ret[1][1] == exp, (dict(ret), exp)
+    # the environment of a one-process-per-GPU launcher; LLM creates the process group itself
+    env = {"WORLD_SIZE": "{world}", "RANK": "{rank}", "LOCAL_RANK": "0", "VITA_AMD_DIST_BACKEND": "gloo"}
+    ret = run_ranks(_tp_llm_worker, 2, d, prompts, env=env, init_group=False, deadline_s=120)
+    assert ret[0][0] == ret[1][0] and ret[0][0] in ("ipc", "torch"), ret
+    assert ret[0][1] == exp and ret[1][1] == exp, (ret, exp)

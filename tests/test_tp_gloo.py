@@ -8,15 +8,14 @@ come from vita_amd.checkpoint.tp_slices — the same function pack_mixtral() use
 engine — so this test proves the partition + collective placement reproduces the unsharded
 oracle; the per-rank arithmetic here is the oracle's (no GPU in this container)."""
 import os
-import socket
 
 import numpy as np
 import pytest
 import torch
 import torch.distributed as dist
-import torch.multiprocessing as mp
 
 from oracle import mixtral as om
+from tests.ranks import run_ranks
 from vita_amd.checkpoint import synth_state_dict, tp_slices, vocab_shard
 from vita_amd.config import VitaConfig
 
@@ -57,63 +56,50 @@ def _tp_forward(sd, t, x, rank, world, n_allreduce):
     return (om.rmsnorm(x[-1:], g("model.norm.weight"), t.rms_norm_eps) @ g("lm_head.weight").T).astype(F32)[0]
 
 
-def _worker(rank, world, port, ret):
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        cfg = VitaConfig.tiny()
-        sd = synth_state_dict(cfg, seed=0, rich=True, parts=("text",))
-        rng = np.random.default_rng(7)
-        ids = rng.integers(3, cfg.text.vocab_size, size=19)
-        x = np.asarray(sd["model.embed_tokens.weight"], F32)[ids]
-        n_ar = [0]
-        logits = _tp_forward(sd, cfg.text, x, rank, world, n_ar)
-        gathered = [torch.zeros(logits.shape[0]) for _ in range(world)]
-        dist.all_gather(gathered, torch.from_numpy(logits))
-        # vocab-sharded LM head (ParallelLMHead + logits gather, vllm_file/mixtral.py:939-951) as the engine does it: every
-        # rank scores ITS rows (vita_amd.checkpoint.vocab_shard), keeps one (max, global index) candidate, writes it into
-        # its slot of a zeroed [world][2] vector, the vector is all-reduced (adding zeros is exact; indices < 2^24 are
-        # exact in fp32) and every rank takes the same argmax with the lowest-index tie rule
-        lo, nrows = vocab_shard(cfg.text.vocab_size, rank, world)
-        mine = logits[lo:lo + nrows]
-        cand = np.zeros((world, 2), F32)
-        j = int(np.argmax(mine))                                  # first maximum = lowest index
-        cand[rank] = (mine[j], lo + j)
-        cand = _allreduce(cand)
-        best = max(range(world), key=lambda r: (cand[r, 0], -cand[r, 1]))
-        tok_sharded = int(cand[best, 1])
-        toks = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
-        dist.all_gather(toks, torch.tensor([tok_sharded]))
-        if rank == 0:
-            full, _ = om.MixtralOracle(sd, cfg.text).forward(x)
-            ret["err"] = float(np.max(np.abs(full[-1] - logits)))
-            ret["argmax_same"] = bool(int(np.argmax(full[-1])) == int(np.argmax(logits)))
-            ret["ranks_agree"] = bool(all(torch.equal(gathered[0], gi) for gi in gathered))
-            ret["n_allreduce"] = n_ar[0]
-            ret["sharded_token_same"] = bool(tok_sharded == int(np.argmax(logits)) and all(int(t[0]) == tok_sharded for t in toks))
-            ret["layers"] = cfg.text.num_hidden_layers
-    finally:
-        dist.destroy_process_group()
-
-
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
+def _worker(ctx):
+    rank, world = ctx.rank, ctx.world
+    cfg = VitaConfig.tiny()
+    sd = synth_state_dict(cfg, seed=0, rich=True, parts=("text",))
+    rng = np.random.default_rng(7)
+    ids = rng.integers(3, cfg.text.vocab_size, size=19)
+    x = np.asarray(sd["model.embed_tokens.weight"], F32)[ids]
+    n_ar = [0]
+    logits = _tp_forward(sd, cfg.text, x, rank, world, n_ar)
+    gathered = [torch.zeros(logits.shape[0]) for _ in range(world)]
+    dist.all_gather(gathered, torch.from_numpy(logits))
+    # vocab-sharded LM head (ParallelLMHead + logits gather, vllm_file/mixtral.py:939-951) as the engine does it: every
+    # rank scores ITS rows (vita_amd.checkpoint.vocab_shard), keeps one (max, global index) candidate, writes it into
+    # its slot of a zeroed [world][2] vector, the vector is all-reduced (adding zeros is exact; indices < 2^24 are
+    # exact in fp32) and every rank takes the same argmax with the lowest-index tie rule
+    lo, nrows = vocab_shard(cfg.text.vocab_size, rank, world)
+    mine = logits[lo:lo + nrows]
+    cand = np.zeros((world, 2), F32)
+    j = int(np.argmax(mine))                                  # first maximum = lowest index
+    cand[rank] = (mine[j], lo + j)
+    cand = _allreduce(cand)
+    best = max(range(world), key=lambda r: (cand[r, 0], -cand[r, 1]))
+    tok_sharded = int(cand[best, 1])
+    toks = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+    dist.all_gather(toks, torch.tensor([tok_sharded]))
+    if rank != 0:
+        return None
+    full, _ = om.MixtralOracle(sd, cfg.text).forward(x)
+    return {"err": float(np.max(np.abs(full[-1] - logits))),
+            "argmax_same": bool(int(np.argmax(full[-1])) == int(np.argmax(logits))),
+            "ranks_agree": bool(all(torch.equal(gathered[0], gi) for gi in gathered)),
+            "n_allreduce": n_ar[0],
+            "sharded_token_same": bool(tok_sharded == int(np.argmax(logits)) and all(int(t[0]) == tok_sharded for t in toks)),
+            "layers": cfg.text.num_hidden_layers}
 
 
 @pytest.mark.timeout(300)
 def test_tp2_partition_matches_unsharded_oracle():
-    world = 2
-    with mp.Manager() as mgr:
-        ret = mgr.dict()
-        mp.spawn(_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
-        assert ret["ranks_agree"]                        # every rank ends with identical logits
-        assert ret["n_allreduce"] == 2 * ret["layers"]   # the reference's 2 collectives per layer
-        assert ret["err"] < 1e-4, ret["err"]             # fp32 summation-order noise only
-        assert ret["argmax_same"]
-        assert ret["sharded_token_same"]                 # the (max, index) exchange of the vocab-sharded head picks the same token
+    ret = run_ranks(_worker, 2, deadline_s=120, gpu=False)[0]      # rank 0 reports for both
+    assert ret["ranks_agree"]                        # every rank ends with identical logits
+    assert ret["n_allreduce"] == 2 * ret["layers"]   # the reference's 2 collectives per layer
+    assert ret["err"] < 1e-4, ret["err"]             # fp32 summation-order noise only
+    assert ret["argmax_same"]
+    assert ret["sharded_token_same"]                 # the (max, index) exchange of the vocab-sharded head picks the same token
 
 
 def test_tp_slices_cover_real_geometry():
@@ -141,55 +127,45 @@ def test_vocab_shards_cover_the_table():
         assert all(rows[r][0] + rows[r][1] == rows[r + 1][0] for r in range(world - 1))
 
 
-def _vote_worker(rank, world, port, ret):
+def _vote_worker(ctx):
     """each rank brings DIFFERENT local measurements; the vote must come out the same on both (MAX-reduced times, any bad
     trial or a shared device forces "kernel")."""
     from vita_amd.parallel import collective_label, vote_decode_exchange
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
-    try:
-        cases = {
-            # name: (same_device, t_kernel per rank, t_fused per rank, fused_ok per rank)
-            "fused_wins": (False, (40.0, 41.0), (33.0, 34.0), (True, True)),
-            "fused_slower_on_one_rank": (False, (40.0, 40.0), (30.0, 45.0), (True, True)),   # slowest rank decides
-            "within_margin": (False, (40.0, 40.0), (39.5, 39.7), (True, True)),              # < 2 % better: keep the kernel form
-            "one_rank_timed_out": (False, (40.0, 40.0), (20.0, 20.0), (True, False)),
-            "shared_device": (True, (40.0, 40.0), (10.0, 10.0), (True, True)),
-            "shared_on_one_rank_only": (rank == 1, (40.0, 40.0), (10.0, 10.0), (True, True)),  # a disagreeing flag is still "shared"
-            "no_timing": (False, (0.0, 0.0), (0.0, 0.0), (True, True)),
-        }
-        out = {}
-        for name, (same, tk, tf, ok) in cases.items():
-            same_flag = same if isinstance(same, bool) else bool(same)
-            choice, tk_all, tf_all = vote_decode_exchange(dist, same_flag, tk[rank], tf[rank], ok[rank])
-            out[name] = (choice, tk_all, tf_all)
-        ret[rank] = out
+    rank = ctx.rank
+    cases = {
+        # name: (same_device, t_kernel per rank, t_fused per rank, fused_ok per rank)
+        "fused_wins": (False, (40.0, 41.0), (33.0, 34.0), (True, True)),
+        "fused_slower_on_one_rank": (False, (40.0, 40.0), (30.0, 45.0), (True, True)),   # slowest rank decides
+        "within_margin": (False, (40.0, 40.0), (39.5, 39.7), (True, True)),              # < 2 % better: keep the kernel form
+        "one_rank_timed_out": (False, (40.0, 40.0), (20.0, 20.0), (True, False)),
+        "shared_device": (True, (40.0, 40.0), (10.0, 10.0), (True, True)),
+        "shared_on_one_rank_only": (rank == 1, (40.0, 40.0), (10.0, 10.0), (True, True)),  # a disagreeing flag is still "shared"
+        "no_timing": (False, (0.0, 0.0), (0.0, 0.0), (True, True)),
+    }
+    out = {}
+    for name, (same, tk, tf, ok) in cases.items():
+        same_flag = same if isinstance(same, bool) else bool(same)
+        choice, tk_all, tf_all = vote_decode_exchange(dist, same_flag, tk[rank], tf[rank], ok[rank])
+        out[name] = (choice, tk_all, tf_all)
 
-        class E:
-            decode_exchange = out["fused_wins"][0]
-        ret[f"label{rank}"] = (collective_label(E(), "ipc"), collective_label(E(), "rccl"))
-    finally:
-        dist.destroy_process_group()
+    class E:
+        decode_exchange = out["fused_wins"][0]
+    return out, (collective_label(E(), "ipc"), collective_label(E(), "rccl"))
 
 
 @pytest.mark.timeout(120)
 def test_decode_exchange_vote_is_rank_consistent():
     """the ranks agree on the batch-1 decode exchange form from their own timings; ranks on one device always
     get the kernel form."""
-    world = 2
-    with mp.Manager() as mgr:
-        ret = mgr.dict()
-        mp.spawn(_vote_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
-        a, b = ret[0], ret[1]
-        assert a == b                                            # same choice AND same reduced numbers on every rank
-        assert a["fused_wins"] == ("fused", 41.0, 34.0)
-        assert a["fused_slower_on_one_rank"][0] == "kernel"
-        assert a["within_margin"][0] == "kernel"
-        assert a["one_rank_timed_out"][0] == "kernel"
-        assert a["shared_device"][0] == "kernel" and a["shared_on_one_rank_only"][0] == "kernel"
-        assert a["no_timing"][0] == "kernel"
-        assert ret["label0"] == ret["label1"] == ("ipc+fused", "rccl")
+    (a, label0), (b, label1) = run_ranks(_vote_worker, 2, deadline_s=60, gpu=False)
+    assert a == b                                            # same choice AND same reduced numbers on every rank
+    assert a["fused_wins"] == ("fused", 41.0, 34.0)
+    assert a["fused_slower_on_one_rank"][0] == "kernel"
+    assert a["within_margin"][0] == "kernel"
+    assert a["one_rank_timed_out"][0] == "kernel"
+    assert a["shared_device"][0] == "kernel" and a["shared_on_one_rank_only"][0] == "kernel"
+    assert a["no_timing"][0] == "kernel"
+    assert label0 == label1 == ("ipc+fused", "rccl")
 
 
 class _ScriptedEngine:
@@ -222,11 +198,9 @@ class _ScriptedComm:
         return 0
 
 
-def _trial_worker(rank, world, port, ret):
+def _trial_worker(ctx):
     import vita_amd.parallel as par
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    rank, world = ctx.rank, ctx.world
     par._device_sync = lambda: None
     tuned = []
     import vita_amd._lib as lib
@@ -261,27 +235,22 @@ def _trial_worker(rank, world, port, ret):
             out["mismatch"] = type(ex).__name__
         os.environ["VITA_AMD_TP_FUSE"] = "1"
         out["forced"] = par.choose_decode_exchange(_ScriptedEngine(rank), _ScriptedComm(), rank, world, dist, "cpu", "gloo", True)
-        ret[rank] = out
+        return out
     finally:
         lib.tune = lib_tune
         os.environ.pop("VITA_AMD_TP_FUSE", None)
         os.environ.pop("VITA_AMD_TP_TRIAL", None)
-        dist.destroy_process_group()
 
 
 @pytest.mark.timeout(120)
 def test_decode_exchange_trial_is_all_or_none():
     """every leg of the timed trial is entered by all ranks or by none, a failing rank takes its peers to the vote
     instead of leaving them in a collective, a forced form is checked across the ranks, and the engine is reset afterwards."""
-    world = 2
-    with mp.Manager() as mgr:
-        ret = mgr.dict()
-        mp.spawn(_trial_worker, args=(world, _free_port(), ret), nprocs=world, join=True)
-        a, b = ret[0], ret[1]
-        assert a["healthy"][0] == b["healthy"][0] and a["healthy"][0] in ("kernel", "fused")
-        assert a["healthy"][1:] == b["healthy"][1:] == (2, 1)                 # two legs, one reset
-        assert a["one_rank_fails"][0] == b["one_rank_fails"][0] == "kernel"
-        assert a["one_rank_fails"][1] == b["one_rank_fails"][1] == 1          # the second leg was entered by nobody
-        assert a["one_rank_fails"][2] == b["one_rank_fails"][2] == 1
-        assert a["mismatch"] == b["mismatch"] == "VitaHipError"
-        assert a["forced"] == b["forced"] == "fused"
+    a, b = run_ranks(_trial_worker, 2, deadline_s=60, gpu=False)
+    assert a["healthy"][0] == b["healthy"][0] and a["healthy"][0] in ("kernel", "fused")
+    assert a["healthy"][1:] == b["healthy"][1:] == (2, 1)                 # two legs, one reset
+    assert a["one_rank_fails"][0] == b["one_rank_fails"][0] == "kernel"
+    assert a["one_rank_fails"][1] == b["one_rank_fails"][1] == 1          # the second leg was entered by nobody
+    assert a["one_rank_fails"][2] == b["one_rank_fails"][2] == 1
+    assert a["mismatch"] == b["mismatch"] == "VitaHipError"
+    assert a["forced"] == b["forced"] == "fused"
