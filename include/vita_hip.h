@@ -37,9 +37,9 @@ extern "C" {
 
 int vh_version(void);
 const char* vh_last_error(void);
-/* Kernel-variant knobs (21 keys: "batch_moe_min", "batch_decode", "attn_impl", "attn_fa", "attn_rows", "attn_ksplit",
+/* Kernel-variant knobs (22 keys: "batch_moe_min", "batch_decode", "attn_impl", "attn_fa", "attn_rows", "attn_ksplit",
  * "prefill_attn_gemm", "prefill_fuse_rows", "ps_cfg", "ps_nt", "tp_overlap", "moe_ksplit", "force_allreduce", "tp_fuse",
- * "comm_allow_coarse", "comm_ranks_per_device", "dec_fused", "dec_gateup_grid", "attn_img", "attn_xcd", "ps_xcd"; vita_amd/csrc/vh_kernels.h: VhTuning says what each selects); the defaults are the
+ * "comm_allow_coarse", "comm_ranks_per_device", "dec_fused", "dec_gateup_grid", "attn_img", "attn_xcd", "ps_xcd", "step_attn"; vita_amd/csrc/vh_kernels.h: VhTuning says what each selects); the defaults are the
  * measured-best variants, ids are identical across variants.  Unknown keys (e.g. of variants removed in r04) return VH_E_ARG. */
 int vh_tune(const char* key, int value);
 
@@ -430,6 +430,29 @@ int vh_mixtral_seq_decode(vh_mixtral_t* m, const int* seqs /* host */, int n, vo
  * bit-identical with the one-by-one path.  K / V tile images stay a feature of the one-segment pass. */
 int vh_mixtral_seq_prefill_batch(vh_mixtral_t* m, const int* seqs /* host */, const int* lens /* host */, int n,
                                  const float* embeds, float* logits_out, void* stream);
+/* A MIXED pass (vLLM's enable_chunked_prefill: the next token of every running sequence rides as one extra row in the pass that
+ * prefills the new prompts; what it replaces is the pair of a vh_mixtral_seq_prefill_batch call and the vh_mixtral_seq_decode
+ * iteration behind it - two passes over the weights).  The rows of the pass are the prefill segments back to back (embeds: device
+ * fp32 [sum(pf_lens)][hidden]; nullable when n_pf == 0), then one row per decode member: the embedding the last select left in that
+ * sequence's state.  Segment i behaves exactly as in vh_mixtral_seq_prefill_batch (first token in seq_tokens[0], n_generated
+ * restarts at 0); every sequence of dec_seqs advances ONE step exactly as vh_mixtral_seq_decode would advance it: its token is
+ * appended, its position, draw index, penalty table and logprob rows go on (its counters are NOT reset).  A prompt longer than the
+ * caller's row budget goes in as chunks over consecutive calls; only the last chunk's token counts.  logits_out (nullable): device
+ * fp32 [n_pf + n_dec][vocab], rows in list order (prefill segments' last positions, then the decode rows).
+ *   The WHOLE call is checked before anything is enqueued or allocated: n_pf + n_dec in [1, max_seqs], every slot live, not poisoned
+ * and listed once across BOTH lists, every pf_lens[i] >= 1, sum(pf_lens) + n_dec <= max_prefill, every position + rows < max_ctx,
+ * decode members have a prompt (position >= 1); VH_E_FULL when the pool cannot hold all members (vh_mixtral_pages_free and every
+ * vh_mixtral_seq_pos are then what they were).  A failure after the first enqueue poisons exactly the listed sequences.
+ * n_dec == 0 IS vh_mixtral_seq_prefill_batch; n_pf == 0 is a decode-only pass (the batched iteration's streaming MoE with the
+ * projections on the GEMM too).
+ *   The single rows' attention: the split-KV row kernels of vh_attn_rows at head_dim 128 with up to 4 query heads per KV head
+ * (vh_tune("step_attn", 0), or another geometry: 1-row segments of the prefill's segment attention).
+ *   Numerics: every row sees the project's exact-mode arithmetic - bf16 hi + lo planes in the GEMMs (the expert formats unchanged),
+ * fp32 attention for the single rows.  Ids and scores of a sequence agree with the fp32 oracle of THAT SEQUENCE ALONE within the
+ * project's bar (ids equal, scores atol 1e-3); a decode member is not bit-identical with vh_mixtral_seq_decode (GEMM instead of GEMV
+ * summation order).  K / V tile images stay a feature of the one-segment pass. */
+int vh_mixtral_seq_step(vh_mixtral_t* m, const int* pf_seqs /* host */, const int* pf_lens /* host */, int n_pf, const float* embeds,
+                        const int* dec_seqs /* host */, int n_dec, float* logits_out, void* stream);
 int vh_mixtral_pages_free(const vh_mixtral_t* m);
 int vh_mixtral_seq_pos(const vh_mixtral_t* m, int seq);                  /* tokens in the sequence's KV cache, -1 = not live */
 const int* vh_mixtral_seq_tokens(const vh_mixtral_t* m, int seq);        /* device int[max_new]  */
@@ -510,6 +533,22 @@ int vh_attn_decode(const float* qkv, float* kcache, float* vcache, int pos, cons
 int vh_attn_decode_batch(int n, const float* const* qkv, float* kcache, float* vcache, const int* pos, const float* rope_cos,
                          const float* rope_sin, int nq, int nkv, int max_ctx, float scale, const int* const* table,
                          float* const* part_o, float* const* part_ml, int* const* tickets, float* const* attn_out, void* stream);
+/* vh_attn_rows: causal GQA attention of n SINGLE query rows whose q is already rotated, each against its own paged sequence - the
+ *   attention of the decode rows of a mixed pass (vh_mixtral_seq_step).  It replaces, for such a row, a 16-row query tile of the
+ *   prefill's segment attention (one block per KV head walking the whole context) and vh_attn_decode_batch (which wants un-rotated
+ *   q|k|v of at most 4 sequences and appends K / V itself): here nothing is appended, row i attends over keys [0, klens[i]) that are
+ *   in the pool already.  q fp32 row i at q + i * ldq = [nq][128]; pools fp32 [nkv][max_ctx][128] in 64-row pages; klens: HOST
+ *   int[n]; tables: HOST array of n device page tables (ceil(klens[i] / 64) entries each).  Pool rows past a row's klens may hold
+ *   anything.  Two launches: one (m, l, o) partial per (row, head, 64-key tile), then a merge in ascending tile order (no hand-off
+ *   inside a launch).  Output row i: out fp32 [n][ldo] and / or the bf16 hi / lo planes out_hi / out_lo (same stride; hi + lo ~ the
+ *   fp32 value, what vh_gemm_ps reads).  scratch: vh_attn_rows_scratch_bytes(n, nq, max klens) device bytes hold all rows in one
+ *   launch pair; with less (at least the descriptors and one row) the rows run in several.  The descriptor upload is waited for.
+ *   VH_E_ARG: a null or misaligned pointer; VH_E_SHAPE: klens outside [1, max_ctx], heads, strides, scratch too small.  Nothing is
+ *   launched on an error.                                                                                                      */
+size_t vh_attn_rows_scratch_bytes(int n, int nq, int max_klen);
+int vh_attn_rows(int n, const float* q, long ldq, const float* kcache, const float* vcache, const int* klens /* host */,
+                 const int* const* tables /* host */, int nq, int nkv, int max_ctx, float scale, void* scratch, size_t scratch_bytes,
+                 float* out, uint16_t* out_hi, uint16_t* out_lo, long ldo, void* stream);
 /* vh_lmhead_argmax (K27 + K28): logits = lm_head(norm(x + delta)) in fp32 (vita_mixtral.py:171-172) and their argmax
  *   (lowest index on ties, as torch.argmax in HF greedy search).  W bf16 [V][H]; logits fp32 [V]; token_out int[1];
  *   blk_val / blk_idx: nblk floats / ints of scratch (nblk = blocks of the launch, e.g. 1024).                               */

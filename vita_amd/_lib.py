@@ -180,6 +180,9 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vh_attn_decode_batch": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vh_attn_rows_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vh_attn_rows": (c_int, [c_int, c_void_p, c_long, c_void_p, c_void_p, C.POINTER(c_int), c_void_p, c_int, c_int, c_int, c_float,
+                             c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "vh_lmhead_argmax": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int, c_void_p]),
     "vh_mixtral_workspace_bytes": (c_size_t, [C.POINTER(MixtralCfg)]),
@@ -217,6 +220,8 @@ SIGNATURES = {
     "vh_mixtral_seq_free": (c_int, [c_void_p, c_int]),
     "vh_mixtral_seq_prefill": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "vh_mixtral_seq_prefill_batch": (c_int, [c_void_p, C.POINTER(c_int), C.POINTER(c_int), c_int, c_void_p, c_void_p, c_void_p]),
+    "vh_mixtral_seq_step": (c_int, [c_void_p, C.POINTER(c_int), C.POINTER(c_int), c_int, c_void_p, C.POINTER(c_int), c_int, c_void_p,
+                                    c_void_p]),
     "vh_mixtral_seq_decode": (c_int, [c_void_p, C.POINTER(c_int), c_int, c_void_p]),
     "vh_mixtral_pages_free": (c_int, [c_void_p]),
     "vh_mixtral_seq_pos": (c_int, [c_void_p, c_int]),

@@ -47,6 +47,7 @@ int vh_tune(const char* key, int value) {
     if (!strcmp(key, "attn_impl")) { g_tuning.attn_impl = value; return VH_OK; }
     if (!strcmp(key, "attn_fa")) { g_tuning.attn_fa = value; return VH_OK; }
     if (!strcmp(key, "attn_rows")) { g_tuning.attn_rows = value; return VH_OK; }
+    if (!strcmp(key, "step_attn")) { g_tuning.step_attn = value; return VH_OK; }
     if (!strcmp(key, "attn_ksplit")) { g_tuning.attn_ksplit = value; return VH_OK; }
     if (!strcmp(key, "prefill_attn_gemm")) { g_tuning.prefill_attn_gemm = value; return VH_OK; }
     if (!strcmp(key, "prefill_fuse_rows")) { g_tuning.prefill_fuse_rows = value; return VH_OK; }
@@ -328,6 +329,49 @@ int vh_attn_decode_batch(int n, const float* const* qkv, float* kcache, float* v
     const int max_splits = (max_ctx + 63) / 64;
     return check_launch("vh_attn_decode_batch", vhk_decb_attn(S(stream), at, n, kcache, vcache, rope_cos, rope_sin, nq, nkv, max_ctx,
                                                             max_splits, scale));
+}
+
+// scratch of vh_attn_rows: the n descriptors (a 256-byte multiple), then the partials
+static size_t attn_rows_desc_bytes(int n) { return ((size_t)n * sizeof(VhSeg) + 255) / 256 * 256; }
+size_t vh_attn_rows_scratch_bytes(int n, int nq, int max_klen) {
+    if (n < 1 || nq < 1 || max_klen < 1) return 0;
+    return attn_rows_desc_bytes(n) + vhk_attn_rows_scratch_floats(nq, (max_klen + 63) / 64, n) * sizeof(float);
+}
+int vh_attn_rows(int n, const float* q, long ldq, const float* kcache, const float* vcache, const int* klens, const int* const* tables,
+                 int nq, int nkv, int max_ctx, float scale, void* scratch, size_t scratch_bytes, float* out, uint16_t* out_hi,
+                 uint16_t* out_lo, long ldo, void* stream) {
+    const char* what = "vh_attn_rows";
+    if (!q || !kcache || !vcache || !klens || !tables || !scratch || (!out && !out_hi) || (out_hi && !out_lo) || (out_lo && !out_hi))
+        return fail(VH_E_ARG, "%s: null pointer", what);
+    if (n < 1 || n > 65535) return fail(VH_E_SHAPE, "%s: %d rows outside [1, 65535]", what, n);
+    if (nq < 1 || nkv < 1 || max_ctx < 1 || nq % nkv != 0 || nq / nkv > 4)
+        return fail(VH_E_SHAPE, "%s: %d query heads on %d KV heads (1 ... 4 per KV head), pool of %d rows", what, nq, nkv, max_ctx);
+    auto al = [](const void* ptr, uintptr_t a) { return (reinterpret_cast<uintptr_t>(ptr) & (a - 1)) == 0; };
+    if (!al(q, 16) || !al(kcache, 16) || !al(vcache, 16) || !al(scratch, 16) || !al(out, 8) || !al(out_hi, 4) || !al(out_lo, 4))
+        return fail(VH_E_ARG, "%s: misaligned pointer (q, K, V and scratch 16 bytes, out 8, planes 4)", what);
+    if (ldq < (long)nq * 128 || (ldq % 4) != 0 || ldo < (long)nq * 128 || (ldo % 2) != 0)
+        return fail(VH_E_SHAPE, "%s: row strides %ld / %ld below %d floats or not a multiple of 4 / 2", what, ldq, ldo, nq * 128);
+    int kmax = 0;
+    for (int i = 0; i < n; ++i) {
+        if (klens[i] < 1 || klens[i] > max_ctx) return fail(VH_E_SHAPE, "%s: %d keys of row %d outside [1, %d]", what, klens[i], i, max_ctx);
+        if (!tables[i]) return fail(VH_E_ARG, "%s: null page table (row %d)", what, i);
+        if (klens[i] > kmax) kmax = klens[i];
+    }
+    const size_t head = attn_rows_desc_bytes(n);
+    if (scratch_bytes < head + vhk_attn_rows_scratch_floats(nq, (kmax + 63) / 64, 1) * sizeof(float))
+        return fail(VH_E_SHAPE, "%s: %zu bytes of scratch do not hold the descriptors and one row of %d keys (vh_attn_rows_scratch_bytes)", what,
+                    scratch_bytes, kmax);
+    std::vector<VhSeg> sg(n);
+    for (int i = 0; i < n; ++i) sg[i] = VhSeg{i, 1, klens[i] - 1, 0, tables[i]};
+    hipStream_t st = S(stream);
+    // the descriptors go up from host memory that ends with this call: the copy is waited for (an operator entry; the engine keeps its
+    // descriptors in storage that outlives the pass)
+    if (hipMemcpyAsync(scratch, sg.data(), (size_t)n * sizeof(VhSeg), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return fail(VH_E_HIP, "%s: descriptor upload failed", what);
+    return check_launch(what, vhk_attn_rows(st, q, ldq, static_cast<const VhSeg*>(scratch), sg.data(), n, kcache, vcache, nq, nkv, max_ctx,
+                                            scale, reinterpret_cast<float*>(static_cast<char*>(scratch) + head),
+                                            (scratch_bytes - head) / sizeof(float), out, out_hi, out_lo, ldo));
 }
 
 int vh_lmhead_argmax(const float* x, const float* delta, const float* norm_w, float eps, const uint16_t* W, int V, int H,
@@ -1228,7 +1272,9 @@ static int head_one(vh_mixtral* m, hipStream_t st, vh_mixtral::Unit& u, const fl
 // One pass over the weights for the rows of nseg segments, back to back in embeds, each on the unit it names.  One segment: unit 0 (the
 // single-sequence engine, contiguous rows) or a slot.  Several: distinct slots, addressed in place — everything row-wise runs on all
 // Sn rows at once; RoPE + KV write and attention take the segment descriptors, the head runs on the list of units.
-struct PfSeg { int unit, len, pos0; };
+// dec: the segment is ONE DECODE STEP of its unit (a mixed pass, vh_mixtral_seq_step): len 1 at pos0 = the unit's position, its row is the
+// embedding the last select left in the unit's xa, its counters go on, the head runs in mode 1.  Decode segments follow the prefill ones.
+struct PfSeg { int unit, len, pos0; int dec = 0; };
 static int prefill_enqueue(vh_mixtral* m, const float* embeds, const PfSeg* sg, int nseg, float* logits_out, float* hidden_dbg,
                            hipStream_t st);
 // The host mirrors of a prefill move here: a pass that was enqueued whole advances its units; one that was not loses its slots (a
@@ -1246,23 +1292,30 @@ static int prefill_impl(vh_mixtral* m, const float* embeds, const PfSeg* sg, int
 }
 static int prefill_enqueue(vh_mixtral* m, const float* embeds, const PfSeg* sg, int nseg, float* logits_out, float* hidden_dbg,
                            hipStream_t st) {
-    int Sn = 0, kmax = 0;
+    int Sn = 0, kmax = 0, npf = 0, Spf = 0, kmax_pf = 0;
     for (int i = 0; i < nseg; ++i) {
         if (sg[i].len < 1) return fail(VH_E_SHAPE, "prefill length %d outside [1,%d]", sg[i].len, m->c.max_prefill);
         if (sg[i].pos0 < 0 || sg[i].pos0 + sg[i].len >= m->c.max_ctx) return fail(VH_E_SHAPE, "prefill exceeds KV capacity %d", m->c.max_ctx);
+        if (sg[i].dec ? sg[i].len != 1 : npf != i) return fail(VH_E_ARG, "mixed pass: decode segments are single rows behind the prefill segments");
         Sn += sg[i].len;
         if (sg[i].pos0 + sg[i].len > kmax) kmax = sg[i].pos0 + sg[i].len;
+        if (!sg[i].dec) { ++npf; Spf += sg[i].len; kmax_pf = kmax; }
     }
     if (Sn < 1 || Sn > m->c.max_prefill) return fail(VH_E_SHAPE, "prefill length %d outside [1,%d]", Sn, m->c.max_prefill);
-    const bool multi = nseg > 1;
+    const int ndec = nseg - npf;
+    const bool multi = nseg > 1 || ndec > 0;
     const int pos0 = sg[0].pos0;
     vh_mixtral::Unit& u0 = m->units[sg[0].unit];   // the unit of a one-segment pass
     const int H = m->H, nq = m->nq, nkv = m->nkv, hd = m->hd, KO = nq * hd;
     const bool tp = m->c.tp_world > 1 || vh_tuning()->force_allreduce;
     const float scale = 1.0f / sqrtf((float)hd);
     int rc;
-    if (hipMemcpyAsync(m->px, embeds, (size_t)Sn * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+    if (Spf > 0 && hipMemcpyAsync(m->px, embeds, (size_t)Spf * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
         return fail(VH_E_HIP, "prefill: embed copy failed");
+    for (int i = npf; i < nseg; ++i)   // a decode member's row: the embedding its last select left in xa (gathered before any head rewrites it)
+        if (hipMemcpyAsync(m->px + (size_t)(Spf + i - npf) * H, m->units[sg[i].unit].xa, (size_t)H * sizeof(float), hipMemcpyDeviceToDevice,
+                           st) != hipSuccess)
+            return fail(VH_E_HIP, "mixed pass: row gather failed");
     if (multi) {
         // the descriptors go up once, before layer 0, from storage that outlives the copy; every listed slot starts as the unit of a
         // one-segment pass does below (counters 1-3 zeroed)
@@ -1272,7 +1325,7 @@ static int prefill_enqueue(vh_mixtral* m, const float* embeds, const PfSeg* sg, 
             const vh_mixtral::Unit& u = m->units[sg[i].unit];
             m->segs_host[i] = VhSeg{row0, sg[i].len, sg[i].pos0, 0, u.table};
             row0 += sg[i].len;
-            if (hipMemsetAsync(u.counters + 1, 0, 3 * sizeof(int), st) != hipSuccess) return fail(VH_E_HIP, "memset failed");
+            if (!sg[i].dec && hipMemsetAsync(u.counters + 1, 0, 3 * sizeof(int), st) != hipSuccess) return fail(VH_E_HIP, "memset failed");
         }
         if (hipMemcpyAsync(m->seq_segs, m->segs_host.data(), (size_t)nseg * sizeof(VhSeg), hipMemcpyHostToDevice, st) != hipSuccess)
             return fail(VH_E_HIP, "prefill: segment descriptor upload failed");
@@ -1308,6 +1361,11 @@ static int prefill_enqueue(vh_mixtral* m, const float* embeds, const PfSeg* sg, 
         q.Sq = Sn; q.Sk = Sn; q.d = hd; q.Hq = nq; q.Hkv = nkv; q.B = 1; q.causal = 1;
         use_img = vhk_attn_fa_applies(q) != 0;
     }
+    // the single rows of a mixed pass: the split-KV row kernels (head_dim 128, up to 4 query heads per KV head: the geometry they are
+    // written for), with py - idle between the RoPE pass and the O projection - as their scratch; vh_tune("step_attn", 0) or another
+    // geometry: 1-row segments of the segment attention
+    const bool row_attn = ndec > 0 && vh_tuning()->step_attn != 0 && hd == 128 && nq % nkv == 0 && nq / nkv <= 4;
+    const int nsa = row_attn ? npf : nseg, Ssa = row_attn ? Spf : Sn, ksa = row_attn ? kmax_pf : kmax;   // what the segment attention takes
     bool combine_pending = false;
     int pend_nslab = 1;
     const int* pend_nslab_dev = nullptr;
@@ -1366,12 +1424,16 @@ static int prefill_enqueue(vh_mixtral* m, const float* embeds, const PfSeg* sg, 
         a.causal = 1; a.q_off = pos0; a.klen = pos0 + Sn; a.chunk = 0; a.left = -1; a.scale = scale;
         a.ktable = u0.table; a.kv_rows = m->c.max_ctx;
         if (multi) {   // every segment against its own sequence's pages, one call
-            a.segs = m->seq_segs; a.segs_host = m->segs_host.data(); a.nseg = nseg;
-            a.Sk = kmax; a.klen = kmax; a.q_off = 0; a.ktable = nullptr;
+            a.segs = m->seq_segs; a.segs_host = m->segs_host.data(); a.nseg = nsa;
+            a.Sq = Ssa; a.Sk = ksa; a.klen = ksa; a.q_off = 0; a.ktable = nullptr;
         }
         if (use_img) { a.kv_img = m->kv_img; a.img_tiles = m->img_tiles; }
         if (attn_planes) { a.O = nullptr; a.O_hi = m->ph_hi; a.O_lo = m->ph_lo; a.ldo_split = KO; }
-        VH_TRY(vhk_attn(st, a), "attention");
+        if (nsa > 0) VH_TRY(vhk_attn(st, a), "attention");
+        if (row_attn)
+            VH_TRY(vhk_attn_rows(st, m->pq, KO, m->seq_segs + npf, m->segs_host.data() + npf, ndec, kc, vc, nq, nkv, m->c.max_ctx, scale,
+                                 m->py, (size_t)4 * m->down_slab(H), attn_planes ? nullptr : m->pattn, attn_planes ? m->ph_hi : nullptr,
+                                 attn_planes ? m->ph_lo : nullptr, KO), "row attention");
         // ---- O projection
         bool o_pending = false;
         if (stream_attn) {
@@ -1458,7 +1520,12 @@ static int prefill_enqueue(vh_mixtral* m, const float* embeds, const PfSeg* sg, 
         }
         HeadArgs ha;
         ha.mode = 0; ha.set_pos = set_pos.data(); ha.sharded = m->head_sharded(/*loopback_counts=*/false); ha.logits_out = logits_out;
-        if ((rc = head(m, st, us.data(), nseg, xin.data(), dl.data(), ha)) != VH_OK) return rc;
+        if (npf > 0 && (rc = head(m, st, us.data(), npf, xin.data(), dl.data(), ha)) != VH_OK) return rc;
+        if (ndec > 0) {   // the decode members of a mixed pass: a decode step's head (append, pos + 1, counters and draw index go on)
+            HeadArgs hb;
+            hb.sharded = ha.sharded; hb.logits_out = logits_out ? logits_out + (size_t)npf * m->V : nullptr;
+            if ((rc = head(m, st, us.data() + npf, ndec, xin.data() + npf, dl.data() + npf, hb)) != VH_OK) return rc;
+        }
     } else {
         if ((rc = head_one(m, st, u0, m->px + (size_t)(Sn - 1) * H, nullptr, /*mode=*/0, /*set_pos=*/pos0 + Sn, nullptr)) != VH_OK) return rc;
         if (logits_out)
@@ -1873,6 +1940,54 @@ int vh_mixtral_seq_prefill_batch(vh_mixtral_t* m, const int* seqs, const int* le
         if (m->ensure_pages(seqs[i], sg[i].pos0 + lens[i], st) != 0) {
             for (int j = i; j >= 0; --j) {          // pages taken for this call go back, in the order they would be handed out again
                 vh_mixtral::Seq& r = m->seqs[seqs[j]];
+                while (r.npages > had[j]) m->unref_page(r.pages[--r.npages]);
+            }
+            return fail(VH_E_HIP, "page table upload failed");
+        }
+    }
+    return prefill_impl(m, embeds, sg.data(), n, logits_out, nullptr, st);   // enqueued in part: exactly the listed sequences are lost
+}
+
+int vh_mixtral_seq_step(vh_mixtral_t* m, const int* pf_seqs, const int* pf_lens, int n_pf, const float* embeds, const int* dec_seqs,
+                        int n_dec, float* logits_out, void* stream) {
+    const char* what = "vh_mixtral_seq_step";
+    if (!m || (n_pf > 0 && (!pf_seqs || !pf_lens || !embeds)) || (n_dec > 0 && !dec_seqs)) return fail(VH_E_ARG, "%s: null pointer", what);
+    if (n_pf < 0 || n_dec < 0 || n_pf + n_dec < 1 || n_pf + (long)n_dec > (long)m->seqs.size())
+        return fail(VH_E_ARG, "%s: %d prompt segments and %d decode members outside [1,%d] together", what, n_pf, n_dec, (int)m->seqs.size());
+    if (n_dec == 0) return vh_mixtral_seq_prefill_batch(m, pf_seqs, pf_lens, n_pf, embeds, logits_out, stream);
+    hipStream_t st = S(stream);
+    // the whole call is checked before anything is enqueued or allocated
+    const int n = n_pf + n_dec;
+    long rows = 0, pages = 0;
+    for (int i = 0; i < n; ++i) {
+        const bool dec = i >= n_pf;
+        const int s = dec ? dec_seqs[i - n_pf] : pf_seqs[i];
+        const int rc = seq_ok(m, s, what);
+        if (rc != VH_OK) return rc;
+        const int pos = m->slot(s).host_pos, len = dec ? 1 : pf_lens[i];
+        if (m->slot(s).poisoned) return fail(VH_E_ARG, "sequence %d: a previous step failed; free it", s);
+        for (int j = 0; j < i; ++j)
+            if ((j >= n_pf ? dec_seqs[j - n_pf] : pf_seqs[j]) == s) return fail(VH_E_ARG, "%s: sequence %d is listed twice", what, s);
+        if (len < 1) return fail(VH_E_SHAPE, "%s: segment %d has %d rows", what, i, len);
+        if (dec && pos < 1) return fail(VH_E_ARG, "sequence %d has no prompt yet", s);
+        if (pos + (long)len >= m->c.max_ctx)
+            return dec ? fail(VH_E_SHAPE, "sequence %d: context limit %d", s, m->c.max_ctx)
+                       : fail(VH_E_SHAPE, "prefill of %d tokens at %d exceeds the pool", len, pos);
+        rows += len;
+        const int need = (pos + len + 63) / 64;
+        if (need > m->seqs[s].npages) pages += need - m->seqs[s].npages;
+    }
+    if (rows > m->c.max_prefill) return fail(VH_E_SHAPE, "%s: %ld rows exceed max_prefill %d", what, rows, m->c.max_prefill);
+    if (pages > (long)m->free_pages.size())
+        return fail(VH_E_FULL, "KV pool exhausted: %d pages free, the %d members need %ld more", (int)m->free_pages.size(), n, pages);
+    std::vector<PfSeg> sg(n);
+    std::vector<int> ids(n), had(n);
+    for (int i = 0; i < n; ++i) { ids[i] = i >= n_pf ? dec_seqs[i - n_pf] : pf_seqs[i]; had[i] = m->seqs[ids[i]].npages; }
+    for (int i = 0; i < n; ++i) {
+        sg[i] = PfSeg{1 + ids[i], i >= n_pf ? 1 : pf_lens[i], m->slot(ids[i]).host_pos, i >= n_pf ? 1 : 0};
+        if (m->ensure_pages(ids[i], sg[i].pos0 + sg[i].len, st) != 0) {
+            for (int j = i; j >= 0; --j) {          // pages taken for this call go back, in the order they would be handed out again
+                vh_mixtral::Seq& r = m->seqs[ids[j]];
                 while (r.npages > had[j]) m->unref_page(r.pages[--r.npages]);
             }
             return fail(VH_E_HIP, "page table upload failed");

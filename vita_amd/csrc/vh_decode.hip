@@ -1409,6 +1409,151 @@ __global__ __launch_bounds__(256) void k_decb_attn(const VhDecBatchAttn bt, floa
                            bt.part_o[b], bt.part_ml[b], bt.cnt[b], bt.attn_out[b], nq, nkv, max_ctx, max_splits, scale, VhGranVec{}, VhGranVec{});
 }
 
+// ---- attn_rows: split-KV paged attention for single query rows whose q is ALREADY rotated (the decode rows of a mixed pass,
+// vh_mixtral_seq_step).  Row i is row segs[i].row0 of q, sees keys [0, segs[i].pos0 + segs[i].len) of the sequence whose pages
+// segs[i].table lists; its own K / V row is in the pool already (the RoPE pass of the prefill wrote it), nothing is appended.
+// Two launches, no hand-off inside either: k_attn_rows_part writes one (m, l, o[128]) partial per (row, head, 64-key tile) with plain
+// stores, k_attn_rows_merge — a launch boundary later — merges them in ascending tile order with plain loads.
+//   partials: grid (tiles of the longest row, nkv, n); a block past its row's keys returns before any barrier.  As the decode
+//   attention block: one tile in LDS shared by the G <= 4 query heads of the KV head (one wave each), lanes index keys for the
+//   scores and head dims (2 per lane) for PV, fp32 FMA.  Keys past klen in the last tile are masked and their K / V rows
+//   replaced by zeros (a pool row behind a sequence's position may hold anything, NaN included).
+//   part_ml [n][nq][T][2], part_o [n][nq][T][128] with T = the launch's tile count (blockDim.x of the grid), r = the row's index
+//   in the launch.
+__global__ __launch_bounds__(256) void k_attn_rows_part(const float* __restrict__ q, long ldq, const VhSeg* __restrict__ segs,
+                                                        const float* __restrict__ kcache, const float* __restrict__ vcache,
+                                                        float* __restrict__ part_o, float* __restrict__ part_ml, int nq, int nkv,
+                                                        int max_ctx, float scale) {
+    __shared__ __attribute__((aligned(16))) float q_s[4][128];
+    __shared__ __attribute__((aligned(16))) float Kt[DA_KT * DA_KSTR];     // the K tile, then the V tile (row stride 128)
+    float* const Vt = Kt;
+    const VhSeg sg = segs[blockIdx.z];
+    const int klen = sg.pos0 + sg.len;
+    const int t = blockIdx.x, T = gridDim.x, h = blockIdx.y, r = blockIdx.z;
+    const int k0 = t * DA_KT;
+    if (k0 >= klen) return;                                                // (block-uniform)
+    const int k1 = min(klen, k0 + DA_KT);
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int G = nq / nkv;
+    const int head = h * G + wid;
+    const int p0 = sg.table[t] * DA_KT;                                    // first physical row of this tile's page
+
+    f32x4 ktile[8], vtile[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {                                          // unconditional loads from clamped rows (dec_attn_issue)
+        const int idx = tid + i * 256;
+        const int row = idx >> 5, c4 = idx & 31;
+        const int key = min(p0 + row, max_ctx - 1);
+        ktile[i] = reinterpret_cast<const f32x4*>(kcache + ((size_t)h * max_ctx + key) * 128)[c4];
+        vtile[i] = reinterpret_cast<const f32x4*>(vcache + ((size_t)h * max_ctx + key) * 128)[c4];
+    }
+    if (wid < G) {
+        const float* qr = q + (size_t)sg.row0 * ldq + (size_t)head * 128;
+        q_s[wid][lane] = qr[lane];
+        q_s[wid][lane + 64] = qr[lane + 64];
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int idx = tid + i * 256;
+        const int row = idx >> 5, c4 = idx & 31;
+        if (k0 + row >= k1) { ktile[i] = f32x4{0.f, 0.f, 0.f, 0.f}; vtile[i] = ktile[i]; }
+        *reinterpret_cast<f32x4*>(&Kt[row * DA_KSTR + c4 * 4]) = ktile[i];
+    }
+    __syncthreads();
+    float p = 0.f, m = 0.f, l = 0.f;
+    if (wid < G) {
+        const bool valid = (k0 + lane) < k1;
+        float sc = 0.f;
+        const float4* qr = reinterpret_cast<const float4*>(q_s[wid]);
+        const float4* kr = reinterpret_cast<const float4*>(&Kt[lane * DA_KSTR]);
+#pragma unroll
+        for (int i = 0; i < 32; ++i) {
+            const float4 qq = qr[i], kk = kr[i];
+            sc = fmaf(qq.x, kk.x, sc);
+            sc = fmaf(qq.y, kk.y, sc);
+            sc = fmaf(qq.z, kk.z, sc);
+            sc = fmaf(qq.w, kk.w, sc);
+        }
+        sc = valid ? sc * scale : -INFINITY;
+        m = wave_max(sc);                                // finite: the tile holds at least key k0 < klen
+        p = valid ? __expf(sc - m) : 0.f;
+        l = wave_sum(p);
+    }
+    __syncthreads();                                     // every wave is done with the K tile
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int idx = tid + i * 256;
+        *reinterpret_cast<f32x4*>(&Vt[(idx >> 5) * 128 + (idx & 31) * 4]) = vtile[i];
+    }
+    __syncthreads();
+    if (wid < G) {
+        float2 o = make_float2(0.f, 0.f);
+#pragma unroll
+        for (int kk = 0; kk < DA_KT; ++kk) {
+            const float pk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p), kk));
+            const float2 vv = reinterpret_cast<const float2*>(&Vt[kk * 128])[lane];
+            o.x = fmaf(pk, vv.x, o.x);
+            o.y = fmaf(pk, vv.y, o.y);
+        }
+        const size_t at = ((size_t)r * nq + head) * T + t;
+        reinterpret_cast<float2*>(part_o + at * 128)[lane] = o;
+        if (lane == 0) reinterpret_cast<float2*>(part_ml + at * 2)[0] = make_float2(m, l);
+    }
+}
+// merge: one wave per (row, head), 4 per block; the statistics a lane per tile in rounds of 64 tiles, the sums in ascending tile order
+// (dec_attn_finish's merge on plain loads).  Output row segs[i].row0: fp32 (out) and / or the bf16 hi / lo planes the O-projection GEMM reads.
+__global__ __launch_bounds__(256) void k_attn_rows_merge(const VhSeg* __restrict__ segs, int n, const float* __restrict__ part_o,
+                                                         const float* __restrict__ part_ml, int T, int nq, float* __restrict__ out,
+                                                         uint16_t* __restrict__ out_hi, uint16_t* __restrict__ out_lo, long ldo) {
+    const int lane = threadIdx.x & 63;
+    const int item = blockIdx.x * 4 + (threadIdx.x >> 6);                  // (row, head), wave-uniform
+    if (item >= n * nq) return;
+    const int r = item / nq, head = item - r * nq;
+    const VhSeg sg = segs[r];
+    const int ns = (sg.pos0 + sg.len + DA_KT - 1) / DA_KT;
+    const float* ml = part_ml + (size_t)item * T * 2;
+    const float* po = part_o + (size_t)item * T * 128;
+    float M = -INFINITY;
+    for (int s0 = 0; s0 < ns; s0 += 64) {
+        const int sl = s0 + lane;
+        const float mv = sl < ns ? ml[sl * 2] : -INFINITY;
+        M = fmaxf(M, wave_max(mv));
+    }
+    float den = 0.f;
+    float2 num = make_float2(0.f, 0.f);
+    for (int s0 = 0; s0 < ns; s0 += 64) {
+        const int sl = s0 + lane;
+        const float2 mlv = sl < ns ? reinterpret_cast<const float2*>(ml)[sl] : make_float2(-INFINITY, 0.f);
+        const float wl = sl < ns ? __expf(mlv.x - M) : 0.f;
+        const int cnt = min(64, ns - s0);
+        for (int k0 = 0; k0 < cnt; k0 += 8) {
+            float2 ov[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) ov[u] = reinterpret_cast<const float2*>(po + (size_t)(s0 + min(k0 + u, cnt - 1)) * 128)[lane];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                if (k0 + u < cnt) {                  // (wave-uniform)
+                    const float wgt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(wl), k0 + u));
+                    const float lv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mlv.y), k0 + u));
+                    den = fmaf(wgt, lv, den);
+                    num.x = fmaf(wgt, ov[u].x, num.x);
+                    num.y = fmaf(wgt, ov[u].y, num.y);
+                }
+            }
+        }
+    }
+    const float inv = 1.0f / den;
+    const float ox = num.x * inv, oy = num.y * inv;
+    const size_t at = (size_t)sg.row0 * ldo + (size_t)head * 128 + 2 * lane;
+    if (out) *reinterpret_cast<float2*>(out + at) = make_float2(ox, oy);
+    if (out_hi) {
+        uint32_t hi, lo;
+        split_bf16_pair(ox, oy, hi, lo);
+        *reinterpret_cast<uint32_t*>(out_hi + at) = hi;
+        *reinterpret_cast<uint32_t*>(out_lo + at) = lo;
+    }
+}
+
 // final RMSNorm + LM head + per-block argmax for every sequence of the batch (the 424 MB table is read once); SAMP: sequences with
 // hd.sample[b].T > 0 compare z + G (as k_dec_lmhead<SAMP>), the others their logits (in double: the same order and winner); PEN: sequences
 // with a token table (hd.pen[b].seen) compare penalised values, the kept rows stay raw
@@ -1872,6 +2017,37 @@ int vhk_decb_attn(hipStream_t st, const VhDecBatchAttn& bt, int n, float* kcache
     }
     hipLaunchKernelGGL(k_decb_attn, dim3(nkv, ms, n), dim3(256), 0, st, bt, kcache, vcache, rope_cos, rope_sin, nq, nkv,
                        max_ctx, max_splits, scale);
+    return 0;
+}
+size_t vhk_attn_rows_scratch_floats(int nq, int max_tiles, int rows) { return (size_t)rows * nq * max_tiles * 130; }
+// rows that do not fit the scratch together run in several launch pairs (the scratch is reused behind each merge, in stream order)
+int vhk_attn_rows(hipStream_t st, const float* q, long ldq, const VhSeg* segs, const VhSeg* segs_host, int n, const float* kcache,
+                  const float* vcache, int nq, int nkv, int max_ctx, float scale, float* scratch, size_t scratch_floats, float* out,
+                  uint16_t* out_hi, uint16_t* out_lo, long ldo) {
+    if (n < 1 || nkv < 1 || nq % nkv != 0 || nq / nkv > 4 || max_ctx < 1 || !scratch || (!out && !out_hi) || (out_hi && !out_lo)) return -1;
+    const int pool_tiles = (max_ctx + DA_KT - 1) / DA_KT;
+    for (int i = 0; i < n; ++i) {
+        const VhSeg& g = segs_host[i];
+        if (g.len != 1 || g.pos0 < 0 || g.pos0 + 1 > max_ctx || g.row0 < 0 || !g.table) return -1;
+    }
+    for (int i0 = 0; i0 < n;) {
+        int i1 = i0, T = 0;
+        while (i1 < n) {
+            const int tl = (segs_host[i1].pos0 + 1 + DA_KT - 1) / DA_KT;
+            const int Tn = tl > T ? tl : T;
+            if (Tn > pool_tiles || vhk_attn_rows_scratch_floats(nq, Tn, i1 - i0 + 1) > scratch_floats) break;
+            T = Tn; ++i1;
+        }
+        if (i1 == i0) return -1;                         // one row alone does not fit the scratch
+        const int cnt = i1 - i0;
+        float* part_o = scratch;
+        float* part_ml = scratch + (size_t)cnt * nq * T * 128;
+        hipLaunchKernelGGL(k_attn_rows_part, dim3(T, nkv, cnt), dim3(256), 0, st, q, ldq, segs + i0, kcache, vcache, part_o, part_ml,
+                           nq, nkv, max_ctx, scale);
+        hipLaunchKernelGGL(k_attn_rows_merge, dim3((cnt * nq + 3) / 4), dim3(256), 0, st, segs + i0, cnt, part_o, part_ml, T, nq, out,
+                           out_hi, out_lo, ldo);
+        i0 = i1;
+    }
     return 0;
 }
 int vhk_decb_lmhead(hipStream_t st, const VhDecBatchVec& bt, const float* norm_w, float eps, const uint16_t* W, int V, int K,

@@ -40,6 +40,8 @@ struct VhTuning {
     int dec_gateup_grid = 0;   // debug: blocks of the batch-1 gate|up launch (0 = auto: 1.5 per CU, equal shares in few rounds for small shards)
     int comm_allow_coarse = 0; // vh_comm_create: 1 = a coarse-grained receive buffer is acceptable when the fine-grained allocation fails (only
                                // correct when every rank drives ONE device: same-device tests); 0 = fail loudly instead
+    int step_attn = 1;         // single query rows of a mixed pass (vh_mixtral_seq_step): 1 = the split-KV row kernels (vhk_attn_rows), 0 = the segment
+                               // attention, a 1-row segment each
     int comm_ranks_per_device = 1;   // engine processes that drive THIS process's device (vita_amd.parallel counts the ranks from the devices' PCI
                                // identities; vita_amd.duplex sets 2 for replicas on one GPU).  > 1: the bulk all-reduce divides its
                                // resident-block cap by it, the decode exchange is never fused into the kernels, and the attention block of a
@@ -321,6 +323,16 @@ struct VhAttnArgs {
     const VhSeg* segs; const VhSeg* segs_host; int nseg;
     const int* klens;                     // nullable, device int[B]: batch b masks keys >= klens[b] (klen = their maximum); fp32 direct kernel only
 };
+// Split-KV paged attention for n single query rows whose q is already rotated (vh_decode.hip k_attn_rows_part / k_attn_rows_merge: the decode
+// rows of a mixed pass): row i = row segs[i].row0 of q [..][nq][128] (row stride ldq) and of the outputs, keys [0, segs[i].pos0 + 1) of the
+// pages segs[i].table lists (len == 1); K / V pools [nkv][max_ctx][128] fp32; nothing is appended.  segs: device descriptors, segs_host: the
+// same on the host (sizes the grids).  scratch: 130 floats per (row, head, 64-key tile of the launch's longest row); rows that do not fit
+// together run in several launch pairs.  out fp32 rows (stride ldo) and / or out_hi / out_lo bf16 planes (same stride).  0, or -1 (shape /
+// a row that does not fit the scratch alone)
+int vhk_attn_rows(hipStream_t st, const float* q, long ldq, const VhSeg* segs, const VhSeg* segs_host, int n, const float* kcache,
+                  const float* vcache, int nq, int nkv, int max_ctx, float scale, float* scratch, size_t scratch_floats, float* out,
+                  uint16_t* out_hi, uint16_t* out_lo, long ldo);
+size_t vhk_attn_rows_scratch_floats(int nq, int max_tiles, int rows);
 int vhk_attn(hipStream_t st, const VhAttnArgs& a);     // 0, -1 (shape) or -2 (klens with a kernel / mask flavour that has no per-batch form)
 int vhk_attn_fa_applies(const VhAttnArgs& a);    // 1 when vhk_attn would run the flash kernel (k_attn_fa) for these arguments
 

@@ -351,6 +351,27 @@ class MixtralEngine:
               "vh_mixtral_seq_prefill_batch")
         return self.gather_vocab(out) if out is not None else None
 
+    def seq_step(self, prefill_seqs, embeds_list, decode_seqs, want_logits=False):
+        """a MIXED pass over the weights (vh_mixtral_seq_step): embeds_list[i] [S_i, hidden] is appended to sequence prefill_seqs[i] as
+        seq_prefill_batch does, and every sequence of decode_seqs advances one step as seq_decode would advance it, in the same pass.
+        All rows together (prompt rows + one per decode member) must fit max_prefill.  want_logits: the
+        [len(prefill_seqs) + len(decode_seqs), vocab] score rows in list order.  Checked as a whole before anything is enqueued."""
+        if len(prefill_seqs) != len(embeds_list) or len(prefill_seqs) + len(decode_seqs) < 1:
+            raise ValueError("seq_step: one embeds tensor per prompt sequence, at least one member")
+        for e in embeds_list:
+            if e.dtype != torch.float32 or not e.is_cuda or e.dim() != 2:
+                raise TypeError("embeds must be float32 GPU tensors [S, hidden]")
+        n_pf, n_dec = len(prefill_seqs), len(decode_seqs)
+        embeds = None if n_pf == 0 else (embeds_list[0].contiguous() if n_pf == 1 else torch.cat(list(embeds_list), dim=0))
+        ids = (C.c_int * max(n_pf, 1))(*[int(x) for x in prefill_seqs])
+        lens = (C.c_int * max(n_pf, 1))(*[int(e.shape[0]) for e in embeds_list])
+        dec = (C.c_int * max(n_dec, 1))(*[int(x) for x in decode_seqs])
+        out = torch.empty((n_pf + n_dec, self.c.vocab), dtype=torch.float32, device=self.device) if want_logits else None
+        check(self.lib.vh_mixtral_seq_step(self.h, ids, lens, n_pf, embeds.data_ptr() if embeds is not None else None, dec, n_dec,
+                                           out.data_ptr() if out is not None else None, self._stream()),
+              "vh_mixtral_seq_step")
+        return self.gather_vocab(out) if out is not None else None
+
     def seq_decode(self, seqs):
         """one greedy step for every listed sequence (one continuous-batching iteration)."""
         arr = (C.c_int * len(seqs))(*[int(x) for x in seqs])

@@ -575,6 +575,40 @@ def attn_decode_batch(qkvs, kcache, vcache, positions, rope_cos, rope_sin, nq, n
     return [s[3] for s in scratch]
 
 
+def attn_rows_scratch(n, nq, max_klen, device):
+    """scratch of attn_rows that holds n rows of up to max_klen keys in one launch pair (uint8, vh_attn_rows_scratch_bytes)."""
+    nbytes = _lib.load().vh_attn_rows_scratch_bytes(int(n), int(nq), int(max_klen))
+    if nbytes == 0:
+        raise ValueError("attn_rows_scratch: n, nq and max_klen must be positive")
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def attn_rows(q, kcache, vcache, klens, tables, nq, nkv, scale, scratch=None, planes=False):
+    """causal GQA attention of single query rows with q ALREADY rotated (vh_attn_rows, the decode rows of a mixed pass): row i of
+    q [n, nq * 128] fp32 attends over keys [0, klens[i]) of the paged sequence tables[i] (int32 page table on the device) in the
+    pools kcache / vcache fp32 [nkv, max_ctx, 128]; nothing is appended.  -> fp32 [n, nq * 128], or with planes=True the bf16
+    (hi, lo) planes [n, nq * 128] whose sum is that row (what the O-projection GEMM reads)."""
+    _dev(q, kcache, vcache)
+    _f32(q, "q")
+    n, max_ctx = q.shape[0], kcache.shape[1]
+    if q.dim() != 2 or q.stride(1) != 1 or not (n == len(klens) == len(tables)):
+        raise ValueError("attn_rows: q [n, nq * 128] with unit column stride, one key count and page table per row")
+    if scratch is None:
+        scratch = attn_rows_scratch(n, nq, max(int(k) for k in klens), q.device)
+    kl = (C.c_int * max(n, 1))(*[int(k) for k in klens])
+    tb = (C.c_void_p * max(n, 1))(*[None if t is None else t.data_ptr() for t in tables])
+    if planes:
+        hi = torch.empty((n, nq * 128), dtype=torch.bfloat16, device=q.device)
+        lo = torch.empty_like(hi)
+        out = None
+    else:
+        out = torch.empty((n, nq * 128), dtype=torch.float32, device=q.device)
+        hi = lo = None
+    check(_lib.load().vh_attn_rows(n, _p(q), q.stride(0), _p(kcache), _p(vcache), kl, tb, nq, nkv, max_ctx, float(scale), _p(scratch),
+                                   scratch.numel() * scratch.element_size(), _p(out), _p(hi), _p(lo), nq * 128, _stream()), "vh_attn_rows")
+    return (hi, lo) if planes else out
+
+
 def lmhead_argmax(x, norm_w, eps, w, delta=None, nblk=1024):
     """logits = lm_head(rmsnorm(x + delta)) fp32 [V] and their argmax (int32 [1], lowest index on ties)."""
     _dev(x, w)

@@ -27,6 +27,7 @@ class Request:
     hit: int = 0                                              # _open(), with a cache: pages adopted at this admission
     keys: List[bytes] = field(default_factory=list)           # _lookup() / _register_written(): chain keys of the blocks hashed so far
     fresh: bool = False                                       # _start(): the prefill's token is not reported yet; harvest clears it
+    done: int = 0                                             # chunked prefill: rows of `suffix` already enqueued (mid-prompt while 0 < done < len)
 
     @property
     def rows(self):
@@ -190,20 +191,42 @@ class ContinuousBatcher:
     stats: prefix_queries (lookups), prefix_hit_tokens, prefix_evictions, prefill_rows (rows sent to prefill calls, counted with the
     cache off as well).  Side tables by request id, each entry the caller's to pop: errors (the exception behind an "error" event),
     logprobs (per-token {id: logprob} of a request with rules["logprobs"] >= 0) and cached_tokens (the hit of its first admission); a
-    request that fails or is aborted loses the last two here (_drop)."""
+    request that fails or is aborted loses the last two here (_drop).
 
-    def __init__(self, engine, embed_tokens=None, max_batch=None, window=1, prefix_cache=False):
+    chunked_prefill=True (vLLM's enable_chunked_prefill, on an engine that has seq_step): an iteration that has prompt
+    rows is ONE pass over the weights.  Every running sequence takes one row of the budget max_batched_tokens (default and upper
+    bound: max_prefill), the rest goes to prompts in admission order — first the request that is mid-prompt, then newly admitted
+    ones; a prompt larger than what is left contributes a chunk and its request stays in `prefilling` (it holds its slot and counts
+    against max_batch, it is not in `running` and is not harvested) until its last chunk, whose token is its first output: the
+    rules are armed in front of that chunk and the prompt's pages are registered with the prefix cache behind it.  One seq_step call
+    replaces the prefill call and the first decode step of the window; the other window - 1 steps are seq_decode calls over
+    everyone who has a token.  An iteration without prompt rows is today's (seq_decode).  If seq_step raises, the iteration falls
+    back to prefill calls and a seq_decode, so that only a culprit fails.  A mid-prompt request yields its slot before any running
+    sequence is preempted and re-queues with its full prompt.  stats: mixed_steps (seq_step calls), mixed_rows (their rows);
+    prefill_rows counts chunk rows."""
+
+    def __init__(self, engine, embed_tokens=None, max_batch=None, window=1, prefix_cache=False, chunked_prefill=False,
+                 max_batched_tokens=None):
         self.eng, self.embed_tokens = engine, embed_tokens
         self.cache = prefix_cache if isinstance(prefix_cache, PrefixCache) else (PrefixCache(engine) if prefix_cache else None)
         self.max_batch = int(max_batch or engine.c.max_seqs)
         if engine.c.max_seqs < 1:
             raise ValueError("the engine was created without sequence slots (max_seqs = 0)")
         self.window = int(window)
+        self.budget = int(max_batched_tokens) if max_batched_tokens is not None else int(engine.max_prefill)
+        if self.budget > engine.max_prefill:
+            raise ValueError(f"max_batched_tokens {self.budget} exceeds the engine's max_prefill {engine.max_prefill}")
+        if chunked_prefill and self.budget <= self.max_batch:
+            raise ValueError(f"max_batched_tokens {self.budget} leaves no prompt row next to {self.max_batch} running sequences")
+        self.chunked = bool(chunked_prefill) and hasattr(engine, "seq_step")
         self.waiting = collections.deque()
         self.running = []                 # admission order
+        self.prefilling = []              # chunked prefill: admitted requests whose prompt is not enqueued whole yet, admission order
         self.errors, self.logprobs, self.cached_tokens = {}, {}, {}
         self.stats = {"iterations": 0, "prefills": 0, "prefill_calls": 0, "preemptions": 0, "decode_steps": 0, "failed": 0,
                       "prefix_queries": 0, "prefix_hit_tokens": 0, "prefix_evictions": 0, "prefill_rows": 0}
+        if chunked_prefill:               # (the keys exist with the flag on only: with it off the stats are what they were)
+            self.stats.update(mixed_steps=0, mixed_rows=0)
 
     def add(self, request_id, embeds, max_tokens, eos=(), sampling=None, rules=None, prompt_ids=None):
         """sampling: None (greedy) or the keywords of MixtralEngine.seq_set_sampling without draw0 (see sampling_of).
@@ -226,15 +249,25 @@ class ContinuousBatcher:
 
     def abort(self, request_id):
         self._drop(request_id)
-        r = next((r for r in (*self.running, *self.waiting) if r.id == request_id), None)
-        if r is not None and r.seq is not None:           # running: it holds a slot
+        r = next((r for r in (*self.running, *self.prefilling, *self.waiting) if r.id == request_id), None)
+        if r is not None and r in self.prefilling:        # mid-prompt: its slot and pages go back, nothing of it is registered
+            self._unslot(r)
+        elif r is not None and r.seq is not None:         # running: it holds a slot
             self._retire(r)
         elif r is not None:
             self.waiting.remove(r)
         return r is not None
 
     def has_work(self):
-        return bool(self.waiting or self.running)
+        return bool(self.waiting or self.running or self.prefilling)
+
+    def _unslot(self, r):
+        """a request that is (or may be) mid-prompt gives its slot back"""
+        if r in self.prefilling:
+            self.prefilling.remove(r)
+        if r.seq is not None:
+            self.eng.seq_free(r.seq)
+        r.seq, r.done, r.hit = None, 0, 0
 
     def _retire(self, r):
         """a running request ends (finished or aborted): its written pages stay findable, its slot goes back"""
@@ -302,20 +335,22 @@ class ContinuousBatcher:
     def _fail(self, r, exc, events):
         """ONE request failed (its prompt does not fit, its prefill was rejected): it ends with an "error" event, nobody else
         is touched; its slot, if it has one, goes back.  Device-level failures (spin time-outs, launch errors) still propagate."""
-        if r.seq is not None:
-            self.eng.seq_free(r.seq)
-            r.seq = None
+        self._unslot(r)
         self.errors[r.id] = exc
         self._drop(r.id)
         self.stats["failed"] += 1
         events.append((r.id, [], True, "error"))
+
+    def _promised(self, g):
+        """pages of the pool that are promised to the rest of g's prompt"""
+        return _pages(g.rows) - (g.hit if g.done == 0 else len(self.eng.seq_pages(g.seq)))
 
     def _room_for(self, r, group):
         """page accounting for the head of the queue -> the cached pages r adopts (pinned; [] without a cache), None when r has to
         wait for pages, or the error of a prompt that the empty pool cannot hold."""
         # the pool as it will be once the group is prefilled: the pages promised to its prompts are gone, its members run
         # (pages a member adopted from the prefix cache are in its table already)
-        free = self.eng.pages_free() - sum(_pages(g.rows) - g.hit for g in group)
+        free = self.eng.pages_free() - sum(self._promised(g) for g in group)
         n_run = len(self.running) + len(group)
         need = _pages(r.rows + 1) + n_run                           # + one page of headroom per runner
         hit = []
@@ -334,8 +369,9 @@ class ContinuousBatcher:
             return RuntimeError(f"request {r.id}: prompt needs {need} KV pages, the pool has {free}")
         return None
 
-    def _open(self, r, hit, events):
-        """a slot for r with its adopted pages, its sampling and its rules -> True; a failure ends r alone (_fail frees the slot)."""
+    def _open(self, r, hit, events, arm=True):
+        """a slot for r with its adopted pages, its sampling and its rules -> True; a failure ends r alone (_fail frees the slot).
+        arm=False (chunked prefill): the rules are armed in front of the last chunk, whenever that is."""
         try:
             r.seq = self.eng.seq_alloc()
             if self.cache is not None:
@@ -349,7 +385,7 @@ class ContinuousBatcher:
                 # draw index of the next token = tokens already generated (r.base after a recompute preemption): the continued
                 # ids are the ones an unpreempted run draws
                 self.eng.seq_set_sampling(r.seq, draw0=r.base, **r.sampling)
-            if len(r.suffix) <= self.eng.max_prefill:        # (a chunked re-prompt arms its rules in front of its last chunk: _prefill)
+            if arm and len(r.suffix) <= self.eng.max_prefill:        # (a chunked re-prompt arms its rules in front of its last chunk: _prefill)
                 self._arm(r)
             return True
         except Exception as e:
@@ -423,11 +459,17 @@ class ContinuousBatcher:
     def _preempt_for(self, steps):
         """make sure `steps` decode steps of every running sequence find their pages; youngest sequences yield."""
         while True:
-            new_pages = sum(self._growth(r, steps) for r in self.running)
+            new_pages = sum(self._growth(r, steps) for r in self.running) + sum(self._promised(g) for g in self.prefilling)
             short = new_pages - self.eng.pages_free()
             if short > 0 and self.cache is not None:              # cached pages yield before a running sequence does
                 self.stats["prefix_evictions"] += self.cache.evict(short)
                 short = new_pages - self.eng.pages_free()
+            if short > 0 and self.prefilling and self.running:    # a mid-prompt request (the youngest, nothing produced yet) yields first
+                g = self.prefilling[-1]
+                self._unslot(g)
+                self.waiting.appendleft(g)
+                self.stats["preemptions"] += 1
+                continue
             if short <= 0 or len(self.running) <= 1:
                 return
             r = self.running.pop()
@@ -475,8 +517,120 @@ class ContinuousBatcher:
         if accepted or reason:
             return (r.id, accepted, reason is not None, reason or "")
 
+    # ---- chunked prefill -----------------------------------------------------------------------------------------------------
+    def _admit_chunked(self):
+        """admission as _admit does it (slot, page accounting over the whole prompt, adoption), without the prefill: the admitted
+        requests join `prefilling`.  Nobody is admitted whose first row would not fit this iteration's budget."""
+        events = []
+        left = self.budget - len(self.running) - sum(len(g.suffix) - g.done for g in self.prefilling)
+        while self.waiting and left > 0 and len(self.running) + len(self.prefilling) < self.max_batch:
+            r = self.waiting[0]
+            hit = self._room_for(r, self.prefilling)
+            if hit is None:
+                break
+            self.waiting.popleft()
+            if isinstance(hit, Exception):
+                self._fail(r, hit, events)
+                continue
+            if self._open(r, hit, events, arm=False):
+                self.prefilling.append(r)
+                left -= len(r.suffix)
+        if self.cache is not None:
+            self.cache.pinned.clear()
+        return events
+
+    def _mixed_pass(self, dec, events):
+        """the prompt rows of this iteration and one decode step of the sequences `dec` in ONE pass (seq_step) -> the requests
+        whose last chunk it carried (they run from here on)."""
+        left = self.budget - len(dec)
+        chunks = []                       # (request, rows of its suffix in this pass)
+        for g in self.prefilling:
+            n = min(len(g.suffix) - g.done, left)
+            if n <= 0:
+                break
+            chunks.append((g, n))
+            left -= n
+        last = [g for g, n in chunks if g.done + n == len(g.suffix)]
+        for g in last:
+            self._arm(g)                  # only the LAST chunk's token is an output (the table counts it)
+        rows = [g.suffix[g.done:g.done + n] for g, n in chunks]
+        try:
+            self.eng.seq_step([g.seq for g, _ in chunks], rows, [r.seq for r in dec])
+            ok = True
+        except Exception:
+            ok = False
+        if ok:
+            self.stats["mixed_steps"] += 1
+            self.stats["mixed_rows"] += sum(n for _, n in chunks) + len(dec)
+            self.stats["prefill_calls"] += 1
+            self.stats["prefill_rows"] += sum(n for _, n in chunks)
+            for g, n in chunks:
+                g.done += n
+            for g in last:
+                self.prefilling.remove(g)
+                self._start(g, events, prefilled=True)
+        else:
+            # today's sequence: whole prompts as a group (one batched call, retried one by one), chunks by seq_prefill, then the
+            # decode step; a rejected seq_step touched nothing, so only a culprit ends with an "error" event
+            group = [g for g, n in chunks if g.done == 0 and g in last]
+            for g, n in chunks:
+                if g in group:
+                    self.prefilling.remove(g)
+                    continue
+                try:
+                    self.eng.seq_prefill(g.seq, g.suffix[g.done:g.done + n])
+                    self.stats["prefill_calls"] += 1
+                    self.stats["prefill_rows"] += n
+                    g.done += n
+                    if g in last:
+                        self.prefilling.remove(g)
+                        self._start(g, events, prefilled=True)
+                except Exception as e:
+                    self._fail(g, e, events)
+            self._prefill_group(group, events)
+            last = [g for g in last if g in self.running]
+            if dec:
+                self.eng.seq_decode([r.seq for r in dec])
+        self.stats["decode_steps"] += len(dec)
+        return last
+
+    def _step_chunked(self):
+        events = self._admit_chunked()
+        if not self.running and not self.prefilling:
+            return events
+        # decode window of the running sequences, bounded as in step(); the pages the mid-prompt requests were promised stay theirs
+        steps, starved, had = self.window, None, bool(self.running)
+        for r in self.running:
+            steps = min(steps, self.eng.max_new - len(r.gen) - r.fresh, self.eng.max_ctx - 2 - self.eng.seq_pos(r.seq))
+        steps = max(steps, 0)
+        self._preempt_for(steps)
+        if steps > 0 and len(self.running) == 1 and not self.prefilling and self._growth(self.running[0], steps) > self.eng.pages_free():
+            starved, steps = self.running[0], 0               # alone and the pool is dry: it ends here ("length")
+        if self.prefilling:
+            dec = list(self.running) if steps > 0 else []
+            started = self._mixed_pass(dec, events)           # the prompt rows + the first step of the window
+            steps = steps - 1 if dec else (0 if had else self.window - 1)
+            for r in started:                                 # their first token is out: what is left of the window is theirs too
+                steps = min(steps, self.eng.max_new - 1, self.eng.max_ctx - 2 - self.eng.seq_pos(r.seq))
+            steps = max(steps, 0)
+            if steps > 0 and self.running:
+                self._preempt_for(steps)
+                if len(self.running) == 1 and self._growth(self.running[0], steps) > self.eng.pages_free():
+                    steps = 0                                 # (a lone sequence on a dry pool: its next iteration ends it)
+        if steps > 0 and self.running:
+            ids = [r.seq for r in self.running]
+            for _ in range(steps):
+                self.eng.seq_decode(ids)
+            self.stats["decode_steps"] += steps * len(ids)
+        self.stats["iterations"] += 1
+        torch.cuda.current_stream().synchronize()
+        harvest = [self._harvest(r, r is starved) for r in list(self.running)]
+        return events + [ev for ev in harvest if ev is not None]
+
     @torch.no_grad()
     def step(self):
+        if self.chunked:
+            return self._step_chunked()
         events = self._admit()
         if not self.running:
             return events

@@ -177,12 +177,16 @@ class LLM:
     def __init__(self, model, dtype=None, tensor_parallel_size=1, trust_remote_code=True, gpu_memory_utilization=None,
                  disable_custom_all_reduce=True, limit_mm_per_prompt=None, max_new_tokens=1024, device="cuda",
                  max_num_seqs=0, kv_pool_tokens=None, quantization=None, max_logprobs=0, penalty_tables=None,
-                 enable_prefix_caching=False, **_):
+                 enable_prefix_caching=False, enable_chunked_prefill=False, max_num_batched_tokens=None, **_):
         from .model.builder import load_pretrained_model
         # vLLM's switch: AsyncLLMEngine's batcher then keeps finished prompts' KV pages under content keys (PrefixCache).  generate()
         # here serves one request at a time on the contiguous pool and does not use the cache; the engine refuses it while the cache
         # holds pages (its error names reset_prefix_cache)
         self.enable_prefix_caching = bool(enable_prefix_caching)
+        # vLLM's switches: AsyncLLMEngine's batcher then runs prompt chunks and the running sequences' decode steps in one pass over the
+        # weights, at most max_num_batched_tokens rows per pass (ContinuousBatcher chunked_prefill; default: the engine's max_prefill)
+        self.enable_chunked_prefill = bool(enable_chunked_prefill)
+        self.max_num_batched_tokens = max_num_batched_tokens
         # vLLM's quantization="experts_int8": the MoE experts as int8 with per-output-row scales
         # "experts_mxfp4": the experts as OCP MXFP4 (e2m1 codes, one power-of-two scale per 32 weights)
         if quantization not in (None, "experts_int8", "experts_mxfp4"):
@@ -400,6 +404,8 @@ class AsyncEngineArgs:
     quantization: Optional[str] = None       # None, "experts_int8" or "experts_mxfp4" (LLM)
     max_logprobs: int = 0                    # > 0 (<= 20): SamplingParams' penalties and logprobs on the device (LLM)
     enable_prefix_caching: bool = False      # reuse the KV pages of earlier prompts with the same leading rows (ContinuousBatcher)
+    enable_chunked_prefill: bool = False     # prompt chunks and the running sequences' decode steps in ONE pass over the weights
+    max_num_batched_tokens: Optional[int] = None   # rows of such a pass (default and upper bound: the engine's max_prefill)
 
 
 class AsyncLLMEngine:
@@ -413,13 +419,19 @@ class AsyncLLMEngine:
     stream (encoders + prefill of admitted requests, then one decode step for every running sequence per iteration) and
     posts RequestOutputs to the callers' event loops."""
 
-    def __init__(self, llm: "LLM", max_num_seqs=None, window=1, enable_prefix_caching=None):
+    def __init__(self, llm: "LLM", max_num_seqs=None, window=1, enable_prefix_caching=None, enable_chunked_prefill=None,
+                 max_num_batched_tokens=None):
         self.llm = llm
         eng = llm.model.engine
         if enable_prefix_caching is None:
             enable_prefix_caching = getattr(llm, "enable_prefix_caching", False)
+        if enable_chunked_prefill is None:
+            enable_chunked_prefill = getattr(llm, "enable_chunked_prefill", False)
+        if max_num_batched_tokens is None:
+            max_num_batched_tokens = getattr(llm, "max_num_batched_tokens", None)
         self.batcher = ContinuousBatcher(eng, embed_tokens=lambda ids: llm.model.model.embed_tokens(ids),
-                                         max_batch=max_num_seqs, window=window, prefix_cache=bool(enable_prefix_caching))
+                                         max_batch=max_num_seqs, window=window, prefix_cache=bool(enable_prefix_caching),
+                                         chunked_prefill=bool(enable_chunked_prefill), max_batched_tokens=max_num_batched_tokens)
         self._cache_resets = []           # threading.Event per pending reset_prefix_cache()
         self._lock = threading.Lock()
         self._cv = threading.Condition(self._lock)
@@ -435,7 +447,8 @@ class AsyncLLMEngine:
                   gpu_memory_utilization=args.gpu_memory_utilization,
                   limit_mm_per_prompt=args.limit_mm_per_prompt, max_new_tokens=args.max_new_tokens, device=args.device,
                   max_num_seqs=args.max_num_seqs, kv_pool_tokens=pool, quantization=args.quantization,
-                  max_logprobs=args.max_logprobs, enable_prefix_caching=args.enable_prefix_caching)
+                  max_logprobs=args.max_logprobs, enable_prefix_caching=args.enable_prefix_caching,
+                  enable_chunked_prefill=args.enable_chunked_prefill, max_num_batched_tokens=args.max_num_batched_tokens)
         return cls(llm, max_num_seqs=args.max_num_seqs, **kw)
 
     def reset_prefix_cache(self, timeout=30.0):
